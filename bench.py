@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark of the fused sim+voxel hot path (BASELINE.json metric:
 "voxel grids/sec (B x Tbins x H x W) at 1/2/4/8 GPU; achieved HBM GB/s vs peak").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--all-workloads]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path (ONE launch of v2v_esim_voxel_hip) over one batch of synthetic clips that is
@@ -10,11 +10,15 @@ already resident in HBM.  Workload at N=1: BASELINE configs[1] -- 256 clips of 3
 C+ = C- = 0.2, 5 temporal-bilinear voxel bins, simulated with the REFERENCE'S OWN EventEmulator constructor defaults
 (data/v2v_core_esim.py:8-16: base_noise_std 0.1, hot_pixel_fraction 1e-3, hot_pixel_std 0.1), i.e. with the noise the
 reference always applies.  With N>1 GPUs every rank gets its own 256 clips (global clip ids rank*256..), no data-path
-collective: weak scaling.  Rank 0 prints ONE JSON line, last and alone on stdout, at most 4 KB: the contract keys only.  The
-default run also times one workload of every other BASELINE config (`also_measured`: own kernel time, algorithmic bytes,
-fraction of the HBM peak) and the loader at the training shape, outside the timed region and after the headline; those,
-the launch trace and the secondary CPU baselines go to the sidecar file the line names (`extra`: bench_extra.json).
-`--full` runs every variant.  They are parity-test cases and secondary measurements, never the headline.
+collective: weak scaling.  Rank 0 prints ONE JSON line, last and alone on stdout, at most 4 KB: the contract keys only.
+
+A plain run sets up, warms up, times the K steps, writes rank 0's outputs of the last timed step when --dump-outputs is given,
+and prints the line: nothing else runs, so its time outside the steps is start-up alone.  `--full` adds, outside the timed
+region and after the headline: 100 more launches once the clocks have settled, one workload of every other BASELINE config
+(`also_measured`: own kernel time, algorithmic bytes, fraction of the HBM peak), the loader at the training shape, the
+host-input leg, the parity guard against the C oracle and the CPU baselines; the launch trace and the secondary figures go to
+the sidecar file the line names (`extra`: bench_extra.json).  `--all-workloads` (implies --full) runs every variant.  They are
+parity-test cases and secondary measurements, never the headline.
 """
 import argparse
 import json
@@ -229,7 +233,7 @@ class Workload:
         n, h, w, bin_mode, tb, fpb, params = wl["n"], wl["h"], wl["w"], wl["bin"], wl["tb"], wl["fpb"], wl["params"]
         tdtype = getattr(torch, wl["dtype"])
         self.clip_id0 = clip_id0 = sharding.weak_shard(b, rank, world).lo          # batch shard: global clip ids, no exchange
-        self.raw = None
+        self.raw = self.pred = None
         if wl["model"] == "pipeline":
             import numpy as np
             from v2v_amd import frontend
@@ -300,7 +304,7 @@ class Workload:
                                       seed=20240001, clip_id0=clip_id0, out=out, validate=False, no_noise=False)
                 if consumer is not None:
                     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
-                        forward_sequence(consumer, out, channels_last=c_last)
+                        self.pred = forward_sequence(consumer, out, channels_last=c_last)   # under hipGraph replay: the graph's own output
         elif wl["model"] == "train_batch":
             from v2v_amd import _lib, postops
             ptensor = torch.tensor([params] * b, dtype=torch.float64, device=dev)
@@ -368,6 +372,16 @@ class Workload:
             verdicts.append("ok" if np.allclose(got, want, rtol=1e-5, atol=1e-5) else "MISMATCH")
         return verdicts[0] if len(set(verdicts)) == 1 else "; ".join(verdicts)
 
+    def outputs(self):
+        """What a caller of step() receives from its last call: the voxel grids, plus the per-clip scales (training batch) or the
+        consumer's predictions (config 5)."""
+        outs = {"voxels": self.out}
+        if self.wl["model"] == "train_batch":
+            outs["scales"] = self.scales
+        if self.pred is not None:
+            outs["predictions"] = self.pred
+        return outs
+
     def free(self):
         self.frames = self.out = self.raw = self.step = None
 
@@ -407,6 +421,7 @@ class StreamWorkload:
             import loader_bench
             from torch.utils.data import DistributedSampler
             from v2v_amd.loader import RingLoader
+            torch.manual_seed(0)                  # the shuffle order and the workers' seeds: the same batches from run to run
             self._tmp = tempfile.TemporaryDirectory()
             n_samples = (steps_needed + 4) * b * world
             ds = loader_bench.make_dataset(self._tmp.name, (n_samples + 1) // 2, loader_bench.PooledFrameSource(), defer_sim=True)   # 2 samples per listed video
@@ -482,6 +497,19 @@ class StreamWorkload:
             return self.loader.bytes_copied / max(1, self.loader.batches_copied)
         return float(self.crop_bytes if self.cfg["zero_copy"] else self.raw_bytes)   # zero-copy: algorithmic (the rectangles once; tile halos re-read a little)
 
+    def outputs(self):
+        """What a caller of step() receives from its last call: the RingLoader's batch (its tensors; `v2e_params` flattened to
+        `v2e_params_<key>`), or the config-4 voxel grids."""
+        import torch
+        if self.cfg["kind"] != "ring":
+            return {"voxels": self.out}
+        outs = {}
+        for k, v in self.last.items():
+            for kk, vv in (v.items() if isinstance(v, dict) else [(None, v)]):
+                if torch.is_tensor(vv):
+                    outs[k if kk is None else f"{k}_{kk}"] = vv
+        return outs
+
     def close(self):
         if self.cfg["kind"] == "ring":
             self._it = self.last = None
@@ -509,10 +537,12 @@ def run_stream(args, torch, dev, rank, local_rank, world, dist, backend):
     per_rank_ms = sharding.gather_floats(dist, my_elapsed / args.steps * 1e3, dev)
     h2d = S.h2d_bytes_per_step()
     per_rank_gbps = sharding.gather_floats(dist, h2d / (my_elapsed / args.steps) / 1e9, dev)
-    gpu_ms = S.gpu_only_ms() if rank == 0 else None                        # the same launches on device-resident input: what the kernels alone take
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(S.outputs(), args.dump_outputs)
+    gpu_ms = S.gpu_only_ms() if rank == 0 and args.full else None         # the same launches on device-resident input: what the kernels alone take
     if rank == 0:
         cfg = S.cfg
-        achieved = S.alg_bytes / (gpu_ms * 1e-3) / 1e9
+        achieved = S.alg_bytes / (gpu_ms * 1e-3) / 1e9 if gpu_ms else None
         line = {
             "metric": "voxel grids/sec", "value": S.grids_per_step * world * args.steps / elapsed, "unit": "voxel grids/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -525,10 +555,11 @@ def run_stream(args, torch, dev, rank, local_rank, world, dist, backend):
                        "sharding": f"one stream per rank, {world} rank(s), no collective"},
             "stream": {"samples_per_s": cfg["b"] * world * args.steps / elapsed, "h2d_bytes_per_step_per_rank": h2d,
                        "pcie_GBps_per_rank": [round(v, 2) for v in per_rank_gbps], "gpu_only_ms_per_step": gpu_ms,
-                       "gpu_busy_fraction_rank0": gpu_ms / per_rank_ms[0]},
+                       "gpu_busy_fraction_rank0": gpu_ms / per_rank_ms[0] if gpu_ms else None},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": None,
                          "kernel": S.kernel_name, "algorithmic_bytes_per_launch": S.alg_bytes, "kernel_ms_avg": gpu_ms,
-                         "note": "the step's kernels timed on device-resident input (HIP events); the stream itself is PCIe / host bound, see `stream`"},
+                         "note": "the step's kernels timed on device-resident input (HIP events); the stream itself is PCIe / host bound, see `stream`"}
+                        if gpu_ms else None,                              # a run of its own: --full
             "cpu_baseline": None, "parity_check": None, "extra": None,
         }
         sys.stderr.flush()
@@ -645,17 +676,17 @@ def load_traffic(name):
 
 MAX_LINE_BYTES = 4096      # the contract line stays far below what the driver's stdout tail keeps (round 4's 21.9 KB line was cut: parsed = null)
 
-# secondary workloads of the default run (one of each kind); --full adds the rest
+# secondary workloads of --full (one of each kind); --all-workloads adds the rest
 ALSO_DEFAULT = ["cfg2_dataset_style", "cfg2_u8", "cfg3_v2e_f32_256x32x256x256_bilinear5", "cfg4_pipeline_720p_to_256_40f_bilinear5",
                 "train_u8_12x201x128x128_sum5", "train_batch_normalised_12x201x128x128", "cfg5_fused_convlstm_channels_last"]
 
 
-def measure_secondary(torch, dev, full, lap, kernels_only=False):
+def measure_secondary(torch, dev, all_workloads, lap, kernels_only=False):
     """Rank 0 at N = 1, after the headline's launches have warmed the clocks and outside the timed region: each secondary workload's own
     kernel time (3 warm-up + 12 timed launches), algorithmic bytes and fraction of the HBM peak; then the loader at the training
     shape (tools/loader_bench.py) and the consumer's ConvLSTM step against the bf16 matrix peak.  Never the headline value."""
     also = {}
-    for name in (ALSO_MEASURED if full else ALSO_DEFAULT):
+    for name in (ALSO_MEASURED if all_workloads else ALSO_DEFAULT):
         try:
             S = Workload(name, dev, 0, 1)
             for _ in range(3):
@@ -686,9 +717,9 @@ def measure_secondary(torch, dev, full, lap, kernels_only=False):
         # YAML only (train.py untouched), + one line of train.py (RingLoader), the reference's deployment (NumPy port in workers)
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import loader_bench
-        also["train_loader_b12_201x128x128"] = loader_bench.measure(batches=200 if full else 60, workers=9, batch=12, dev=dev,
-                                                                    simulating_batches=40 if full else 0, cpu_port_budget_s=60.0 if full else 8.0,
-                                                                    consumer_batches=20 if full else 6, yaml_only_host_return_batches=10 if full else 0)
+        also["train_loader_b12_201x128x128"] = loader_bench.measure(batches=200 if all_workloads else 60, workers=9, batch=12, dev=dev,
+                                                                    simulating_batches=40 if all_workloads else 0, cpu_port_budget_s=60.0 if all_workloads else 8.0,
+                                                                    consumer_batches=20 if all_workloads else 6, yaml_only_host_return_batches=10 if all_workloads else 0)
     except Exception as exc:  # noqa: BLE001
         also["train_loader_b12_201x128x128"] = {"error": f"{type(exc).__name__}: {exc}"}
     lap("train_loader")
@@ -757,6 +788,32 @@ def write_sidecar(obj, path):
         except OSError as exc:
             print(f"[bench] could not write {target}: {exc}", file=sys.stderr, flush=True)
     return written
+
+
+DUMP_LIMIT_BYTES = 60 << 20     # all arrays of one --dump-outputs together (the headline's grids are 320 MiB: a sample of them)
+
+
+def dump_outputs(outputs, out_dir, limit=DUMP_LIMIT_BYTES):
+    """`--dump-outputs DIR`: `outputs` (name -> device tensor, or a list of per-time-step tensors) as DIR/<name>.npy, float64 where the
+    output is float64 or integer, float32 otherwise.  When they exceed `limit` bytes in all, every array keeps the same share of its
+    leading (clip) axis: the sorted indices np.random.default_rng(0).choice(n, k, replace=False) -- the same clips in every run with the
+    same arguments, so that two builds can be compared output for output."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for name, t in outputs.items():
+        if isinstance(t, (list, tuple)):
+            t = torch.stack(list(t), 1)                                            # [B, T, ...]
+        wide = t.dtype == torch.float64 or not t.is_floating_point()
+        arrays[name] = (t, torch.float64 if wide else torch.float32)
+    total = sum(t.numel() * (8 if dt == torch.float64 else 4) for t, dt in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (t, dt) in arrays.items():
+        if total > limit and t.dim() > 0:
+            n = t.shape[0]
+            idx = np.sort(np.random.default_rng(0).choice(n, max(1, n * limit // total), replace=False))
+            t = t[torch.as_tensor(idx, device=t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.to(dt).cpu().numpy())
 
 
 def contract_line(*, workload, wl, clips_per_gpu, grids_per_step, alg_bytes, kernel_name, world, steps, warmup, elapsed_s, per_rank_ms, kern_ms_sorted,
@@ -828,11 +885,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS) + sorted(STREAM_WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="override clips per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary workloads of the default run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what rank 0's last timed step computed as DIR/<name>.npy (float32 / float64; a seeded sample of clips beyond 60 MiB)")
+    ap.add_argument("--full", action="store_true", help="after the headline: settled-clock launches, the secondary workloads, the loader bench, the "
+                                                        "host-input leg, the parity guard, the CPU baselines and the sidecar file (a plain run times the headline only)")
+    ap.add_argument("--all-workloads", action="store_true", help="implies --full: every secondary workload, 200-batch loader bench, NumPy process-pool baseline (minutes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-also", action="store_true", help="--full without the settled-clock launches and the secondary workloads")
     ap.add_argument("--kernels-only", action="store_true", help="secondary workloads: kernel timings only (no loader bench, no ConvLSTM roofline, no host-input leg)")
-    ap.add_argument("--full", action="store_true", help="every secondary workload, 200-batch loader bench, NumPy process-pool baseline (minutes)")
-    ap.add_argument("--extra-out", default=None, help="sidecar file for everything that is not the contract line (default: bench_extra.json next to bench.py)")
+    ap.add_argument("--extra-out", default=None, help="sidecar file of --full for everything that is not the contract line (default: bench_extra.json next to bench.py)")
     ap.add_argument("--cpu-budget", type=float, default=10.0, help="seconds of the single-core NumPy-port baseline")
     ap.add_argument("--cpu-pool-budget", type=float, default=6.0, help="seconds of the all-cores NumPy-port baseline (timed part)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for dry runs)")
@@ -840,6 +901,7 @@ def main():
     ap.add_argument("--hip-graph", choices=["auto", "on", "off"], default="auto",
                     help="replay the step from a captured hipGraph (auto: multi-launch pipeline workloads only)")
     args = ap.parse_args()
+    args.full = args.full or args.all_workloads
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU under
@@ -882,9 +944,11 @@ def main():
     elapsed = sharding.max_over_ranks(dist, my_elapsed, dev)
     per_rank_ms = sharding.gather_floats(dist, my_elapsed / args.steps * 1e3, dev)        # every rank's own ms per step
     kern_avg_ms = sum(kern_ms) / len(kern_ms)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(W.outputs(), args.dump_outputs)
 
-    # Everything below is outside the timed region.  Order: secondary kernel workloads first (the headline's launches have just
-    # warmed the clocks), then the parity guard and the CPU baselines (the GPU idles under those).
+    # Everything below is outside the timed region, and measures or checks only under --full.  Order: secondary kernel workloads first
+    # (the headline's launches have just warmed the clocks), then the parity guard and the CPU baselines (the GPU idles under those).
     extra = {"seconds": {}}
     t_sec = time.perf_counter()
 
@@ -897,18 +961,18 @@ def main():
     # the same step again, OUTSIDE the timed region, once the clocks have settled (the chip ramps for ~30 ms after idle: the K timed launches
     # of a short run sit in that ramp): 100 more launches, their median -- context for `frac`, never `value`
     settled_ms = None
-    if rank == 0 and world == 1 and not args.no_also:
+    if args.full and rank == 0 and world == 1 and not args.no_also:
         tail = sorted(time_launches(step, 100, torch))
         settled_ms = tail[len(tail) // 2]
-    secondary = rank == 0 and world == 1 and args.workload == DEFAULT_WORKLOAD and not args.no_also and not args.batch
+    secondary = args.full and rank == 0 and world == 1 and args.workload == DEFAULT_WORKLOAD and not args.no_also and not args.batch
     if secondary:
-        extra["also_measured"] = measure_secondary(torch, dev, args.full, lap, args.kernels_only)
+        extra["also_measured"] = measure_secondary(torch, dev, args.all_workloads, lap, args.kernels_only)
         if not args.kernels_only:
             extra["host_input"] = measure_host_input(torch, dev, W, wl, kern_avg_ms)
             lap("host_input")
 
     parity = cpu = cpu_all = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             from oracle import clib
             clib.build()
@@ -957,7 +1021,8 @@ def main():
             e2 = (extra["also_measured"]["train_loader_b12_201x128x128"].get("ring_loader_feeding_e2vid") or {}).get("samples_per_s")
             if e2:
                 line["train_loader_samples_per_s"]["ring_loader_feeding_e2vid"] = round(e2, 1)
-        line["extra"] = write_sidecar(dict(line, **extra), args.extra_out)
+        if args.full:
+            line["extra"] = write_sidecar(dict(line, **extra), args.extra_out)
         sys.stderr.flush()
         print(line_text(line), flush=True)
     if dist is not None:

@@ -50,9 +50,9 @@ def test_linearity_of_binning_modes():
 
 
 def test_bench_contract_json():
-    """bench.py prints ONE JSON line with the contract's keys (small batch so it runs in seconds)."""
+    """bench.py --full prints ONE JSON line with the contract's keys (small batch so it runs in seconds)."""
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8",
-                          "--cpu-budget", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--full", "--cpu-budget", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -72,13 +72,13 @@ def test_bench_contract_json():
 
 
 def test_bench_default_command_prints_a_small_last_line_and_a_sidecar(tmp_path):
-    """The DRIVER's command, unabridged (`python bench.py --gpus 1 --steps 20 --warmup 5`: full batch, every default secondary
+    """The driver's command with --full (`python bench.py --gpus 1 --steps 20 --warmup 5 --full`: full batch, every default secondary
     workload, the loader bench, the CPU baseline).  Round 4's line had grown to 21.9 KB and the driver could not parse it: the contract
     line is the LAST non-empty stdout line, alone, at most 4 KB, and everything else sits in the sidecar file it names."""
     import time
     side = tmp_path / "bench_extra.json"
     t0 = time.perf_counter()
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--extra-out", str(side)],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--extra-out", str(side)],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     wall = time.perf_counter() - t0
     assert res.returncode == 0, res.stderr[-3000:]
@@ -115,6 +115,33 @@ def test_bench_default_command_prints_a_small_last_line_and_a_sidecar(tmp_path):
     assert wall < 240, f"the default run took {wall:.0f} s"
 
 
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """The plain command (no --full) sets up, warms up, times its K steps and prints the line: no parity guard, no CPU baseline, no
+    settled-clock launches, no sidecar.  --dump-outputs writes what the last timed step computed: a seeded sample of the 256 clips'
+    grids under 64 MB, equal bit for bit to the same launch made here on the same synthetic clips."""
+    import bench
+    from v2v_amd import esim
+    dump, side = tmp_path / "dump", tmp_path / "bench_extra.json"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(dump),
+                          "--extra-out", str(side)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-3000:]
+    out_lines = [l for l in res.stdout.splitlines() if l.strip()]
+    assert len(out_lines) == 1, [l[:200] for l in out_lines]
+    d = json.loads(out_lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["config"]["clips_per_gpu"] == 256 and d["unit"] == "voxel grids/s" and d["dtype"] == "f64"
+    assert abs(d["value"] - 256 * 7 / (d["ms_per_step"] * 7e-3)) / d["value"] < 1e-6 and d["higher_is_better"] is True
+    assert d["parity_check"] is None and d["cpu_baseline"] is None and d["extra"] is None and "cpu_baseline_all_cores" not in d
+    assert "kernel_ms_settled_p50" not in d["roofline"] and not side.exists()
+    assert sorted(os.listdir(dump)) == ["voxels.npy"] and os.path.getsize(dump / "voxels.npy") <= 64e6
+    got = np.load(dump / "voxels.npy")
+    assert got.dtype == np.float32 and got.shape == (48, 5, 256, 256)
+    idx = np.sort(np.random.default_rng(0).choice(256, 48, replace=False))
+    wl = bench.WORKLOADS[bench.DEFAULT_WORKLOAD]
+    frames = esim.synth_clips(256, wl["n"], wl["h"], wl["w"], dtype=torch.float32, seed=20240001, clip_id0=0, device="cuda")
+    want = esim.esim_voxel_batch(frames, wl["params"], bin_mode="bilinear", num_bins=5, rng_mode="philox", seed=20240001, clip_id0=0)
+    assert np.array_equal(got, want[torch.as_tensor(idx, device="cuda")].cpu().numpy())
+
+
 def test_bench_two_ranks_under_torch_distributed_run():
     """The N > 1 path exactly as the driver launches it -- `python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2`
     -- on this 1-GPU box: both ranks share cuda:0 (--share-gpu) and rendezvous over gloo (RCCL refuses two ranks on one
@@ -127,7 +154,7 @@ def test_bench_two_ranks_under_torch_distributed_run():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--batch", "16",
-           "--share-gpu", "--backend", "gloo"]
+           "--full", "--share-gpu", "--backend", "gloo"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert res.returncode == 0, (res.stdout[-1500:], res.stderr[-3000:])
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -157,7 +184,7 @@ def test_bench_host_fed_stream_workloads_on_two_ranks(workload, clips, grids_per
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--workload", workload,
-           "--share-gpu", "--backend", "gloo"]
+           "--full", "--share-gpu", "--backend", "gloo"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert res.returncode == 0, (res.stdout[-1500:], res.stderr[-3000:])
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -300,7 +327,7 @@ def test_bench_pipeline_workloads_run_with_two_ranks(workload, batch):
     N > 1 path: two ranks on this box's one GPU (gloo), each with its own clips (global clip ids by rank), one JSON line."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", str(batch),
-                          "--workload", workload, "--share-gpu", "--backend", "gloo", "--hip-graph", "off"],
+                          "--workload", workload, "--full", "--share-gpu", "--backend", "gloo", "--hip-graph", "off"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert res.returncode == 0, (res.stdout[-1500:], res.stderr[-3000:])
     d = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -314,7 +341,7 @@ def test_bench_gpus_n_without_a_launcher_starts_the_ranks_itself():
     share the box's one GPU over gloo; n_gpus, the world size the process group reports and one time per rank are in the line."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8",
-                          "--share-gpu", "--backend", "gloo"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--full", "--share-gpu", "--backend", "gloo"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert res.returncode == 0, (res.stdout[-1500:], res.stderr[-3000:])
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]

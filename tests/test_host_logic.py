@@ -111,6 +111,31 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
     assert res.returncode != 0 and "WORLD_SIZE=1" in (res.stderr + res.stdout)
 
 
+def test_bench_dump_outputs_keeps_the_same_seeded_clips_under_the_limit(tmp_path):
+    """bench.py --dump-outputs (runs without a GPU on host tensors): float64 and integer outputs as float64, the rest as float32, lists of
+    time steps stacked on axis 1; above the limit every array keeps the same seeded clips of its leading axis, in order, and the files
+    together stay under it; the same call twice writes the same arrays."""
+    import bench
+    vox = torch.randn((40, 3, 8, 8), generator=torch.Generator().manual_seed(1))
+    preds = [vox[:, 0].to(torch.bfloat16), vox[:, 1].to(torch.bfloat16)]
+    outs = {"voxels": vox, "scales": torch.arange(80, dtype=torch.int32).reshape(40, 2), "preds": preds, "mass": vox.double().sum()}
+    limit = 10 * 1024
+    for sub in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / sub), limit=limit)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["mass.npy", "preds.npy", "scales.npy", "voxels.npy"]
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in names}
+    assert all(np.array_equal(a[f[:-4]], np.load(tmp_path / "b" / f)) for f in names)
+    assert [a[f[:-4]].dtype for f in names] == [np.float64, np.float32, np.float64, np.float32]
+    assert sum(v.nbytes for v in a.values()) <= limit and a["mass"] == vox.double().sum().item()
+    rows = (a["scales"][:, 0] / 2).astype(np.int64)
+    assert 0 < len(rows) < 40 and np.all(np.diff(rows) > 0) and np.array_equal(a["scales"][:, 1], 2 * rows + 1)
+    assert np.array_equal(a["voxels"], vox.numpy()[rows])
+    assert np.array_equal(a["preds"], torch.stack(preds, 1).float().numpy()[rows])
+    bench.dump_outputs({"voxels": vox}, str(tmp_path / "c"))                      # under the default limit: the whole output
+    assert np.array_equal(np.load(tmp_path / "c" / "voxels.npy"), vox.numpy())
+
+
 def test_pause_chain_draws_equal_the_scalar_loop(tmp_path):
     """_draw_geometry draws the pause chain's uniforms in ONE np.random.rand(n) call.  The reference's loop
     (data/v2v_datasets.py:292-300) calls np.random.rand() once per step (the other test of the if / elif short-circuits before its

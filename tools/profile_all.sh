@@ -12,7 +12,7 @@ for WL in $WLS; do
   OUT=$REPO/gpurun_out/prof_$TAG/$WL
   mkdir -p $OUT
   cd /tmp
-  ARGS="$REPO/bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-also --workload $WL"
+  ARGS="$REPO/bench.py --steps 12 --warmup 3 --full --no-cpu-baseline --no-also --workload $WL"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $ARGS > $OUT/bench_under_stats.json 2> $OUT/stats.err
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o fetch -- python3 $ARGS > $OUT/bench_under_pmc_fetch.json 2> $OUT/pmc_fetch.err
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o write -- python3 $ARGS > $OUT/bench_under_pmc_write.json 2> $OUT/pmc_write.err

@@ -12,9 +12,9 @@ TRACE=$(find /tmp/pdrv -name "*kernel_trace.csv" | head -1)
 python3 - $OUT $TRACE <<'PY'
 import csv, json, sys
 out = sys.argv[1]
-# The headline instance is launched 5 (warm-up) + 20 (timed region) + 100 (settled tail, outside the timed region) times by the driver's
-# command: kernel_stats.csv averages all 125.  What must agree with the line's HIP-event average is the TIMED REGION: dispatches 6..25 of
-# that kernel in the kernel trace, in start order.
+# The headline instance is launched 5 (warm-up) + 20 (timed region) times by the driver's command (100 more, the settled tail, only
+# under --full): kernel_stats.csv averages all of them.  What must agree with the line's HIP-event average is the TIMED REGION:
+# dispatches 6..25 of that kernel in the kernel trace, in start order.
 try:
     rows = [r for r in csv.DictReader(open(sys.argv[2])) if "esim_voxel_kernel<1, 4, 1, 1, true, false, false, true, false>" in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))

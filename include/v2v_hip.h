@@ -362,6 +362,42 @@ int v2v_conv1x1_nhwc_hip(const void *x, const void *skip, const float *weight, c
  * model/submodules.py:267-271 RecurrentConvLayer = ConvLayer(relu) -> ConvLSTM).  C % 64 == 0 and (H*W) % 64 == 0. */
 int v2v_nchw_to_nhwc_bf16_hip(const void *src, int src_dtype, int64_t B, int64_t C, int64_t H, int64_t W, int relu, void *dst, void *stream);
 
+/* ---- Backward passes of the recurrent UNet (training: v2v_amd.unet.E2VIDRecurrent(trainable=True)) ---------------------------------
+ * All NHWC; activation gradients bf16, cell-state gradients and parameter gradients fp32; bf16 MFMA operands with fp32 accumulation.
+ * Caller-owned memory (a *_workspace_bytes query where a scratch slab is needed), no allocation, no synchronisation.  No float atomics:
+ * every result is bitwise reproducible from run to run.
+ *
+ * ConvLSTM step backward (gate order i, r, o, g as in model/submodules.py:ConvLSTM): the 3x3 gate GEMM recomputed from the SAVED x,
+ * h_prev (may be NULL: zero state), c_prev (may be NULL) with the forward's packed weights and bias; dh fp32 [B,H,W,C], dc fp32 (NULL:
+ * zero) -> dgates bf16 [B,H,W,4C] (gradient of the pre-activation gates) and dc_prev fp32 [B,H,W,C].  Same shape limits as the step. */
+int v2v_convlstm_step_bwd_hip(const void *x, const void *h_prev, const float *c_prev, const void *packed, const float *bias, const float *dh,
+                              const float *dc, int64_t B, int64_t H, int64_t W, int64_t C, void *dgates, float *dc_prev, void *stream);
+/* ReLU backward from the saved post-ReLU output: out = y > 0 ? dy : 0 on [M, C] bf16 (y NULL: a copy); C % 8 == 0. */
+int v2v_relu_bwd_nhwc_hip(const void *dy, const void *y, int64_t M, int64_t C, void *out, void *stream);
+/* Data gradient of a ks x ks convolution (pad ks/2) with weight fp32 [Cout,Cin,ks,ks]: dx [B,Hin,Win,Cin] = the stride-1 convolution of
+ * dy [B,Hin/stride,Win/stride,Cout] (stride 2: spread onto the input grid, zeros between) with the flipped, transposed weights, on the
+ * forward convolution kernel -- so Cout -> Cin must be a shape v2v_conv_nhwc_hip takes.  The weights are packed once per update
+ * (scratch: Cin*Cout*ks*ks floats); residual (may be NULL) [B,Hin,Win,Cin] bf16 is added before the one bf16 rounding. */
+int64_t v2v_conv_dgrad_packed_elems(int64_t Cin, int64_t Cout, int ks);
+int v2v_conv_dgrad_pack_weights_hip(const float *weight, int64_t Cin, int64_t Cout, int ks, float *scratch, void *packed, void *stream);
+int64_t v2v_conv_dgrad_workspace_bytes(int64_t B, int64_t Hin, int64_t Win, int64_t Cin, int64_t Cout, int stride);
+int v2v_conv_dgrad_nhwc_hip(const void *dy, const void *packed, const void *residual, int64_t B, int64_t Hin, int64_t Win, int64_t Cin, int64_t Cout,
+                            int ks, int stride, void *workspace, void *dx, void *stream);
+/* Weight and bias gradient of a ks x ks convolution (ks 1, 3 or 5, pad ks/2, stride 1 or 2): dy [B,Ho,Wo,Cout] bf16 (Cout % 32 == 0),
+ * input x1 [B,Hin,Win,C1] | x2 [B,Hin,Win,C2] bf16 (x2 may be NULL: zeros; the ConvLSTM's cat(x, h_prev) without the copy) ->
+ * dw fp32 [Cout, Cin_out, ks, ks] (the first Cin_out <= C1 + C2 input channels: the head's 8-channel padded input), db fp32 [Cout]
+ * (may be NULL).  An MFMA GEMM with K = the output pixels, split into slabs and summed in a fixed order. */
+int64_t v2v_conv_wgrad_workspace_bytes(int64_t B, int64_t Ho, int64_t Wo, int64_t Cin, int64_t Cout, int ks);
+int v2v_conv_wgrad_nhwc_hip(const void *dy, const void *x1, int64_t C1, const void *x2, int64_t C2, int64_t Cin_out, int64_t B, int64_t Hin, int64_t Win,
+                            int64_t Cout, int ks, int stride, void *workspace, float *dw, float *db, void *stream);
+/* Adjoint of v2v_upsample2x_nhwc_hip: dout [B,2H,2W,C] bf16 -> dx [B,H,W,C] bf16 (fp32 sums; the gradient of x and of the skip). */
+int v2v_upsample2x_bwd_nhwc_hip(const void *dout, int64_t B, int64_t H, int64_t W, int64_t C, void *dx, void *stream);
+/* Backward of the prediction layer (v2v_conv1x1_nhwc_hip with Cout = 1): dy [M] fp32 -> dx [M,C] bf16 = dy * bf16(w) (the gradient of
+ * x and of the skip), dw [C] = sum dy * bf16(x + skip), db [1] = sum dy (fp32).  C a power of two in 8..128. */
+int64_t v2v_conv1x1_bwd_workspace_bytes(int64_t M, int64_t C);
+int v2v_conv1x1_bwd_nhwc_hip(const float *dy, const void *x, const void *skip, const float *weight, int64_t M, int64_t C, void *dx, float *dw, float *db,
+                             void *workspace, void *stream);
+
 /* normalize_batch_voxel's per-sample k-th values gathered BY THE SIMULATOR'S WRITER (model/train_utils.py:147-166):
  * v2v_esim_voxel_stats_hip = v2v_esim_voxel_padded_hip + `stats`, uint32 [B][V2V_VOXEL_STATS_WORDS] (zeroed here, then accumulated by
  * the launch): word 256 + v counts the voxels of clip b equal to the integer v in -255..255 except v = 0 (left 0: the reader derives

@@ -27,7 +27,10 @@ EXPORTS = ("v2v_version", "v2v_last_error", "v2v_device_count", "v2v_lut_get", "
            "v2v_convlstm_packed_bytes", "v2v_convlstm_pack_weights_hip", "v2v_convlstm_step_hip", "v2v_nchw_to_nhwc_bf16_hip",
            "v2v_conv3x3_pack_weights_hip", "v2v_conv3x3_nhwc_hip", "v2v_conv_pack_weights_hip", "v2v_conv_nhwc_hip", "v2v_upsample2x_nhwc_hip", "v2v_conv1x1_nhwc_hip", "v2v_conv_packed_elems", "v2v_conv_head_packed_elems", "v2v_conv_head_pack_weights_hip",
            "v2v_to_nhwc8_bf16_hip", "v2v_conv_head_nhwc_hip", "v2v_clip_frames_f32_hip",
-           "v2v_esim_voxel_stats_hip", "v2v_voxel_scales_hip", "v2v_voxel_apply_scales_hip", "v2v_voxel_scales_select_hip", "v2v_to_nhwc8_bf16_scaled_hip", "v2v_esim_voxel_ex_hip", "v2v_clip_frames_f32_ex_hip", "v2v_clip_frames_f32_bounded_hip")
+           "v2v_esim_voxel_stats_hip", "v2v_voxel_scales_hip", "v2v_voxel_apply_scales_hip", "v2v_voxel_scales_select_hip", "v2v_to_nhwc8_bf16_scaled_hip", "v2v_esim_voxel_ex_hip", "v2v_clip_frames_f32_ex_hip", "v2v_clip_frames_f32_bounded_hip",
+           "v2v_convlstm_step_bwd_hip", "v2v_relu_bwd_nhwc_hip", "v2v_conv_dgrad_packed_elems", "v2v_conv_dgrad_pack_weights_hip",
+           "v2v_conv_dgrad_workspace_bytes", "v2v_conv_dgrad_nhwc_hip", "v2v_conv_wgrad_workspace_bytes", "v2v_conv_wgrad_nhwc_hip",
+           "v2v_upsample2x_bwd_nhwc_hip", "v2v_conv1x1_bwd_workspace_bytes", "v2v_conv1x1_bwd_nhwc_hip")
 EV_MAKE_VOXEL_DISCRETE, EV_MAKE_VOXEL_INTERP, EV_BILINEAR = 0, 1, 2
 NORM_NONE, NORM_RADIX, NORM_COUNT = 0, 1, 2
 VOXEL_STATS_WORDS = 516
@@ -189,6 +192,22 @@ def lib():
     L.v2v_v2e_voxel_hip.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                     C.POINTER(V2EParams), C.c_int, C.c_uint64, C.c_uint64, C.POINTER(V2EReplay), C.c_int,
                                     C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    # backward passes (v2v_amd/train.py)
+    P, I64 = C.c_void_p, C.c_int64
+    for name, res, args in (
+            ("v2v_convlstm_step_bwd_hip", C.c_int, [P] * 7 + [I64] * 4 + [P, P, P]),
+            ("v2v_relu_bwd_nhwc_hip", C.c_int, [P, P, I64, I64, P, P]),
+            ("v2v_conv_dgrad_packed_elems", I64, [I64, I64, C.c_int]),
+            ("v2v_conv_dgrad_pack_weights_hip", C.c_int, [P, I64, I64, C.c_int, P, P, P]),
+            ("v2v_conv_dgrad_workspace_bytes", I64, [I64] * 5 + [C.c_int]),
+            ("v2v_conv_dgrad_nhwc_hip", C.c_int, [P, P, P] + [I64] * 5 + [C.c_int, C.c_int, P, P, P]),
+            ("v2v_conv_wgrad_workspace_bytes", I64, [I64] * 5 + [C.c_int]),
+            ("v2v_conv_wgrad_nhwc_hip", C.c_int, [P, P, I64, P, I64, I64, I64, I64, I64, I64, C.c_int, C.c_int, P, P, P, P]),
+            ("v2v_upsample2x_bwd_nhwc_hip", C.c_int, [P] + [I64] * 4 + [P, P]),
+            ("v2v_conv1x1_bwd_workspace_bytes", I64, [I64, I64]),
+            ("v2v_conv1x1_bwd_nhwc_hip", C.c_int, [P, P, P, P, I64, I64, P, P, P, P, P])):
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = res, args
     if L.v2v_version() != ABI_VERSION:
         raise ImportError(f"libv2v_hip.so ABI {L.v2v_version()} != binding ABI {ABI_VERSION}: rebuild")
     _lib = L

@@ -15,8 +15,8 @@ v2v_upsample2x_nhwc_hip.
     nchw_to_nhwc_bf16(x, relu=False)                      layout change in front of them (not needed for channels-last bf16 input)
 
 The 3x3 gate convolution runs as an implicit GEMM on the bf16 matrix cores with fp32 accumulation and the gate / cell / hidden
-update fused on the accumulators (v2v_amd/csrc/v2v_convlstm.hpp).  Inference only (no autograd through the kernel: a call
-that would need a gradient raises).  No fallback: shapes the kernel does not take (hidden_size % 64, H*W % 4, kernel_size
+update fused on the accumulators (v2v_amd/csrc/v2v_convlstm.hpp).  Inference only by default (a call that would need a gradient
+raises); trainable=True on a layer records its backward kernels under grad (v2v_amd/train.py).  No fallback: shapes the kernel does not take (hidden_size % 64, H*W % 4, kernel_size
 != 3, input_size != hidden_size) raise ValueError.
 """
 from __future__ import annotations
@@ -59,6 +59,18 @@ def _to_nhwc_bf16(x: torch.Tensor, relu: bool = False) -> torch.Tensor:
     if relu:
         x = torch.relu(x)
     return x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
+
+
+def _is_nhwc_bf16(v) -> bool:
+    return v.dtype == torch.bfloat16 and v.dim() == 4 and v.is_contiguous(memory_format=torch.channels_last) and not v.is_contiguous()
+
+
+def _nhwc_in(x: torch.Tensor) -> torch.Tensor:
+    """The trainable layers' input as a contiguous bfloat16 [B,H,W,C] tensor through differentiable views / copies: a channels-last bfloat16
+    tensor as the view of its memory, anything else rounded to bfloat16 (the same values the layout kernel of the inference path writes)."""
+    if _is_nhwc_bf16(x):
+        return x.permute(0, 2, 3, 1)
+    return x.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()
 
 
 def pack_gate_weights(weight: torch.Tensor) -> torch.Tensor:
@@ -113,7 +125,7 @@ class ConvLSTM(nn.Module):
     kept beside it and reused when the (hidden, cell) pair comes back untouched (UNetRecurrent.forward, model/unet.py:293-296);
     any other prev_state (cloned, loaded, edited) is converted from its float32 values, which gives the same bits."""
 
-    def __init__(self, input_size, hidden_size, kernel_size):
+    def __init__(self, input_size, hidden_size, kernel_size, trainable: bool = False):
         super().__init__()
         if kernel_size != 3 or input_size != hidden_size:
             raise ValueError("the fused ConvLSTM covers the configuration the reference instantiates "
@@ -122,6 +134,12 @@ class ConvLSTM(nn.Module):
         self.Gates = nn.Conv2d(input_size + hidden_size, 4 * hidden_size, kernel_size, padding=kernel_size // 2)
         self._packed, self._packed_key = None, None
         self._h_cache = None                                           # (hidden tensor, its version, bf16 NHWC twin)
+        self.trainable = trainable                                     # True: under grad, forward records v2v_amd.train.ConvLSTMFn
+        # trainable, under grad: the hidden state's consumers each get their OWN output of ConvLSTMFn (same values), so that their
+        # gradients meet in fp32 inside its backward instead of in a bf16 sum made by autograd: the layer downstream (`hidden`),
+        # the next step (the cached twin) and -- when a network asks for it (UNetRecurrent: the decoder's sum skip) -- skip_twin(hidden)
+        self.wants_skip_twin = False
+        self._skip_twin = None                                         # (hidden tensor, its twin for the skip connection)
 
     def _weights(self):
         w = self.Gates.weight
@@ -133,6 +151,8 @@ class ConvLSTM(nn.Module):
     def forward(self, input_, prev_state=None, input_relu: bool = False):
         """input_relu=True takes the PRE-activation output of the convolution in front (RecurrentConvLayer.conv,
         model/submodules.py:110-116) and applies its ReLU inside the layout-change kernel."""
+        if self.trainable and torch.is_grad_enabled():
+            return self._forward_train(input_, prev_state, input_relu)
         if torch.is_grad_enabled() and (input_.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise RuntimeError("v2v_amd.convlstm.ConvLSTM is inference-only (no autograd through the fused kernel): "
                                "call it under torch.no_grad() / in eval mode")
@@ -165,6 +185,37 @@ class ConvLSTM(nn.Module):
         hidden_out = h_state.permute(0, 3, 1, 2) if nhwc_io else h_nchw
         self._h_cache = (hidden_out, hidden_out._version, h_state)
         return hidden_out, c_state.permute(0, 3, 1, 2)
+
+    def _forward_train(self, input_, prev_state, input_relu):
+        """forward() with autograd (trainable=True, grad enabled): the same step kernel on the same operands, recorded as ConvLSTMFn."""
+        from .train import ConvLSTMFn
+        nhwc_io = _is_nhwc_bf16(input_)
+        x = _nhwc_in(input_)
+        h_prev = c_prev = None
+        if prev_state is not None:
+            hidden, cell = prev_state
+            cache = self._h_cache
+            if cache is not None and cache[0] is hidden and cache[1] == hidden._version:
+                h_prev = cache[2]
+            else:
+                h_prev = _nhwc_in(hidden)
+            c_prev = cell.permute(0, 2, 3, 1)
+            if c_prev.dtype != torch.float32 or not c_prev.is_contiguous():
+                c_prev = c_prev.float().contiguous()
+        n_twins = 2 if (nhwc_io and self.wants_skip_twin) else 1
+        outs = ConvLSTMFn.apply(x, h_prev, c_prev, self.Gates.weight, self.Gates.bias, self, None if nhwc_io else input_.dtype, bool(input_relu),
+                                n_twins)
+        h_state, c_state, twins = outs[0], outs[1], outs[2:2 + n_twins]
+        hidden_out = h_state.permute(0, 3, 1, 2) if nhwc_io else outs[2 + n_twins]
+        self._h_cache = (hidden_out, hidden_out._version, twins[0])    # the next step's h_prev: its own output
+        self._skip_twin = (hidden_out, twins[1].permute(0, 3, 1, 2)) if n_twins == 2 else None
+        return hidden_out, c_state.permute(0, 3, 1, 2)
+
+    def skip_twin(self, hidden):
+        """The tensor a skip connection should read for `hidden` (the last forward's output): its own twin output under training (see
+        wants_skip_twin), `hidden` itself otherwise.  Same values either way."""
+        tw = self._skip_twin
+        return tw[1] if tw is not None and tw[0] is hidden else hidden
 
 
 # ---- the residual blocks of the same encoder (model/submodules.py:143-177) on the same matrix-core kernel ---------------------
@@ -206,7 +257,7 @@ class ResidualBlock(nn.Module):
     accumulation; a channels-last bfloat16 input is consumed and produced in place, anything else goes through the
     layout-change kernel and comes back NCHW in the input's dtype."""
 
-    def __init__(self, in_channels, out_channels, stride=1, downsample=None, norm=None, BN_momentum=0.1):
+    def __init__(self, in_channels, out_channels, stride=1, downsample=None, norm=None, BN_momentum=0.1, trainable: bool = False):
         super().__init__()
         if stride != 1 or downsample is not None or norm is not None or in_channels != out_channels:
             raise ValueError("the fused ResidualBlock covers the configuration E2VID instantiates "
@@ -214,6 +265,7 @@ class ResidualBlock(nn.Module):
         self.conv1 = nn.Conv2d(in_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=True)
         self.conv2 = nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=True)
         self._packed = {}
+        self.trainable = trainable                                     # True: under grad, forward records v2v_amd.train.ResidualBlockFn
 
     def _weights(self, conv, name):
         w = conv.weight
@@ -223,6 +275,10 @@ class ResidualBlock(nn.Module):
         return self._packed[name][1]
 
     def forward(self, x):
+        if self.trainable and torch.is_grad_enabled():
+            from .train import ResidualBlockFn
+            out = ResidualBlockFn.apply(_nhwc_in(x), self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias, self).permute(0, 3, 1, 2)
+            return out if _is_nhwc_bf16(x) else out.contiguous().to(x.dtype)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise RuntimeError("v2v_amd.convlstm.ResidualBlock is inference-only (no autograd through the fused kernel)")
         nhwc_io = x.dtype == torch.bfloat16 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
@@ -361,7 +417,7 @@ class ConvLayer(nn.Module):
     encoder); <= 8 input channels with 32 outputs = the head; kernel_size 1 = the prediction layer; else ValueError (no fallback)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, activation="relu", norm=None, BN_momentum=0.1,
-                 upsample=False):
+                 upsample=False, trainable: bool = False):
         super().__init__()
         if norm is not None or activation not in ("relu", None) or kernel_size not in (1, 3, 5) or padding != kernel_size // 2 or stride not in (1, 2) \
                 or (kernel_size == 1 and (stride != 1 or activation is not None or upsample or out_channels > 3)):
@@ -374,6 +430,7 @@ class ConvLayer(nn.Module):
             raise ValueError("with <= 8 input channels the fused ConvLayer is the UNet's head: 32 output channels, stride 1")
         self.force_channels_last = False          # head only: hand out the kernel's NHWC buffer as a channels-last view whatever came in
         self._packed = (None, None)
+        self.trainable = trainable                # True: under grad, forward records a v2v_amd.train Function (ConvFn / UpConvFn / HeadFn / PredFn)
 
     def _weights(self):
         w = self.conv2d.weight
@@ -385,6 +442,8 @@ class ConvLayer(nn.Module):
     def forward(self, x, skip=None, scales=None):
         """skip (upsample=True only): the sum skip connection model/unet.py:304 adds in front of the decoder, folded into the
         upsampling kernel -- layer(x, skip) == layer(x + skip)."""
+        if self.trainable and torch.is_grad_enabled():
+            return self._forward_train(x, skip, scales)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise RuntimeError("v2v_amd.convlstm.ConvLayer is inference-only (no autograd through the fused kernel)")
         if scales is not None and not self.head:
@@ -429,4 +488,44 @@ class ConvLayer(nn.Module):
             xn = upsample2x_nhwc(xn, None if skip is None else skip.permute(0, 2, 3, 1))
         out = conv_nhwc(xn, self._weights(), self.conv2d.bias.detach().float(), self.conv2d.kernel_size[0], self.conv2d.stride[0],
                         relu=self.relu).permute(0, 3, 1, 2)
+        return out if nhwc_io else out.contiguous().to(x.dtype)
+
+    def _forward_train(self, x, skip, scales):
+        """forward() with autograd (trainable=True, grad enabled): the inference path's kernels on the same operands, recorded as one
+        v2v_amd.train Function per layer; the fusions are differentiated as fused (skip into the upsampling, pred(x + head))."""
+        from . import train
+        if scales is not None and not self.head:
+            raise ValueError("`scales` is applied by the head kernel only (in_channels <= 8, kernel 3 or 5)")
+        conv = self.conv2d
+        if conv.kernel_size[0] == 1:
+            if conv.out_channels != 1:
+                raise ValueError("the trainable prediction layer has one output channel (model/unet.py:263)")
+            nhwc = all(v is None or _is_nhwc_bf16(v) for v in (x, skip))
+            if not nhwc:
+                x, skip = (x if skip is None else x + skip), None
+            # float32 out (the bf16 kernel values widened exactly; with a float32 input the inference path's dtype too): the loss
+            # gradient then reaches the backward kernel unrounded -- UNetRecurrent.forward's .to(out_dtype) gives the inference bits
+            out = train.PredFn.apply(_nhwc_in(x), None if skip is None else skip.permute(0, 2, 3, 1), conv.weight, conv.bias,
+                                     torch.bfloat16 if nhwc else x.dtype).permute(0, 3, 1, 2)
+            return out if (nhwc or x.dtype == torch.float32) else out.contiguous().to(x.dtype)
+        if skip is not None and not self.upsample:
+            raise ValueError("skip is the decoder's (upsample=True) sum skip connection")
+        if self.head:
+            if x.requires_grad:
+                raise ValueError("the trainable head computes no gradient for its input (the voxel grid)")
+            low = x.dtype == torch.bfloat16 or (x.is_cuda and torch.is_autocast_enabled())
+            cl = self.force_channels_last or any(v.is_contiguous(memory_format=torch.channels_last) and not v.is_contiguous() for v in (x, conv.weight))
+            out = train.HeadFn.apply(to_nhwc8_bf16(x.detach().float(), scales), conv.weight, conv.bias, self).permute(0, 3, 1, 2)
+            out = out if cl else out.contiguous()
+            return out if low else out.to(x.dtype)
+        nhwc_io = _is_nhwc_bf16(x)
+        if skip is not None and not (nhwc_io and _is_nhwc_bf16(skip)):
+            x, skip = x + skip, None
+            nhwc_io = _is_nhwc_bf16(x)
+        xn = _nhwc_in(x)
+        if self.upsample:
+            out = train.UpConvFn.apply(xn, None if skip is None else skip.permute(0, 2, 3, 1), conv.weight, conv.bias, self)
+        else:
+            out = train.ConvFn.apply(xn, conv.weight, conv.bias, self)
+        out = out.permute(0, 3, 1, 2)
         return out if nhwc_io else out.contiguous().to(x.dtype)

@@ -105,9 +105,24 @@ struct ConvLstmArgs {
     int32_t n_cols, relu;
     int32_t ks, stride, Hin, Win;          // taps per side (3 or 5, pad ks/2), stride (1 or 2), input size (H, W = the OUTPUT size)
     int32_t pack_cols;                     // columns per PACKED weight tile when the instance's tile is narrower (0: the same)
+    // the step's backward (EPI = 2): dh [B,H,W,C] fp32, dc fp32 or null (zero) in; dgates bf16 [B,H,W,4C], dc_prev fp32 [B,H,W,C] out
+    const float *dh, *dc;
+    uint16_t *dgates;
+    float *dc_prev;
 };
 hipError_t launch_convlstm_step(const ConvLstmArgs &a, int tile_rows, hipStream_t s);   // tile_rows: 0 auto, 64, 128 or 256
 hipError_t launch_convlstm_pack(const float *w, uint16_t *wp, int C, hipStream_t s);
+hipError_t launch_convlstm_step_bwd(const ConvLstmArgs &a, hipStream_t s);
+// backward passes of the recurrent UNet (v2v_train_tu.hip)
+int64_t wgrad_slabs(int64_t M, int Cout, int64_t N);
+hipError_t launch_conv_wgrad(const uint16_t *dy, const uint16_t *x1, int C1, const uint16_t *x2, int C2, int Cin_out, float *dw, float *db, float *ws,
+                             int B, int Hin, int Win, int Ho, int Wo, int Cout, int ks, int stride, hipStream_t s);
+hipError_t launch_relu_mask_stuff(const uint16_t *dy, const uint16_t *y, uint16_t *out, int B, int Ho, int Wo, int C, int stride, hipStream_t s);
+hipError_t launch_dgrad_flip(const float *w, float *wt, int Cout, int Cin, int ks, hipStream_t s);
+hipError_t launch_upsample2x_bwd(const uint16_t *dout, uint16_t *dx, int B, int H, int W, int C, hipStream_t s);
+hipError_t launch_conv1x1_bwd(const float *dy, const uint16_t *x, const uint16_t *skip, const float *w, uint16_t *dx, float *dw, float *db, float *ws,
+                              int64_t M, int C, hipStream_t s);
+int64_t conv1x1_bwd_slabs(int64_t M);
 hipError_t launch_conv_nhwc(const ConvLstmArgs &a, int tile_rows, hipStream_t s);
 int conv_tile_cols(int Cout);             // columns per tile of the instance launch_conv_nhwc takes for Cout (0: unsupported)
 hipError_t launch_conv_head(const uint16_t *x8, const uint16_t *wp, const float *bias, uint16_t *out, int B, int H, int W, int ks, int relu, hipStream_t s);

@@ -1000,4 +1000,142 @@ int v2v_nchw_to_nhwc_bf16_hip(const void *src, int src_dtype, int64_t B, int64_t
     return e == hipSuccess ? V2V_OK : hip_fail(e, "nchw_to_nhwc_bf16_kernel launch");
 }
 
+
+// ---- backward passes (training; kernels in v2v_train_tu.hip and the EPI = 2 step) ------------------------------------------------
+int v2v_convlstm_step_bwd_hip(const void *x, const void *h_prev, const float *c_prev, const void *packed, const float *bias, const float *dh,
+                              const float *dc, int64_t B, int64_t H, int64_t W, int64_t C, void *dgates, float *dc_prev, void *stream)
+{
+    if (!x || !packed || !bias || !dh || !dgates || !dc_prev) return fail(V2V_ERR_NULL, "v2v_convlstm_step_bwd_hip: x/packed/bias/dh/dgates/dc_prev is NULL");
+    if (B < 1 || H < 1 || W < 1 || C < 64 || C % 64 != 0 || C > 4096 || (H * W) % 4 != 0 || B * H * W * 4 * C > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C %% 64 == 0, C <= 4096, (H*W) %% 4 == 0, tensors below 2^31 elements");
+    if (dgates == x || dgates == h_prev) return fail(V2V_ERR_PARAM, "dgates must not alias x or h_prev (neighbouring tiles read them)");
+    if (!aligned(x, 16) || !aligned(h_prev, 16) || !aligned(packed, 16) || !aligned(c_prev, 4) || !aligned(dh, 4) || !aligned(dc, 4)
+        || !aligned(dgates, 2) || !aligned(dc_prev, 4) || !aligned(bias, 4))
+        return fail(V2V_ERR_ALIGN, "x/h_prev/packed need 16-byte alignment, c_prev/dh/dc/dc_prev/bias 4-byte, dgates 2-byte");
+    v2v::ConvLstmArgs a{};
+    a.x = static_cast<const uint16_t *>(x); a.h_prev = static_cast<const uint16_t *>(h_prev); a.c_prev = c_prev;
+    a.wp = static_cast<const uint16_t *>(packed); a.bias = bias;
+    a.B = (int)B; a.H = (int)H; a.W = (int)W; a.C = (int)C;
+    a.dh = dh; a.dc = dc; a.dgates = static_cast<uint16_t *>(dgates); a.dc_prev = dc_prev;
+    const hipError_t e = v2v::launch_convlstm_step_bwd(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "convlstm_step_kernel (EPI = 2) launch");
+}
+
+int v2v_relu_bwd_nhwc_hip(const void *dy, const void *y, int64_t M, int64_t C, void *out, void *stream)
+{
+    if (!dy || !out) return fail(V2V_ERR_NULL, "v2v_relu_bwd_nhwc_hip: dy/out is NULL");
+    if (M < 1 || C < 8 || C % 8 != 0 || M * C > 0x7FFFFFFFLL) return fail(V2V_ERR_SHAPE, "need M >= 1, C %% 8 == 0, M*C below 2^31");
+    if (!aligned(dy, 16) || !aligned(y, 16) || !aligned(out, 16)) return fail(V2V_ERR_ALIGN, "dy/y/out need 16-byte alignment");
+    const hipError_t e = v2v::launch_relu_mask_stuff(static_cast<const uint16_t *>(dy), static_cast<const uint16_t *>(y), static_cast<uint16_t *>(out),
+                                                     1, 1, (int)M, (int)C, 1, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "relu_mask_stuff_kernel launch");
+}
+
+int64_t v2v_conv_dgrad_packed_elems(int64_t Cin, int64_t Cout, int ks) { return v2v_conv_packed_elems(Cout, Cin, ks); }
+
+int v2v_conv_dgrad_pack_weights_hip(const float *weight, int64_t Cin, int64_t Cout, int ks, float *scratch, void *packed, void *stream)
+{
+    if (!weight || !scratch || !packed) return fail(V2V_ERR_NULL, "v2v_conv_dgrad_pack_weights_hip: weight/scratch/packed is NULL");
+    if ((ks != 3 && ks != 5) || v2v_conv_dgrad_packed_elems(Cin, Cout, ks) < 0)
+        return fail(V2V_ERR_SHAPE, "the transposed convolution (Cout -> Cin, ks 3 or 5) is not a shape the convolution kernel takes");
+    if (!aligned(packed, 16) || !aligned(scratch, 4)) return fail(V2V_ERR_ALIGN, "packed needs 16-byte alignment");
+    hipError_t e = v2v::launch_dgrad_flip(weight, scratch, (int)Cout, (int)Cin, ks, static_cast<hipStream_t>(stream));
+    if (e == hipSuccess) e = v2v::launch_conv_pack(scratch, static_cast<uint16_t *>(packed), (int)Cout, (int)Cin, ks, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "dgrad weight packing launch");
+}
+
+int64_t v2v_conv_dgrad_workspace_bytes(int64_t B, int64_t Hin, int64_t Win, int64_t Cin, int64_t Cout, int stride)
+{
+    if (B < 1 || Hin < 1 || Win < 1 || Cin < 1 || Cout < 1 || (stride != 1 && stride != 2)) return -1;
+    return (Cin * 4 + 255) / 256 * 256 + (stride == 2 ? B * Hin * Win * Cout * 2 : 0);
+}
+
+int v2v_conv_dgrad_nhwc_hip(const void *dy, const void *packed, const void *residual, int64_t B, int64_t Hin, int64_t Win, int64_t Cin, int64_t Cout,
+                            int ks, int stride, void *workspace, void *dx, void *stream)
+{
+    if (!dy || !packed || !workspace || !dx) return fail(V2V_ERR_NULL, "v2v_conv_dgrad_nhwc_hip: dy/packed/workspace/dx is NULL");
+    if ((ks != 3 && ks != 5) || (stride != 1 && stride != 2)) return fail(V2V_ERR_PARAM, "ks must be 3 or 5, stride 1 or 2");
+    if (B < 1 || Hin < 1 || Win < 1 || v2v_conv_dgrad_packed_elems(Cin, Cout, ks) < 0 || Hin % stride != 0 || Win % stride != 0 || (Hin * Win) % 4 != 0
+        || B * Hin * Win * (Cin > Cout ? Cin : Cout) > 0x7FFFFFFFLL || Cout % 8 != 0)
+        return fail(V2V_ERR_SHAPE, "need the transposed convolution Cout -> Cin to be a shape the convolution kernel takes, Hin, Win multiples "
+                                   "of the stride, (Hin*Win) %% 4 == 0, tensors below 2^31 elements");
+    if (dx == dy) return fail(V2V_ERR_PARAM, "dx must not alias dy");
+    if (!aligned(dy, 16) || !aligned(packed, 16) || !aligned(workspace, 256) || !aligned(dx, 2) || !aligned(residual, 2))
+        return fail(V2V_ERR_ALIGN, "dy/packed need 16-byte, workspace 256-byte alignment");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    float *zero_bias = static_cast<float *>(workspace);
+    hipError_t e = hipMemsetAsync(zero_bias, 0, Cin * 4, s);
+    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(zero bias)");
+    const uint16_t *src = static_cast<const uint16_t *>(dy);
+    if (stride == 2) {
+        uint16_t *grid = reinterpret_cast<uint16_t *>(static_cast<unsigned char *>(workspace) + (Cin * 4 + 255) / 256 * 256);
+        e = v2v::launch_relu_mask_stuff(src, nullptr, grid, (int)B, (int)(Hin / 2), (int)(Win / 2), (int)Cout, 2, s);
+        if (e != hipSuccess) return hip_fail(e, "relu_mask_stuff_kernel launch");
+        src = grid;
+    }
+    v2v::ConvLstmArgs a{};
+    a.x = src; a.wp = static_cast<const uint16_t *>(packed); a.bias = zero_bias;
+    a.residual = static_cast<const uint16_t *>(residual); a.out_nhwc = static_cast<uint16_t *>(dx);
+    a.n_cols = (int)Cin; a.relu = 0; a.ks = ks; a.stride = 1; a.Hin = (int)Hin; a.Win = (int)Win;
+    a.B = (int)B; a.H = (int)Hin; a.W = (int)Win; a.C = (int)Cout;
+    e = v2v::launch_conv_nhwc(a, 0, s);
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "dgrad (convlstm_step_kernel, EPI = 1) launch");
+}
+
+int64_t v2v_conv_wgrad_workspace_bytes(int64_t B, int64_t Ho, int64_t Wo, int64_t Cin, int64_t Cout, int ks)
+{
+    if (B < 1 || Ho < 1 || Wo < 1 || Cin < 1 || Cout < 32 || Cout % 32 != 0 || (ks != 1 && ks != 3 && ks != 5)) return -1;
+    const int64_t N = (int64_t)ks * ks * Cin, Npad = (N + 127) / 128 * 128;
+    const int64_t S = v2v::wgrad_slabs(B * Ho * Wo, (int)Cout, N);
+    return S * Cout * (Npad + 1) * 4;
+}
+
+int v2v_conv_wgrad_nhwc_hip(const void *dy, const void *x1, int64_t C1, const void *x2, int64_t C2, int64_t Cin_out, int64_t B, int64_t Hin, int64_t Win,
+                            int64_t Cout, int ks, int stride, void *workspace, float *dw, float *db, void *stream)
+{
+    if (!dy || !x1 || !workspace || !dw) return fail(V2V_ERR_NULL, "v2v_conv_wgrad_nhwc_hip: dy/x1/workspace/dw is NULL");
+    if ((ks != 1 && ks != 3 && ks != 5) || (stride != 1 && stride != 2)) return fail(V2V_ERR_PARAM, "ks must be 1, 3 or 5, stride 1 or 2");
+    const int64_t Ho = (Hin - 1) / stride + 1, Wo = (Win - 1) / stride + 1;
+    if (B < 1 || Hin < 1 || Win < 1 || C1 < 1 || C2 < 0 || Cin_out < 1 || Cin_out > C1 + C2 || Cout < 32 || Cout % 32 != 0
+        || B * Hin * Win * (C1 > C2 ? C1 : C2) > 0x7FFFFFFFLL || B * Ho * Wo * Cout > 0x7FFFFFFFLL || (int64_t)ks * ks * (C1 + C2) > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C1 >= 1, 1 <= Cin_out <= C1 + C2, Cout a multiple of 32, tensors below 2^31 elements");
+    if (!aligned(dy, 2) || !aligned(x1, 2) || !aligned(x2, 2) || !aligned(workspace, 4) || !aligned(dw, 4) || !aligned(db, 4))
+        return fail(V2V_ERR_ALIGN, "buffers misaligned");
+    const hipError_t e = v2v::launch_conv_wgrad(static_cast<const uint16_t *>(dy), static_cast<const uint16_t *>(x1), (int)C1,
+                                                static_cast<const uint16_t *>(x2), (int)C2, (int)Cin_out, dw, db, static_cast<float *>(workspace),
+                                                (int)B, (int)Hin, (int)Win, (int)Ho, (int)Wo, (int)Cout, ks, stride, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv_wgrad_kernel launch");
+}
+
+int v2v_upsample2x_bwd_nhwc_hip(const void *dout, int64_t B, int64_t H, int64_t W, int64_t C, void *dx, void *stream)
+{
+    if (!dout || !dx) return fail(V2V_ERR_NULL, "v2v_upsample2x_bwd_nhwc_hip: dout/dx is NULL");
+    if (B < 1 || H < 1 || W < 1 || C < 8 || C % 8 != 0 || B * 4 * H * W * C > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C %% 8 == 0, tensors below 2^31 elements");
+    if (!aligned(dout, 16) || !aligned(dx, 16)) return fail(V2V_ERR_ALIGN, "dout/dx need 16-byte alignment");
+    const hipError_t e = v2v::launch_upsample2x_bwd(static_cast<const uint16_t *>(dout), static_cast<uint16_t *>(dx), (int)B, (int)H, (int)W, (int)C,
+                                                    static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "upsample2x_bwd_kernel launch");
+}
+
+int64_t v2v_conv1x1_bwd_workspace_bytes(int64_t M, int64_t C)
+{
+    if (M < 1 || C < 8 || C > 128 || (C & (C - 1)) != 0) return -1;
+    return v2v::conv1x1_bwd_slabs(M) * (C + 1) * 4;
+}
+
+int v2v_conv1x1_bwd_nhwc_hip(const float *dy, const void *x, const void *skip, const float *weight, int64_t M, int64_t C, void *dx, float *dw, float *db,
+                             void *workspace, void *stream)
+{
+    if (!dy || !x || !weight || !dx || !dw || !db || !workspace) return fail(V2V_ERR_NULL, "v2v_conv1x1_bwd_nhwc_hip: a required pointer is NULL");
+    if (M < 1 || C < 8 || C > 128 || (C & (C - 1)) != 0 || M * C > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need M >= 1 and C a power of two in 8..128 (one output channel)");
+    if (!aligned(dy, 4) || !aligned(x, 16) || !aligned(skip, 16) || !aligned(dx, 16) || !aligned(weight, 4) || !aligned(workspace, 4))
+        return fail(V2V_ERR_ALIGN, "x/skip/dx need 16-byte alignment, dy/weight/workspace 4-byte");
+    const hipError_t e = v2v::launch_conv1x1_bwd(dy, static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(skip),
+                                                 weight, static_cast<uint16_t *>(dx), dw, db, static_cast<float *>(workspace), M, (int)C,
+                                                 static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv1x1_bwd_kernel launch");
+}
+
 }  // extern "C"

@@ -101,7 +101,8 @@ __device__ __forceinline__ void cl_epilogue_conv(const ConvLstmArgs &a, cl_f32x1
     }
 }
 
-// EPI = 0: ConvLSTM step (two inputs x|h, 4C gate columns, gate/cell epilogue).  EPI = 1: plain 3x3 convolution of x with
+// EPI = 0: ConvLSTM step (two inputs x|h, 4C gate columns, gate/cell epilogue).  EPI = 2: the step's BACKWARD on the same main loop
+// (the gate GEMM recomputed from the saved x, h_prev; the cell backward on the accumulators, epilogue below).  EPI = 1: plain 3x3 convolution of x with
 // n_cols output channels (a multiple of 256), epilogue bias (+ residual) (+ ReLU) -> bf16 NHWC: the residual blocks of the same
 // encoder (model/submodules.py:143-177) on the same tiles and pipeline.
 // WN x NF: wave columns x 32-column B fragments per wave = the tile's columns (2 x 4 = 256 for the gates; 1 x {4,2,1} = 128 / 64 /
@@ -129,15 +130,15 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, KS == 2 || WM * WN == 16 ? 
     unsigned char *const cl_lds = cl_lds_all + kgrp * (STAGES * kClStage);
     const int wm = wave % WM, wn = wave / WM;
     const int C = a.C, HW = a.H * a.W;
-    const int ks = EPI == 0 ? 3 : a.ks, pad = ks >> 1, n_taps = ks * ks, stride = EPI == 0 ? 1 : a.stride;
-    const int Hin = EPI == 0 ? a.H : a.Hin, Win = EPI == 0 ? a.W : a.Win;
+    const int ks = EPI != 1 ? 3 : a.ks, pad = ks >> 1, n_taps = ks * ks, stride = EPI != 1 ? 1 : a.stride;
+    const int Hin = EPI != 1 ? a.H : a.Hin, Win = EPI != 1 ? a.W : a.Win;
     constexpr int kStepCh = WN * 32;                              // hidden channels per column tile of the step (64, or 32 with one wave column)
-    const int n_ct = EPI == 0 ? C / kStepCh : a.n_cols / kBN;     // column tiles
+    const int n_ct = EPI != 1 ? C / kStepCh : a.n_cols / kBN;     // column tiles
     const int ct = blockIdx.x % n_ct;
     const int64_t m0 = (int64_t)(blockIdx.x / n_ct) * kClBM;      // first pixel of the tile (flattened b,y,x)
     const int64_t M = (int64_t)a.B * HW;                          // pixels of the launch: the LAST tile may reach past them (any B*H*W with H*W % 4 == 0)
-    const int cc_x = TPC == 2 ? 1 : C / kClBK, cc_all = EPI == 0 ? 2 * cc_x : cc_x;
-    const int cc_eff = (EPI == 0 && a.h_prev) ? cc_all : cc_x;    // zero state: skip h's chunks
+    const int cc_x = TPC == 2 ? 1 : C / kClBK, cc_all = EPI != 1 ? 2 * cc_x : cc_x;
+    const int cc_eff = (EPI != 1 && a.h_prev) ? cc_all : cc_x;    // zero state: skip h's chunks
     const int n_chunks = TPC == 2 ? (n_taps + 1) / 2 : n_taps * cc_eff;
 
     // ---- staging plan: wave w issues A pieces NA*w.. (8 rows each) and B pieces NB*w.. per chunk ----------------------
@@ -166,7 +167,7 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, KS == 2 || WM * WN == 16 ? 
         boff[j] = (uint32_t)(row * kClBK + (sslot ^ ((row >> 1) & 7)) * 8);
     }
     // a column tile narrower than the packed one (EPI = 1, 128-column instances on 256-column packing): sub-tile `ct % per`
-    const int pcols = EPI == 0 ? kClBN : a.pack_cols ? a.pack_cols : kBN, per = pcols / kBN;   // the step's weights are packed per 64 channels
+    const int pcols = EPI != 1 ? kClBN : a.pack_cols ? a.pack_cols : kBN, per = pcols / kBN;   // the step's weights are packed per 64 channels
     const uint16_t *wtile = a.wp + (int64_t)(ct / per) * (TPC == 2 ? n_chunks : n_taps * cc_all) * (pcols * kClBK) + (ct % per) * (kBN * kClBK);
 
     // LDS-DMA of chunk ck into buffer buf (part / nparts: a subset of the pieces, j % nparts == part).  The main loop issues
@@ -373,6 +374,42 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, KS == 2 || WM * WN == 16 ? 
                 } else {
                     *reinterpret_cast<float4 *>(static_cast<float *>(a.h_nchw) + o) = make_float4(hv[0], hv[1], hv[2], hv[3]);
                 }
+            }
+        }
+    }
+    }
+    if constexpr (EPI == 2) {
+    // ---- backward epilogue: the forward's gate / cell values recomputed on the accumulators (same expressions), then
+    //   tc = tanh(c);  dc_tot = dc + dh * o * (1 - tc^2);  d_o = dh * tc;  d_i = dc_tot * g;  d_g = dc_tot * i;  d_r = dc_tot * c_prev
+    //   dgates = (d_i i(1-i), d_r r(1-r), d_o o(1-o), d_g (1-g^2)) -> bf16 NHWC [B,H,W,4C] (gate-major channels, i r o g);
+    //   dc_prev = dc_tot * r (fp32).  dh / dc fp32 NHWC (dc may be null: zero).  The gate tensor itself never leaves the registers.
+    const int ch = ct * kStepCh + wn * 32 + fr;
+    const float b_i = a.bias[ch], b_r = a.bias[C + ch], b_o = a.bias[2 * C + ch], b_g = a.bias[3 * C + ch];
+#pragma unroll
+    for (int i = 0; i < MF; ++i) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t mq = m0 + wm * 32 * MF + i * 32 + q * 8 + fh * 4;
+            if (mq >= M) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int r = q * 4 + e;
+                const int64_t idx = (mq + e) * C + ch;
+                const float gi = cl_sigmoid(acc[i][0][r] + b_i), gr = cl_sigmoid(acc[i][1][r] + b_r);
+                const float go = cl_sigmoid(acc[i][2][r] + b_o), gg = cl_tanh(acc[i][3][r] + b_g);
+                const float cp = a.c_prev ? a.c_prev[idx] : 0.0f;
+                const float cn = gr * cp + gi * gg;
+                const float tc = cl_tanh(cn);
+                const float dh = a.dh[idx];
+                const float dct = (a.dc ? a.dc[idx] : 0.0f) + dh * go * (1.0f - tc * tc);
+                const float d_i = dct * gg * (gi * (1.0f - gi)), d_r = dct * cp * (gr * (1.0f - gr));
+                const float d_o = dh * tc * (go * (1.0f - go)), d_g = dct * gi * (1.0f - gg * gg);
+                const int64_t go_ = (mq + e) * (int64_t)(4 * C) + ch;
+                a.dgates[go_] = f32_to_bf16_rne(d_i);
+                a.dgates[go_ + C] = f32_to_bf16_rne(d_r);
+                a.dgates[go_ + 2 * C] = f32_to_bf16_rne(d_o);
+                a.dgates[go_ + 3 * C] = f32_to_bf16_rne(d_g);
+                a.dc_prev[idx] = dct * gr;
             }
         }
     }

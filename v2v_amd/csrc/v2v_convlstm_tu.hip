@@ -22,7 +22,7 @@ hipError_t launch_step_t(const ConvLstmArgs &a, hipStream_t s)
         if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_release);
     }
     // ceil: the last pixel tile may be partial (rows past B*H*W read the zero line and are not stored)
-    const int64_t tiles = (((int64_t)a.B * a.H * a.W + 32 * MF * WM - 1) / (32 * MF * WM)) * (EPI == 0 ? a.C / (WN * 32) : a.n_cols / (WN * NF * 32));
+    const int64_t tiles = (((int64_t)a.B * a.H * a.W + 32 * MF * WM - 1) / (32 * MF * WM)) * (EPI != 1 ? a.C / (WN * 32) : a.n_cols / (WN * NF * 32));
     hipLaunchKernelGGL((convlstm_step_kernel<MF, WM, STAGES, EPI, WN, NF, TPC, KS>), dim3((unsigned)tiles), dim3(64 * WM * WN * KS), lds, s, a);
     return hipGetLastError();
 }
@@ -52,6 +52,9 @@ hipError_t launch_convlstm_step(const ConvLstmArgs &a, int tile_rows, hipStream_
     if (tile_rows == 256) return launch_step_t<1, 8, 2>(a, s);
     return tile_rows == 128 ? launch_step_t<1, 4, 3>(a, s) : launch_step_t<1, 2, 2>(a, s);
 }
+
+// the step's backward (EPI = 2): 64-pixel tiles of 4 waves (two workgroups per CU), the forward's 64-pixel instance with the backward epilogue
+hipError_t launch_convlstm_step_bwd(const ConvLstmArgs &a, hipStream_t s) { return launch_step_t<1, 2, 2, 2>(a, s); }
 
 // plain convolution (EPI = 1): Cout % 256 == 0 takes the 256-column tiles of the gate kernel (three pixel-tile sizes), Cout =
 // 128 / 64 / 32 a 256-pixel tile of 4 waves with 4 / 2 / 1 column fragments per wave

@@ -1,0 +1,322 @@
+// v2v_train_tu.hip -- backward passes of the recurrent UNet's layers (training with trainable=True, v2v_amd/train.py).
+//
+// Kernels in this file:  conv_wgrad_kernel + wgrad_reduce_kernel (weight / bias gradient of every convolution: K = the pixels, split
+// into slabs, fixed-order sum) | relu_mask_stuff_kernel (ReLU backward from the saved post-ReLU output, optionally spread onto the
+// stride-2 input grid) | dgrad_flip_kernel (weights flipped and transposed: the data gradient of a convolution is a convolution that
+// runs on the forward kernels) | upsample2x_bwd_kernel (adjoint of the x2 bilinear upsampling) | conv1x1_bwd_kernel +
+// conv1x1_bwd_reduce_kernel (the prediction layer).  The ConvLSTM step's backward is an epilogue of convlstm_step_kernel (EPI = 2,
+// v2v_convlstm.hpp).  Numerics: bf16 MFMA operands, fp32 accumulation, fp32 parameter gradients; no float atomics anywhere, so every
+// gradient is bitwise reproducible from run to run.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "v2v_args.hpp"
+
+namespace v2v {
+
+namespace {
+typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 tr_bf16x8;
+typedef __attribute__((__vector_size__(16 * sizeof(float)))) float tr_f32x16;
+typedef __bf16 tr_hwbf16x2 __attribute__((ext_vector_type(2)));
+typedef float tr_f32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint16_t tr_bf16(float f)     // round to nearest even (v_cvt_pk_bf16_f32), NaN stays NaN
+{
+    return (uint16_t)__builtin_bit_cast(uint32_t, __builtin_convertvector(tr_f32x2{f, f}, tr_hwbf16x2));
+}
+__device__ __forceinline__ float tr_f32(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
+
+constexpr int kWgTileN = 128;                            // weight-gradient columns per workgroup (4 waves x 32)
+}  // namespace
+
+// ---- weight gradient: dW[co][tap, ci] = sum_p dy[p][co] * x[p + tap][ci] -------------------------------------------------------
+// One MFMA GEMM per convolution: M = Cout (32-row fragments), N = taps * Cin (n = tap * Cin + ci), K = the B*Ho*Wo output pixels.
+// K is split into `S` slabs (grid z); slab s writes its partial sums ws[s][co][n] (fp32) and its bias partial wsb[s][co]; the reduce
+// kernel adds the slabs in slab order.  The input is x1 (C1 channels) | x2 (C2 channels, may be null = zero): the ConvLSTM gates'
+// cat(x, h_prev) without the copy.  A lane's 8 k values are 8 consecutive pixels: 2-byte gathers from the NHWC tensors (32 lanes of a
+// fragment row read 64 consecutive bytes of one pixel).
+__global__ void __launch_bounds__(256) conv_wgrad_kernel(const uint16_t *dy, const uint16_t *x1, int C1, const uint16_t *x2, int C2, float *ws,
+                                                         float *wsb, int B, int Hin, int Win, int Ho, int Wo, int Cout, int ks, int stride,
+                                                         int N, int Npad, int k_slab)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 31, fh = lane >> 5;
+    const int Cin = C1 + C2, pad = ks >> 1;
+    const int co = blockIdx.y * 32 + fr;
+    const int n = blockIdx.x * kWgTileN + wave * 32 + fr;
+    const int tap = n / Cin, ci = n - tap * Cin;
+    const int ty = tap / ks - pad, tx = tap % ks - pad;
+    const bool live = n < N;
+    const uint16_t *src = ci < C1 ? x1 : x2;
+    const int csrc = ci < C1 ? C1 : C2, coff = ci < C1 ? ci : ci - C1;
+    const int M = B * Ho * Wo, HWo = Ho * Wo;
+    const int k0 = blockIdx.z * k_slab, k1 = min(M, k0 + k_slab);
+    const bool do_bias = blockIdx.x == 0 && wave == 0;
+    tr_f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    float bsum = 0.0f;
+    for (int k = k0; k < k1; k += 16) {
+        tr_bf16x8 af, bf;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int p = k + 8 * fh + j;
+            uint16_t av = 0, bv = 0;
+            if (p < k1) {
+                av = dy[(int64_t)p * Cout + co];
+                const int b = p / HWo, q = p - b * HWo, oy = q / Wo, ox = q - oy * Wo;
+                const int iy = oy * stride + ty, ix = ox * stride + tx;
+                if (live && src && (unsigned)iy < (unsigned)Hin && (unsigned)ix < (unsigned)Win)
+                    bv = src[(((int64_t)b * Hin + iy) * Win + ix) * csrc + coff];
+            }
+            if (do_bias) bsum += tr_f32(av);
+            af[j] = __builtin_bit_cast(__bf16, av);
+            bf[j] = __builtin_bit_cast(__bf16, bv);
+        }
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf, acc, 0, 0, 0);
+    }
+    // accumulator element r: row (co) (r & 3) + 8 (r >> 2) + 4 fh, column (n) fr
+    float *const wsl = ws + ((int64_t)blockIdx.z * Cout + blockIdx.y * 32) * Npad + n;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) wsl[(int64_t)((r & 3) + 8 * (r >> 2) + 4 * fh) * Npad] = acc[r];
+    if (do_bias) {
+        const float other = __shfl_xor(bsum, 32);
+        if (fh == 0) wsb[(int64_t)blockIdx.z * Cout + co] = bsum + other;
+    }
+}
+
+// dW in nn.Conv2d's layout [Cout, Cin_out, ks, ks] (Cin_out <= C1 + C2: the head's padded channels dropped) and db [Cout]: one
+// work-item per element, slabs added in slab order
+__global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float *ws, const float *wsb, float *dw, float *db, int S, int Cout, int Cin,
+                                                           int Cin_out, int taps, int Npad)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t nw = (int64_t)Cout * Cin_out * taps;
+    if (i < nw) {
+        const int tap = (int)(i % taps), ci = (int)((i / taps) % Cin_out), co = (int)(i / ((int64_t)taps * Cin_out));
+        const float *p = ws + (int64_t)co * Npad + tap * Cin + ci;
+        float s = 0.0f;
+        for (int k = 0; k < S; ++k) s += p[(int64_t)k * Cout * Npad];
+        dw[i] = s;
+    } else if (i < nw + Cout && db) {
+        const int co = (int)(i - nw);
+        float s = 0.0f;
+        for (int k = 0; k < S; ++k) s += wsb[(int64_t)k * Cout + co];
+        db[co] = s;
+    }
+}
+
+// slabs of the weight gradient: about 2048 workgroups in all, at least 256 pixels per slab
+int64_t wgrad_slabs(int64_t M, int Cout, int64_t N)
+{
+    const int64_t tiles = ((N + kWgTileN - 1) / kWgTileN) * (Cout / 32);
+    int64_t s = (2048 + tiles - 1) / tiles;
+    const int64_t smax = (M + 255) / 256;
+    if (s > smax) s = smax;
+    if (s < 1) s = 1;
+    const int64_t k_slab = ((M + s - 1) / s + 15) / 16 * 16;
+    return (M + k_slab - 1) / k_slab;
+}
+
+hipError_t launch_conv_wgrad(const uint16_t *dy, const uint16_t *x1, int C1, const uint16_t *x2, int C2, int Cin_out, float *dw, float *db, float *ws,
+                             int B, int Hin, int Win, int Ho, int Wo, int Cout, int ks, int stride, hipStream_t s)
+{
+    const int64_t M = (int64_t)B * Ho * Wo;
+    const int N = ks * ks * (C1 + C2), ntiles = (N + kWgTileN - 1) / kWgTileN, Npad = ntiles * kWgTileN;
+    const int64_t S = wgrad_slabs(M, Cout, N);
+    const int k_slab = (int)((M + S - 1) / S + 15) / 16 * 16;
+    float *wsb = ws + S * Cout * Npad;
+    hipLaunchKernelGGL(conv_wgrad_kernel, dim3((unsigned)ntiles, (unsigned)(Cout / 32), (unsigned)S), dim3(256), 0, s, dy, x1, C1, x2, C2, ws, wsb,
+                       B, Hin, Win, Ho, Wo, Cout, ks, stride, N, Npad, k_slab);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int64_t n = (int64_t)Cout * Cin_out * ks * ks + Cout;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws, wsb, dw, db, (int)S, Cout, C1 + C2, Cin_out,
+                       ks * ks, Npad);
+    return hipGetLastError();
+}
+
+// ---- ReLU backward (+ the stride-2 spread) ---------------------------------------------------------------------------------------
+// out = dy where y > 0 else 0 (y = the saved post-ReLU output; null: no mask).  stride 2: out is [B, 2 Ho, 2 Wo, C] with the masked
+// dy at the even positions and zeros between -- the data gradient of a stride-2 convolution is then the stride-1 convolution of
+// this grid with the flipped weights.  One work-item per pixel and 8 channels.
+__global__ void __launch_bounds__(256) relu_mask_stuff_kernel(const uint16_t *dy, const uint16_t *y, uint16_t *out, int B, int Ho, int Wo, int C, int stride)
+{
+    const int G = C / 8, Hs = Ho * stride, Ws = Wo * stride;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)B * Hs * Ws * G) return;
+    const int g = (int)(i % G);
+    const int64_t pix = i / G;
+    const int sx = (int)(pix % Ws), sy = (int)((pix / Ws) % Hs), b = (int)(pix / ((int64_t)Ws * Hs));
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (sx % stride == 0 && sy % stride == 0) {
+        const int64_t src = (((int64_t)b * Ho + sy / stride) * Wo + sx / stride) * C + g * 8;
+        v = *reinterpret_cast<const uint4 *>(dy + src);
+        if (y) {
+            const uint4 m = *reinterpret_cast<const uint4 *>(y + src);
+            uint32_t *vv = reinterpret_cast<uint32_t *>(&v);
+            const uint32_t *mm = reinterpret_cast<const uint32_t *>(&m);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t lo = tr_f32((uint16_t)(mm[j] & 0xFFFFu)) > 0.0f ? 0x0000FFFFu : 0u;
+                const uint32_t hi = tr_f32((uint16_t)(mm[j] >> 16)) > 0.0f ? 0xFFFF0000u : 0u;
+                vv[j] &= lo | hi;
+            }
+        }
+    }
+    *reinterpret_cast<uint4 *>(out + i * 8) = v;
+}
+
+hipError_t launch_relu_mask_stuff(const uint16_t *dy, const uint16_t *y, uint16_t *out, int B, int Ho, int Wo, int C, int stride, hipStream_t s)
+{
+    const int64_t n = (int64_t)B * Ho * stride * Wo * stride * (C / 8);
+    hipLaunchKernelGGL(relu_mask_stuff_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dy, y, out, B, Ho, Wo, C, stride);
+    return hipGetLastError();
+}
+
+// ---- data gradient: the weights of the transposed convolution ------------------------------------------------------------------
+// w [Cout, Cin, ks, ks] -> wt [Cin, Cout, ks, ks] with both taps reversed: dx = conv(dy, wt) (pad ks/2, stride 1), packed afterwards
+// by the forward's own packing kernel for Cin' = Cout, Cout' = Cin
+__global__ void __launch_bounds__(256) dgrad_flip_kernel(const float *w, float *wt, int Cout, int Cin, int ks)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int taps = ks * ks;
+    if (i >= (int64_t)Cout * Cin * taps) return;
+    const int tap = (int)(i % taps), co = (int)((i / taps) % Cout), ci = (int)(i / ((int64_t)taps * Cout));
+    wt[i] = w[((int64_t)co * Cin + ci) * taps + (taps - 1 - tap)];
+}
+
+hipError_t launch_dgrad_flip(const float *w, float *wt, int Cout, int Cin, int ks, hipStream_t s)
+{
+    const int64_t n = (int64_t)Cout * Cin * ks * ks;
+    hipLaunchKernelGGL(dgrad_flip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, wt, Cout, Cin, ks);
+    return hipGetLastError();
+}
+
+// ---- adjoint of the x2 bilinear upsampling (align_corners=False, clamped edges) -------------------------------------------------
+// Forward (upsample2x_nhwc_bf16_kernel): output row 2m reads rows (max(m-1, 0), m) with weights (0.25, 0.75), row 2m+1 reads
+// (m, min(m+1, H-1)) with (0.75, 0.25); columns alike.  Gather form: input row k receives from output rows 2k-1 .. 2k+2, each with
+// the sum of the weights under which it read k.  One work-item per input pixel and 8 channels, fp32 sums, one bf16 rounding.
+// The result is the gradient of x AND of the skip (the forward upsamples x + skip).
+__device__ __forceinline__ float up_w(int j, int k, int n)
+{
+    const int m = j >> 1;
+    const int lo = (j & 1) ? m : (m > 0 ? m - 1 : 0), hi = (j & 1) ? (m + 1 < n ? m + 1 : n - 1) : m;
+    const float wlo = (j & 1) ? 0.75f : 0.25f, whi = (j & 1) ? 0.25f : 0.75f;
+    return (lo == k ? wlo : 0.0f) + (hi == k ? whi : 0.0f);
+}
+
+__global__ void __launch_bounds__(256) upsample2x_bwd_kernel(const uint16_t *dout, uint16_t *dx, int B, int H, int W, int C)
+{
+    const int G = C / 8;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)B * H * W * G) return;
+    const int g = (int)(i % G);
+    const int64_t pix = i / G;
+    const int kx = (int)(pix % W), ky = (int)((pix / W) % H), b = (int)(pix / ((int64_t)W * H));
+    const int H2 = 2 * H, W2 = 2 * W;
+    float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (int jy = 2 * ky - 1; jy <= 2 * ky + 2; ++jy) {
+        if (jy < 0 || jy >= H2) continue;
+        const float wy = up_w(jy, ky, H);
+        float row[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        for (int jx = 2 * kx - 1; jx <= 2 * kx + 2; ++jx) {
+            if (jx < 0 || jx >= W2) continue;
+            const float wx = up_w(jx, kx, W);
+            const uint4 v = *reinterpret_cast<const uint4 *>(dout + (((int64_t)b * H2 + jy) * W2 + jx) * C + g * 8);
+            const uint32_t *vv = reinterpret_cast<const uint32_t *>(&v);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                row[2 * j] += wx * tr_f32((uint16_t)(vv[j] & 0xFFFFu));
+                row[2 * j + 1] += wx * tr_f32((uint16_t)(vv[j] >> 16));
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] += wy * row[j];
+    }
+    uint4 o;
+    uint32_t *oo = reinterpret_cast<uint32_t *>(&o);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) oo[j] = (uint32_t)tr_bf16(acc[2 * j]) | ((uint32_t)tr_bf16(acc[2 * j + 1]) << 16);
+    *reinterpret_cast<uint4 *>(dx + pix * C + g * 8) = o;
+}
+
+hipError_t launch_upsample2x_bwd(const uint16_t *dout, uint16_t *dx, int B, int H, int W, int C, hipStream_t s)
+{
+    const int64_t n = (int64_t)B * H * W * (C / 8);
+    hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dout, dx, B, H, W, C);
+    return hipGetLastError();
+}
+
+// ---- the prediction layer's backward (1x1, C -> 1, on bf16(x + skip)) ------------------------------------------------------------
+// dy fp32 (the loss gradient of the prediction, unrounded); dx[m][c] = bf16(dy[m] * bf16(w[c])) -- the gradient of x and of the skip; dW[c] = sum_m dy[m] * bf16(x + skip)[m][c], db = sum_m dy[m].
+// One workgroup per slab of kC1x1Slab pixels: C / 8 lanes per pixel (8 channels each), the workgroup's partial sums meet in LDS in
+// a fixed order and go to ws[slab][C + 1]; the reduce kernel adds the slabs in slab order.
+constexpr int kC1x1Slab = 2048;
+__global__ void __launch_bounds__(256) conv1x1_bwd_kernel(const float *dy, const uint16_t *x, const uint16_t *skip, const float *w, uint16_t *dx,
+                                                          float *ws, int64_t M, int C)
+{
+    __shared__ float red[256 * 9];
+    const int G = C / 8, rows = 256 / G;
+    const int g = threadIdx.x % G, pr = threadIdx.x / G;
+    float wb[8], acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, accb = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) wb[j] = tr_f32(tr_bf16(w[g * 8 + j]));
+    const int64_t p0 = (int64_t)blockIdx.x * kC1x1Slab, p1 = p0 + kC1x1Slab < M ? p0 + kC1x1Slab : M;
+    for (int64_t p = p0 + pr; p < p1; p += rows) {
+        const float d = dy[p];
+        const uint4 xv = *reinterpret_cast<const uint4 *>(x + p * C + g * 8);
+        uint4 sv = make_uint4(0u, 0u, 0u, 0u);
+        if (skip) sv = *reinterpret_cast<const uint4 *>(skip + p * C + g * 8);
+        const uint32_t *xx = reinterpret_cast<const uint32_t *>(&xv), *ss = reinterpret_cast<const uint32_t *>(&sv);
+        uint4 o;
+        uint32_t *oo = reinterpret_cast<uint32_t *>(&o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float xs0 = tr_f32((uint16_t)(xx[j] & 0xFFFFu)), xs1 = tr_f32((uint16_t)(xx[j] >> 16));
+            if (skip) {
+                xs0 = tr_f32(tr_bf16(xs0 + tr_f32((uint16_t)(ss[j] & 0xFFFFu))));
+                xs1 = tr_f32(tr_bf16(xs1 + tr_f32((uint16_t)(ss[j] >> 16))));
+            }
+            acc[2 * j] += d * xs0;
+            acc[2 * j + 1] += d * xs1;
+            oo[j] = (uint32_t)tr_bf16(d * wb[2 * j]) | ((uint32_t)tr_bf16(d * wb[2 * j + 1]) << 16);
+        }
+        *reinterpret_cast<uint4 *>(dx + p * C + g * 8) = o;
+        accb += d;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) red[threadIdx.x * 9 + j] = acc[j];
+    red[threadIdx.x * 9 + 8] = accb;
+    __syncthreads();
+    if ((int)threadIdx.x <= C) {                         // thread c < C: channel c; thread C: the bias (from the lanes of channel group 0)
+        const int c = threadIdx.x, cg = c < C ? c / 8 : 0, slot = c < C ? c % 8 : 8;
+        float s = 0.0f;
+        for (int r = 0; r < rows; ++r) s += red[(r * G + cg) * 9 + slot];
+        ws[(int64_t)blockIdx.x * (C + 1) + c] = s;
+    }
+}
+
+__global__ void __launch_bounds__(256) conv1x1_bwd_reduce_kernel(const float *ws, float *dw, float *db, int S, int C)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c > C) return;
+    float s = 0.0f;
+    for (int k = 0; k < S; ++k) s += ws[(int64_t)k * (C + 1) + c];
+    if (c < C) dw[c] = s;
+    else db[0] = s;
+}
+
+int64_t conv1x1_bwd_slabs(int64_t M) { return (M + kC1x1Slab - 1) / kC1x1Slab; }
+
+hipError_t launch_conv1x1_bwd(const float *dy, const uint16_t *x, const uint16_t *skip, const float *w, uint16_t *dx, float *dw, float *db, float *ws,
+                              int64_t M, int C, hipStream_t s)
+{
+    const int64_t S = conv1x1_bwd_slabs(M);
+    hipLaunchKernelGGL(conv1x1_bwd_kernel, dim3((unsigned)S), dim3(256), 0, s, dy, x, skip, w, dx, ws, M, C);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(conv1x1_bwd_reduce_kernel, dim3((unsigned)((C + 1 + 255) / 256)), dim3(256), 0, s, ws, dw, db, (int)S, C);
+    return hipGetLastError();
+}
+
+}  // namespace v2v

@@ -10,7 +10,8 @@ v2v_amd/convlstm.py under the REFERENCE'S OWN module tree, so that a reference c
 
 Configuration covered = what config/train_v2v_e2vid_10k.yaml:21-30 instantiates: skip_type 'sum', recurrent_block_type
 'convlstm', use_upsample_conv true, norm none, kernel_size 5, base_num_channels 32, channel_multiplier 2 (anything else raises:
-there is no stock-layer fallback inside this module).  Inference only (the kernels have no backward).
+there is no stock-layer fallback inside this module).  Inference by default; trainable=True adds the backward kernels of
+v2v_amd/train.py (back-propagation through time through the ConvLSTM states when grad is enabled).
 
 Inside forward() everything runs in bfloat16 NHWC (torch.channels_last views of the kernels' own buffers): the head takes
 the float voxel grid in any layout, every later layer consumes and produces NHWC in place, the cell states stay float32, and
@@ -28,22 +29,22 @@ from .convlstm import ConvLayer, ConvLSTM, ResidualBlock
 class UpsampleConvLayer(ConvLayer):
     """model/submodules.py:68-96: bilinear x2 upsampling + convolution + ReLU; forward(x, skip) == forward(skip_sum(x, skip))."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, activation="relu", norm=None):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, activation="relu", norm=None, trainable: bool = False):
         super().__init__(in_channels, out_channels, kernel_size, stride=stride, padding=padding, activation=activation, norm=norm,
-                         upsample=True)
+                         upsample=True, trainable=trainable)
 
 
 class RecurrentConvLayer(nn.Module):
     """model/submodules.py:99-119: ConvLayer followed by the ConvLSTM; same attribute names (`conv`, `recurrent_block`)."""
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=0, recurrent_block_type="convlstm",
-                 activation="relu", norm=None, BN_momentum=0.1):
+                 activation="relu", norm=None, BN_momentum=0.1, trainable: bool = False):
         super().__init__()
         if recurrent_block_type != "convlstm":
             raise ValueError("only recurrent_block_type 'convlstm' runs on the device kernels")
         self.recurrent_block_type = recurrent_block_type
-        self.conv = ConvLayer(in_channels, out_channels, kernel_size, stride, padding, activation, norm)
-        self.recurrent_block = ConvLSTM(input_size=out_channels, hidden_size=out_channels, kernel_size=3)
+        self.conv = ConvLayer(in_channels, out_channels, kernel_size, stride, padding, activation, norm, trainable=trainable)
+        self.recurrent_block = ConvLSTM(input_size=out_channels, hidden_size=out_channels, kernel_size=3, trainable=trainable)
 
     def forward(self, x, prev_state, conv_out=None):
         """conv_out (this implementation only): self.conv(x) when the caller has it already -- the convolution does not touch the state,
@@ -54,10 +55,12 @@ class RecurrentConvLayer(nn.Module):
 
 
 class UNetRecurrent(nn.Module):
-    """model/unet.py:252-310 (+ BaseUNet :13-64).  `unet_kwargs` as the reference's YAML gives them."""
+    """model/unet.py:252-310 (+ BaseUNet :13-64).  `unet_kwargs` as the reference's YAML gives them.  trainable=True: every layer records
+    its backward (v2v_amd/train.py) when grad is enabled; with grad disabled, or trainable=False, the network is the inference one."""
 
-    def __init__(self, unet_kwargs):
+    def __init__(self, unet_kwargs, trainable: bool = False):
         super().__init__()
+        self.trainable = bool(trainable)
         kw = dict(unet_kwargs)
         final_activation = kw.pop("final_activation", "none")
         self.final_activation = getattr(torch, final_activation, None) if final_activation else None
@@ -81,16 +84,19 @@ class UNetRecurrent(nn.Module):
         self.encoder_output_sizes = [int(self.base_num_channels * pow(mult, i + 1)) for i in range(self.num_encoders)]
         self.max_num_channels = self.encoder_output_sizes[-1]
         k = self.kernel_size
-        self.head = ConvLayer(self.num_bins, self.base_num_channels, kernel_size=k, stride=1, padding=k // 2)
+        self.head = ConvLayer(self.num_bins, self.base_num_channels, kernel_size=k, stride=1, padding=k // 2, trainable=trainable)
         self.head.force_channels_last = True               # NHWC from the first layer on, whatever layout the voxel grid arrives in
         self.encoders = nn.ModuleList(
-            RecurrentConvLayer(i, o, kernel_size=k, stride=2, padding=k // 2, recurrent_block_type=self.recurrent_block_type, norm=self.norm)
+            RecurrentConvLayer(i, o, kernel_size=k, stride=2, padding=k // 2, recurrent_block_type=self.recurrent_block_type, norm=self.norm,
+                               trainable=trainable)
             for i, o in zip(self.encoder_input_sizes, self.encoder_output_sizes))
-        self.resblocks = nn.ModuleList(ResidualBlock(self.max_num_channels, self.max_num_channels, norm=self.norm)
+        for enc in self.encoders:
+            enc.recurrent_block.wants_skip_twin = True         # training: the decoder's skip reads its own output of the step (fp32 dh sum)
+        self.resblocks = nn.ModuleList(ResidualBlock(self.max_num_channels, self.max_num_channels, norm=self.norm, trainable=trainable)
                                        for _ in range(self.num_residual_blocks))
-        self.decoders = nn.ModuleList(UpsampleConvLayer(i, o, kernel_size=k, padding=k // 2, norm=self.norm)
+        self.decoders = nn.ModuleList(UpsampleConvLayer(i, o, kernel_size=k, padding=k // 2, norm=self.norm, trainable=trainable)
                                       for i, o in zip(reversed(self.encoder_output_sizes), reversed(self.encoder_input_sizes)))
-        self.pred = ConvLayer(self.base_num_channels, self.num_output_channels, 1, activation=None, norm=self.norm)
+        self.pred = ConvLayer(self.base_num_channels, self.num_output_channels, 1, activation=None, norm=self.norm, trainable=trainable)
         self.states = [None] * self.num_encoders
 
     def _encode(self, x, event_scales, head=None, conv0=None):
@@ -104,8 +110,10 @@ class UNetRecurrent(nn.Module):
         blocks = []
         for i, encoder in enumerate(self.encoders):
             x, state = encoder(x, self.states[i], conv_out=conv0 if i == 0 else None)
-            blocks.append(x)
+            blocks.append(encoder.recurrent_block.skip_twin(x))
             self.states[i] = state
+        if blocks[-1] is not x:                                 # training: the skips are the steps' twin outputs; the residual blocks
+            blocks.append(x)                                    # read blocks[-1] = the last hidden state itself (_decode)
         return head, blocks
 
     def _decode(self, head, blocks):
@@ -155,6 +163,8 @@ class UNetRecurrent(nn.Module):
         out_dtype = torch.bfloat16 if (events.dtype == torch.bfloat16 or torch.is_autocast_enabled()) else events.dtype
         if out is None:
             out = torch.empty((n, t_steps, self.num_output_channels) + tuple(events.shape[-2:]), dtype=out_dtype, device=events.device)
+        if self.trainable and torch.is_grad_enabled():
+            overlap = False                                     # training: the plain step loop (autograd records every step on this stream)
         if not overlap:
             for t in range(t_steps):
                 head, blocks = self._encode(events[:, t], event_scales)
@@ -224,11 +234,12 @@ def copy_states(states):
 class E2VIDRecurrent(nn.Module):
     """model/model.py:194-223: `unetrecurrent` + the states property / reset_states the training loop uses."""
 
-    def __init__(self, unet_kwargs):
+    def __init__(self, unet_kwargs, trainable: bool = False):
         super().__init__()
         self.num_bins = unet_kwargs["num_bins"]
         self.num_encoders = unet_kwargs["num_encoders"]
-        self.unetrecurrent = UNetRecurrent(unet_kwargs)
+        self.trainable = bool(trainable)           # the YAML switch: model: {target: ..E2VIDRecurrent, params: {unet_kwargs: .., trainable: true}}
+        self.unetrecurrent = UNetRecurrent(unet_kwargs, trainable=trainable)
 
     @property
     def states(self):
@@ -253,9 +264,11 @@ class E2VIDRecurrent(nn.Module):
         then on: ~20 launches per time step cost the host ~12 ms per 40-step sequence when issued one by one, about what the GPU needs to
         run them.  Inputs are copied into the graph's static buffers; the returned tensor is the graph's static output (overwritten by
         the next call with the same shapes -- clone it to keep it); the states after the call are those of the sequence's last step.
-        Inference only, like every layer here."""
+        Inference only (with trainable=True and grad enabled: ValueError)."""
         if not graph:
             return self.unetrecurrent.forward_sequence(events, event_scales, out=out, overlap=overlap)
+        if self.trainable and torch.is_grad_enabled():
+            raise ValueError("graph=True captures inference only: run training steps with graph=False (or under torch.no_grad())")
         if out is not None:
             raise ValueError("graph=True returns the captured graph's own output buffer; `out` is not supported")
         params = list(self.parameters())

@@ -307,6 +307,27 @@ def test_conv3x3_matches_reference_semantics(shape, tile_rows, res, relu):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("cin,cout", [(64, 256), (32, 64)])
+def test_conv3x3_is_the_ks3_case_of_the_general_pair(cin, cout):
+    """pack_conv3x3_weights / conv3x3_nhwc are pack_conv_weights / conv_nhwc at ks = 3, bit for bit, and the packed stream has the
+    size the pack kernel writes (v2v_conv_packed_elems: for 32 input channels the taps are padded along K, so it is NOT Cout*Cin*9)."""
+    import torch
+    from v2v_amd import _lib
+    from v2v_amd import convlstm as CL
+    g = torch.Generator().manual_seed(cin + cout)
+    weight = ((torch.rand((cout, cin, 3, 3), generator=g) * 2 - 1) * (3.0 / np.sqrt(cin * 9))).cuda()
+    bias = ((torch.rand((cout,), generator=g) * 2 - 1) * 0.5).cuda()
+    x = torch.randn((2, 16, 16, cin), generator=g).to(torch.bfloat16).cuda()
+    r = torch.randn((2, 16, 16, cout), generator=g).to(torch.bfloat16).cuda()
+    p3, p = CL.pack_conv3x3_weights(weight), CL.pack_conv_weights(weight)
+    assert p3.numel() == p.numel() == _lib.lib().v2v_conv_packed_elems(cin, cout, 3) and torch.equal(p3, p)
+    for res, relu in ((None, False), (r, True)):
+        assert torch.equal(CL.conv3x3_nhwc(x, p3, bias, residual=res, relu=relu), CL.conv_nhwc(x, p, bias, 3, residual=res, relu=relu))
+    with pytest.raises(ValueError):
+        CL.pack_conv3x3_weights(torch.zeros((cout, cin, 5, 5), device="cuda"))
+
+
+@pytest.mark.gpu
 def test_residual_block_is_a_drop_in():
     """Same constructor / parameter names / forward contract as the reference's ResidualBlock; against the stock fp32 block with the
     same weights: 2e-2 absolute on unit-scale activations (bf16 operands, two convolutions); channels-last bf16 in place."""

@@ -1,0 +1,343 @@
+"""The raw NHWC bfloat16 operators of the recurrent UNet, forward and backward: one Python function per C entry point of the layer kernels
+(v2v_amd/csrc/v2v_convlstm.hpp, v2v_train_tu.hip), plus the packed-weight cache every layer shares.  No nn.Module and no autograd here:
+v2v_amd/train.py builds the torch.autograd.Functions on these, v2v_amd/convlstm.py the layers.
+
+    convlstm_step / conv_nhwc / conv3x3_nhwc / upsample2x_nhwc     the forward operators
+    conv1x1_nhwc                                           the 1x1 prediction layer on skip_sum(x, head)
+    conv_head_nhwc / to_nhwc8_bf16 / pack_head_weights     the head (voxel bins -> 32 channels)
+    pack_gate_weights / pack_conv_weights / pack_dgrad_weights     one-off weight packing; packed_weights = the cache in front of them
+    nchw_to_nhwc_bf16(x, relu=False)                      layout change in front of them (not needed for channels-last bf16 input)
+    relu_bwd_nhwc / conv_dgrad_nhwc / conv_wgrad_nhwc / upsample2x_bwd_nhwc / conv1x1_bwd_nhwc / convlstm_step_bwd     the backward operators
+
+Activations are bf16 NHWC with fp32 accumulation; activation gradients bf16 NHWC, the cell-state gradient fp32, parameter gradients fp32.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+
+import torch
+
+from . import _lib
+
+
+_DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def packed_weights(cache: dict, slot: str, w: torch.Tensor, pack) -> torch.Tensor:
+    """pack(w), kept in cache[slot] (a layer's `_packed` dict) and repacked when the weight changed: another tensor (load_state_dict into
+    a new parameter), an in-place update (_version: an optimizer step, copy_) or another device."""
+    key = (w.data_ptr(), w._version, w.device)
+    hit = cache.get(slot)
+    if hit is None or hit[0] != key:
+        hit = cache[slot] = (key, pack(w.detach()))
+    return hit[1]
+
+
+@functools.lru_cache(maxsize=None)
+def _conv_packed_elems(cin: int, cout: int, ks: int) -> int:
+    """v2v_conv_packed_elems (a pure function of three integers), asked once per shape instead of once per launch."""
+    return _lib.lib().v2v_conv_packed_elems(cin, cout, ks)
+
+
+# ---- layout ---------------------------------------------------------------------------------------------------------------------------
+def nchw_to_nhwc_bf16(x: torch.Tensor, relu: bool = False) -> torch.Tensor:
+    """float32 or bfloat16 [B,C,H,W] -> bfloat16 [B,H,W,C] (optionally through ReLU) in one HIP kernel."""
+    _lib.require_gpu()
+    if not x.is_cuda or x.dtype not in _DTYPES or x.dim() != 4:
+        raise ValueError("x must be a float32 or bfloat16 CUDA tensor [B,C,H,W]")
+    x = x.contiguous()
+    b, c, h, w = x.shape
+    out = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_nchw_to_nhwc_bf16_hip(_ptr(x), _DTYPES[x.dtype], b, c, h, w, int(bool(relu)), _ptr(out), _lib.stream_ptr()))
+    return out
+
+
+def _to_nhwc_bf16(x: torch.Tensor, relu: bool = False) -> torch.Tensor:
+    """[B,C,H,W] float32 / bfloat16 -> a contiguous bfloat16 [B,H,W,C] tensor: the layout kernel where it applies (64-channel x
+    64-pixel tiles: C % 64 == 0 and H*W % 64 == 0), one torch copy otherwise -- the same guard for every layer, so an odd
+    spatial size does not surface as an opaque V2V_ERR_SHAPE from the kernel."""
+    if x.shape[1] % 64 == 0 and (x.shape[2] * x.shape[3]) % 64 == 0:
+        return nchw_to_nhwc_bf16(x, relu=relu)
+    if relu:
+        x = torch.relu(x)
+    return x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
+
+
+def to_nhwc8_bf16(x, scales=None):
+    """float32 [B, C <= 8, H, W] of any strides -> bfloat16 [B, H, W, 8] with the channels zero-padded to 8: the head's input layout.
+    scales: optional float32 [B,2] = (neg_max, pos_max) per sample (v2v_amd.postops.scales_from_stats): normalize_batch_voxel's
+    where(x > 0, x / pos_max, x / neg_max) (model/train_utils.py:162-166) applied while the voxels are read."""
+    _lib.require_gpu()
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] > 8:
+        raise ValueError("x must be a float32 CUDA tensor [B, C <= 8, H, W]")
+    b, c, h, w = x.shape
+    if scales is not None and (scales.dtype != torch.float32 or tuple(scales.shape) != (b, 2) or not scales.is_contiguous() or scales.device != x.device):
+        raise ValueError(f"scales must be a contiguous float32 [{b},2] tensor on x's device")
+    out = torch.empty((b, h, w, 8), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_to_nhwc8_bf16_scaled_hip(_ptr(x), *x.stride(), b, c, h, w, _ptr(scales), _ptr(out), _lib.stream_ptr()))
+    return out
+
+
+# ---- the ConvLSTM step ------------------------------------------------------------------------------------------------------------------
+def pack_gate_weights(weight: torch.Tensor) -> torch.Tensor:
+    """Gates.weight float32 [4C, 2C, 3, 3] -> the packed bfloat16 stream the kernel reads (flat tensor)."""
+    _lib.require_gpu()
+    if not weight.is_cuda or weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) \
+            or weight.shape[0] != 2 * weight.shape[1]:
+        raise ValueError("weight must be a float32 CUDA tensor [4C, 2C, 3, 3]")
+    c = weight.shape[0] // 4
+    n = C.c_uint64(0)
+    _lib.check(_lib.lib().v2v_convlstm_packed_bytes(c, C.byref(n)))
+    packed = torch.empty((n.value // 2,), dtype=torch.bfloat16, device=weight.device)
+    with torch.cuda.device(weight.device):
+        _lib.check(_lib.lib().v2v_convlstm_pack_weights_hip(_ptr(weight.detach().contiguous()), c, _ptr(packed), _lib.stream_ptr()))
+    return packed
+
+
+def convlstm_step(x, h_prev, c_prev, packed, bias, nchw_dtype=torch.float32, tile_rows: int = 0, c_out=None):
+    """One step on NHWC state.  x, h_prev: bfloat16 [B,H,W,C]; c_prev: float32 [B,H,W,C]; h_prev / c_prev None = zero state.
+    Returns (h_state bf16 NHWC, c_state fp32 NHWC, h as [B,C,H,W] in nchw_dtype -- float32 / bfloat16 -- or None when
+    nchw_dtype is None).  c_out may be c_prev (updated in place)."""
+    _lib.require_gpu()
+    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("x must be a contiguous bfloat16 CUDA tensor [B,H,W,C]")
+    b, h, w, c = x.shape
+    for name, t, dt in (("h_prev", h_prev, torch.bfloat16), ("c_prev", c_prev, torch.float32)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (b, h, w, c) or not t.is_contiguous() or t.device != x.device):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor [B,H,W,C] on x's device")
+    if bias.dtype != torch.float32 or bias.numel() != 4 * c or packed.dtype != torch.bfloat16 or packed.numel() != 4 * c * 2 * c * 9:
+        raise ValueError("bias must be float32 [4C] and packed the output of pack_gate_weights for the same C")
+    h_state = torch.empty_like(x)
+    c_state = c_out if c_out is not None else torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
+    if nchw_dtype is not None and nchw_dtype not in _DTYPES:
+        raise ValueError("nchw_dtype must be torch.float32, torch.bfloat16 or None")
+    h_nchw = torch.empty((b, c, h, w), dtype=nchw_dtype, device=x.device) if nchw_dtype is not None else None
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_convlstm_step_hip(_ptr(x), _ptr(h_prev), _ptr(c_prev), _ptr(packed), _ptr(bias.detach().contiguous()),
+                                                    b, h, w, c, _ptr(h_state), _ptr(c_state), _ptr(h_nchw), _DTYPES.get(nchw_dtype, _lib.F32), tile_rows,
+                                                    _lib.stream_ptr()))
+    return h_state, c_state, h_nchw
+
+
+# ---- the convolutions (ConvLayer / UpsampleConvLayer / ResidualBlock, model/submodules.py:6-96, :143-177) on the same matrix-core kernel ---
+def pack_conv_weights(weight: torch.Tensor) -> torch.Tensor:
+    """nn.Conv2d(Cin, Cout, ks, padding=ks//2).weight float32 [Cout, Cin, ks, ks] (ks 3 or 5) -> the packed bfloat16 stream."""
+    _lib.require_gpu()
+    if not weight.is_cuda or weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
+        raise ValueError("weight must be a float32 CUDA tensor [Cout, Cin, ks, ks]")
+    cout, cin, ks = weight.shape[0], weight.shape[1], weight.shape[2]
+    n = _conv_packed_elems(cin, cout, ks)
+    if n < 0:
+        raise ValueError(f"the convolution kernel does not take {cin} -> {cout} channels, {ks}x{ks}")
+    packed = torch.empty((n,), dtype=torch.bfloat16, device=weight.device)
+    with torch.cuda.device(weight.device):
+        _lib.check(_lib.lib().v2v_conv_pack_weights_hip(_ptr(weight.detach().contiguous()), cin, cout, ks, _ptr(packed), _lib.stream_ptr()))
+    return packed
+
+
+def conv_nhwc(x, packed, bias, ks: int, stride: int = 1, residual=None, relu=False, tile_rows: int = 0):
+    """out = [relu](conv_ks(x, stride, pad ks//2) + bias [+ residual]) on NHWC bfloat16: x [B,Hin,Win,Cin] -> [B,Hout,Wout,Cout]."""
+    _lib.require_gpu()
+    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("x must be a contiguous bfloat16 CUDA tensor [B,H,W,Cin]")
+    b, hin, win, cin = x.shape
+    cout = bias.numel()
+    if bias.dtype != torch.float32 or packed.dtype != torch.bfloat16 or packed.numel() != _conv_packed_elems(cin, cout, ks):
+        raise ValueError("bias must be float32 [Cout] and packed the output of pack_conv_weights for the same Cin, Cout, ks")
+    h, w = (hin - 1) // stride + 1, (win - 1) // stride + 1
+    if residual is not None and (residual.dtype != torch.bfloat16 or tuple(residual.shape) != (b, h, w, cout) or not residual.is_contiguous()
+                                 or residual.device != x.device):
+        raise ValueError("residual must be a contiguous bfloat16 tensor [B,Hout,Wout,Cout] on x's device")
+    out = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_conv_nhwc_hip(_ptr(x), _ptr(packed), _ptr(bias.detach().contiguous()), _ptr(residual), int(bool(relu)),
+                                                b, hin, win, cin, cout, ks, stride, _ptr(out), tile_rows, _lib.stream_ptr()))
+    return out
+
+
+def pack_conv3x3_weights(weight: torch.Tensor) -> torch.Tensor:
+    """nn.Conv2d(Cin, Cout, 3, padding=1).weight float32 [Cout, Cin, 3, 3] -> its packed bfloat16 stream: pack_conv_weights at ks = 3."""
+    if weight.dim() == 4 and tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError("weight must be a float32 CUDA tensor [Cout, Cin, 3, 3]")
+    return pack_conv_weights(weight)
+
+
+def conv3x3_nhwc(x, packed, bias, residual=None, relu=False, tile_rows: int = 0):
+    """out = [relu](conv3x3(x) + bias [+ residual]) on NHWC bfloat16: x [B,H,W,Cin], residual / out [B,H,W,Cout]: conv_nhwc at ks = 3."""
+    return conv_nhwc(x, packed, bias, 3, residual=residual, relu=relu, tile_rows=tile_rows)
+
+
+def upsample2x_nhwc(x, skip=None):
+    """out = bilinear_x2(x [+ skip]) on NHWC bfloat16 ([B,H,W,C] -> [B,2H,2W,C]): f.interpolate(scale_factor=2, mode='bilinear',
+    align_corners=False) of UpsampleConvLayer.forward (model/submodules.py:86-87) behind the sum skip (model/unet.py:304)."""
+    _lib.require_gpu()
+    for name, v in (("x", x), ("skip", skip)):
+        if v is not None and (not v.is_cuda or v.dtype != torch.bfloat16 or v.dim() != 4 or not v.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous bfloat16 CUDA tensor [B,H,W,C]")
+    if skip is not None and (skip.shape != x.shape or skip.device != x.device):
+        raise ValueError("skip must have x's shape and device")
+    b, h, w, c = x.shape
+    out = torch.empty((b, 2 * h, 2 * w, c), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_upsample2x_nhwc_hip(_ptr(x), _ptr(skip), b, h, w, c, _ptr(out), _lib.stream_ptr()))
+    return out
+
+
+def conv1x1_nhwc(x, weight, bias, skip=None, out_dtype=torch.bfloat16):
+    """out[..., o] = bias[o] + sum_c weight[o, c] * (x[..., c] + skip[..., c]) on NHWC bfloat16 ([B,H,W,C] -> [B,H,W,Cout], Cout <= 3):
+    the prediction layer ConvLayer(base, out, 1, activation=None) on skip_sum(x, head) (model/unet.py:58-64, :307)."""
+    _lib.require_gpu()
+    for name, v in (("x", x), ("skip", skip)):
+        if v is not None and (not v.is_cuda or v.dtype != torch.bfloat16 or v.dim() != 4 or not v.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous bfloat16 CUDA tensor [B,H,W,C]")
+    if skip is not None and (skip.shape != x.shape or skip.device != x.device):
+        raise ValueError("skip must have x's shape and device")
+    b, h, w, c = x.shape
+    weight = weight.detach().reshape(weight.shape[0], -1).float().contiguous()
+    if weight.shape[1] != c or bias.numel() != weight.shape[0] or out_dtype not in _DTYPES:
+        raise ValueError("weight must be [Cout, C(,1,1)], bias [Cout], out_dtype float32 or bfloat16")
+    out = torch.empty((b, h, w, weight.shape[0]), dtype=out_dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_conv1x1_nhwc_hip(_ptr(x), _ptr(skip), _ptr(weight), _ptr(bias.detach().float().contiguous()), b * h * w, c,
+                                                   weight.shape[0], _ptr(out), _DTYPES[out_dtype], _lib.stream_ptr()))
+    return out
+
+
+def pack_head_weights(weight):
+    """nn.Conv2d(Cin <= 8, 32, ks, padding=ks//2).weight float32 -> the head kernel's packed bfloat16 stream (taps along K)."""
+    _lib.require_gpu()
+    if not weight.is_cuda or weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[0] != 32 or weight.shape[1] > 8 \
+            or weight.shape[2] != weight.shape[3] or weight.shape[2] not in (3, 5):
+        raise ValueError("weight must be a float32 CUDA tensor [32, Cin <= 8, ks, ks], ks 3 or 5")
+    ks = weight.shape[2]
+    packed = torch.empty((_lib.lib().v2v_conv_head_packed_elems(ks),), dtype=torch.bfloat16, device=weight.device)
+    with torch.cuda.device(weight.device):
+        _lib.check(_lib.lib().v2v_conv_head_pack_weights_hip(_ptr(weight.detach().contiguous()), weight.shape[1], ks, _ptr(packed), _lib.stream_ptr()))
+    return packed
+
+
+def conv_head_nhwc(x8, packed, bias, ks: int, relu=True):
+    """out = [relu](conv_ks(x, stride 1, pad ks//2) + bias): x8 [B,H,W,8] bfloat16 (to_nhwc8_bf16) -> [B,H,W,32] bfloat16; the UNet's
+    head ConvLayer(num_bins, 32, 5, stride 1, padding 2) (model/unet.py:77-78).  H and W multiples of 16."""
+    _lib.require_gpu()
+    if not x8.is_cuda or x8.dtype != torch.bfloat16 or x8.dim() != 4 or x8.shape[3] != 8 or not x8.is_contiguous():
+        raise ValueError("x8 must be a contiguous bfloat16 CUDA tensor [B,H,W,8]")
+    if bias.numel() != 32 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_conv_head_packed_elems(ks):
+        raise ValueError("bias must be [32] and packed the output of pack_head_weights for the same ks")
+    b, h, w, _ = x8.shape
+    out = torch.empty((b, h, w, 32), dtype=torch.bfloat16, device=x8.device)
+    with torch.cuda.device(x8.device):
+        _lib.check(_lib.lib().v2v_conv_head_nhwc_hip(_ptr(x8), _ptr(packed), _ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w, ks,
+                                                     _ptr(out), _lib.stream_ptr()))
+    return out
+
+
+# ---- backward: the data gradient of a convolution is the stride-1 convolution of the output gradient (spread onto the input grid for
+# stride 2) with the flipped, transposed weights on the forward convolution kernel; the weight / bias gradient is an MFMA GEMM over the
+# pixels (slabs + a fixed-order sum); the ConvLSTM step recomputes its gate GEMM and runs the cell backward on the accumulators -------------
+def _workspace(nbytes: int, device) -> torch.Tensor:
+    if nbytes < 0:
+        raise ValueError("shape not taken by the backward kernels")
+    return torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=device)
+
+
+def _nhwc_bf16(t: torch.Tensor) -> torch.Tensor:
+    if t.dtype != torch.bfloat16:
+        t = t.to(torch.bfloat16)
+    return t.contiguous()
+
+
+def relu_bwd_nhwc(dy, y):
+    """y > 0 ? dy : 0 on NHWC bfloat16 (y = the saved post-ReLU output)."""
+    dy = _nhwc_bf16(dy)
+    out = torch.empty_like(dy)
+    with torch.cuda.device(dy.device):
+        _lib.check(_lib.lib().v2v_relu_bwd_nhwc_hip(_ptr(dy), _ptr(y), dy.numel() // dy.shape[-1], dy.shape[-1], _ptr(out), _lib.stream_ptr()))
+    return out
+
+
+def pack_dgrad_weights(weight: torch.Tensor) -> torch.Tensor:
+    """nn.Conv2d weight float32 [Cout, Cin, ks, ks] -> the packed stream of the transposed convolution (Cout -> Cin, flipped taps)."""
+    cout, cin, ks = weight.shape[0], weight.shape[1], weight.shape[2]
+    n = _lib.lib().v2v_conv_dgrad_packed_elems(cin, cout, ks)
+    if n < 0:
+        raise ValueError(f"no data-gradient kernel for {cin} -> {cout} channels, {ks}x{ks}")
+    packed = torch.empty((n,), dtype=torch.bfloat16, device=weight.device)
+    scratch = torch.empty((weight.numel(),), dtype=torch.float32, device=weight.device)
+    with torch.cuda.device(weight.device):
+        _lib.check(_lib.lib().v2v_conv_dgrad_pack_weights_hip(_ptr(weight.detach().float().contiguous()), cin, cout, ks, _ptr(scratch), _ptr(packed),
+                                                              _lib.stream_ptr()))
+    return packed
+
+
+def conv_dgrad_nhwc(dy, packed, cin: int, ks: int, stride: int, hin: int, win: int, residual=None):
+    """dx [B,Hin,Win,Cin] bf16 of a ks x ks convolution (pad ks//2) from its output gradient dy [B,Hout,Wout,Cout] (ReLU already applied)."""
+    dy = _nhwc_bf16(dy)
+    b, cout = dy.shape[0], dy.shape[3]
+    ws = _workspace(_lib.lib().v2v_conv_dgrad_workspace_bytes(b, hin, win, cin, cout, stride), dy.device)
+    dx = torch.empty((b, hin, win, cin), dtype=torch.bfloat16, device=dy.device)
+    with torch.cuda.device(dy.device):
+        _lib.check(_lib.lib().v2v_conv_dgrad_nhwc_hip(_ptr(dy), _ptr(packed), _ptr(residual), b, hin, win, cin, cout, ks, stride, _ptr(ws), _ptr(dx),
+                                                      _lib.stream_ptr()))
+    return dx
+
+
+def conv_wgrad_nhwc(dy, x1, x2=None, c2: int = 0, cin_out: int | None = None, ks: int = 3, stride: int = 1):
+    """(dW float32 [Cout, Cin_out, ks, ks], db float32 [Cout]) of a convolution with input x1 [B,Hin,Win,C1] | x2 [.., C2] (x2 None = zeros)."""
+    dy = _nhwc_bf16(dy)
+    b, ho, wo, cout = dy.shape
+    hin, win, c1 = x1.shape[1], x1.shape[2], x1.shape[3]
+    cin_out = c1 + c2 if cin_out is None else cin_out
+    ws = _workspace(_lib.lib().v2v_conv_wgrad_workspace_bytes(b, ho, wo, c1 + c2, cout, ks), dy.device)
+    dw = torch.empty((cout, cin_out, ks, ks), dtype=torch.float32, device=dy.device)
+    db = torch.empty((cout,), dtype=torch.float32, device=dy.device)
+    with torch.cuda.device(dy.device):
+        _lib.check(_lib.lib().v2v_conv_wgrad_nhwc_hip(_ptr(dy), _ptr(x1), c1, _ptr(x2), c2, cin_out, b, hin, win, cout, ks, stride, _ptr(ws), _ptr(dw),
+                                                      _ptr(db), _lib.stream_ptr()))
+    return dw, db
+
+
+def upsample2x_bwd_nhwc(dout):
+    """Adjoint of upsample2x_nhwc: [B,2H,2W,C] -> [B,H,W,C] bf16 (the gradient of x and of the skip)."""
+    dout = _nhwc_bf16(dout)
+    b, h2, w2, c = dout.shape
+    dx = torch.empty((b, h2 // 2, w2 // 2, c), dtype=torch.bfloat16, device=dout.device)
+    with torch.cuda.device(dout.device):
+        _lib.check(_lib.lib().v2v_upsample2x_bwd_nhwc_hip(_ptr(dout), b, h2 // 2, w2 // 2, c, _ptr(dx), _lib.stream_ptr()))
+    return dx
+
+
+def conv1x1_bwd_nhwc(dy, x, skip, weight):
+    """Prediction layer (C -> 1 on bf16(x + skip)): dy [B,H,W,1] (read as float32) -> (dx [B,H,W,C] bf16 = the gradient of x and skip,
+    dW [1,C,1,1], db [1])."""
+    dy = dy.float().contiguous()
+    b, h, w, c = x.shape
+    m = b * h * w
+    ws = _workspace(_lib.lib().v2v_conv1x1_bwd_workspace_bytes(m, c), x.device)
+    dx = torch.empty_like(x)
+    dw = torch.empty((c,), dtype=torch.float32, device=x.device)
+    db = torch.empty((1,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_conv1x1_bwd_nhwc_hip(_ptr(dy), _ptr(x), _ptr(skip), _ptr(weight.detach().float().reshape(-1).contiguous()), m, c,
+                                                       _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), _lib.stream_ptr()))
+    return dx, dw.reshape(weight.shape), db
+
+
+def convlstm_step_bwd(x, h_prev, c_prev, packed, bias, dh, dc):
+    """Backward of convlstm_step from the saved x / h_prev / c_prev: (dgates bf16 [B,H,W,4C], dc_prev float32 [B,H,W,C])."""
+    b, h, w, c = x.shape
+    dh = dh.float().contiguous()
+    dc = dc.float().contiguous() if dc is not None else None
+    dgates = torch.empty((b, h, w, 4 * c), dtype=torch.bfloat16, device=x.device)
+    dc_prev = torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_convlstm_step_bwd_hip(_ptr(x), _ptr(h_prev), _ptr(c_prev), _ptr(packed), _ptr(bias), _ptr(dh), _ptr(dc), b, h, w, c,
+                                                        _ptr(dgates), _ptr(dc_prev), _lib.stream_ptr()))
+    return dgates, dc_prev

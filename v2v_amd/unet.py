@@ -135,10 +135,7 @@ class UNetRecurrent(nn.Module):
         pack kernels have written them (and the packed tensors would live in one side stream's allocator pool while every stream reads
         them).  Packed here, they are ordered before every side stream by the wait_stream() that follows."""
         for m in self.modules():
-            if isinstance(m, ResidualBlock):
-                m._weights(m.conv1, "conv1")
-                m._weights(m.conv2, "conv2")
-            elif isinstance(m, ConvLSTM) or (isinstance(m, ConvLayer) and m.conv2d.kernel_size[0] != 1):   # the 1x1 prediction layer has no packed copy
+            if isinstance(m, (ConvLayer, ConvLSTM, ResidualBlock)):
                 m._weights()
 
     def forward_sequence(self, events, event_scales=None, out=None, overlap=True):

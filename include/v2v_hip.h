@@ -473,6 +473,29 @@ int v2v_clip_frames_f32_bounded_hip(const void *src, int64_t clip_stride, const 
                                     int64_t pick_stride, const int32_t *stored_frames, int64_t src_elems, int64_t B, int64_t L, int64_t H, int64_t W,
                                     int64_t C, float *out, void *stream);
 
+/* ---- the plain UNet (EVFlowNet, model/unet.py:313-352): stem, concat skips, a trainable prediction of 1..3 outputs -------------------
+ * Stem = UNet.encoders[0]: x8 bf16 [B,H,W,8] (what v2v_to_nhwc8_bf16[_scaled]_hip makes) -> out bf16 [B,H/2,W/2,64] =
+ * [relu](conv3x3(x, stride 2, pad 1) + bias); weight float32 [64, Cin <= 8, 3, 3] packed once; H, W multiples of 16. */
+int64_t v2v_conv_stem_packed_elems(void);
+int v2v_conv_stem_pack_weights_hip(const float *weight, int64_t Cin, void *packed, void *stream);
+int v2v_conv_stem_nhwc_hip(const void *x8, const void *packed, const float *bias, int relu, int64_t B, int64_t H, int64_t W, void *out, void *stream);
+/* Concat skip in front of a decoder: out bf16 [B,2H,2W,C1+C2] = cat(up2(x [B,H,W,C1]), up2(skip [B,H,W,C2])) along the channels, i.e. the
+ * bilinear x2 upsampling (align_corners = false) of cat(x, skip) without ever writing that tensor; the arithmetic of the sum-skip upsampling
+ * entry above, per channel.  C1, C2 multiples of 8; skip NULL with C2 = 0 gives that entry's result without a skip, bit for bit. */
+int v2v_upsample2x_cat_nhwc_hip(const void *x, int64_t C1, const void *skip, int64_t C2, int64_t B, int64_t H, int64_t W, void *out, void *stream);
+/* Its adjoint for one channel slice: dout bf16 [B,2H,2W,Ctot], channels [c0, c0 + C) -> dx bf16 [B,H,W,C] (fp32 sums, gather form, no
+ * atomics).  c0 = 0 and C = Ctot gives the sum-skip adjoint's result bit for bit. */
+int v2v_upsample2x_cat_bwd_nhwc_hip(const void *dout, int64_t B, int64_t H, int64_t W, int64_t Ctot, int64_t c0, int64_t C, void *dx, void *stream);
+/* Backward of the prediction layer for Cout = 1..3: dy fp32 [M,Cout] -> dx bf16 [M,C] = sum_o dy[m][o] * bf16(w[o][c]) (one rounding),
+ * dw fp32 [Cout,C], db fp32 [Cout] by fixed-order slab sums (bitwise reproducible).  C a power of two in 8..128; skip may be NULL. */
+int64_t v2v_conv1x1_bwd_cout_workspace_bytes(int64_t M, int64_t C, int64_t Cout);
+int v2v_conv1x1_bwd_cout_nhwc_hip(const float *dy, const void *x, const void *skip, const float *weight, int64_t M, int64_t C, int64_t Cout, void *dx,
+                                  float *dw, float *db, void *workspace, void *stream);
+/* The convolution entry with its automatic tile chosen as for a batch of B_like images (0: B): a batch that folds T time steps of B_like
+ * images runs the instance a single step would, so every image comes out bit-identical to the per-step launch. */
+int v2v_conv_nhwc_like_hip(const void *x, const void *packed, const float *bias, const void *residual, int relu, int64_t B, int64_t Hin, int64_t Win,
+                           int64_t Cin, int64_t Cout, int ks, int stride, void *out, int64_t B_like, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

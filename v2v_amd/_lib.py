@@ -30,7 +30,9 @@ EXPORTS = ("v2v_version", "v2v_last_error", "v2v_device_count", "v2v_lut_get", "
            "v2v_esim_voxel_stats_hip", "v2v_voxel_scales_hip", "v2v_voxel_apply_scales_hip", "v2v_voxel_scales_select_hip", "v2v_to_nhwc8_bf16_scaled_hip", "v2v_esim_voxel_ex_hip", "v2v_clip_frames_f32_ex_hip", "v2v_clip_frames_f32_bounded_hip",
            "v2v_convlstm_step_bwd_hip", "v2v_relu_bwd_nhwc_hip", "v2v_conv_dgrad_packed_elems", "v2v_conv_dgrad_pack_weights_hip",
            "v2v_conv_dgrad_workspace_bytes", "v2v_conv_dgrad_nhwc_hip", "v2v_conv_wgrad_workspace_bytes", "v2v_conv_wgrad_nhwc_hip",
-           "v2v_upsample2x_bwd_nhwc_hip", "v2v_conv1x1_bwd_workspace_bytes", "v2v_conv1x1_bwd_nhwc_hip")
+           "v2v_upsample2x_bwd_nhwc_hip", "v2v_conv1x1_bwd_workspace_bytes", "v2v_conv1x1_bwd_nhwc_hip",
+           "v2v_conv_stem_packed_elems", "v2v_conv_stem_pack_weights_hip", "v2v_conv_stem_nhwc_hip", "v2v_upsample2x_cat_nhwc_hip",
+           "v2v_upsample2x_cat_bwd_nhwc_hip", "v2v_conv1x1_bwd_cout_workspace_bytes", "v2v_conv1x1_bwd_cout_nhwc_hip", "v2v_conv_nhwc_like_hip")
 EV_MAKE_VOXEL_DISCRETE, EV_MAKE_VOXEL_INTERP, EV_BILINEAR = 0, 1, 2
 NORM_NONE, NORM_RADIX, NORM_COUNT = 0, 1, 2
 VOXEL_STATS_WORDS = 516
@@ -205,7 +207,16 @@ def lib():
             ("v2v_conv_wgrad_nhwc_hip", C.c_int, [P, P, I64, P, I64, I64, I64, I64, I64, I64, C.c_int, C.c_int, P, P, P, P]),
             ("v2v_upsample2x_bwd_nhwc_hip", C.c_int, [P] + [I64] * 4 + [P, P]),
             ("v2v_conv1x1_bwd_workspace_bytes", I64, [I64, I64]),
-            ("v2v_conv1x1_bwd_nhwc_hip", C.c_int, [P, P, P, P, I64, I64, P, P, P, P, P])):
+            ("v2v_conv1x1_bwd_nhwc_hip", C.c_int, [P, P, P, P, I64, I64, P, P, P, P, P]),
+            # the plain UNet (EVFlowNet): stem, concat-skip upsampling + adjoint, prediction backward for 1..3 outputs
+            ("v2v_conv_stem_packed_elems", I64, []),
+            ("v2v_conv_stem_pack_weights_hip", C.c_int, [P, I64, P, P]),
+            ("v2v_conv_stem_nhwc_hip", C.c_int, [P, P, P, C.c_int, I64, I64, I64, P, P]),
+            ("v2v_upsample2x_cat_nhwc_hip", C.c_int, [P, I64, P, I64, I64, I64, I64, P, P]),
+            ("v2v_upsample2x_cat_bwd_nhwc_hip", C.c_int, [P] + [I64] * 6 + [P, P]),
+            ("v2v_conv1x1_bwd_cout_workspace_bytes", I64, [I64, I64, I64]),
+            ("v2v_conv1x1_bwd_cout_nhwc_hip", C.c_int, [P, P, P, P, I64, I64, I64, P, P, P, P, P]),
+            ("v2v_conv_nhwc_like_hip", C.c_int, [P, P, P, P, C.c_int] + [I64] * 5 + [C.c_int, C.c_int, P, I64, P])):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     if L.v2v_version() != ABI_VERSION:

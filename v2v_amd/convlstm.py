@@ -11,6 +11,7 @@ v2v_upsample2x_nhwc_hip.
     convlstm_step / conv_nhwc / conv3x3_nhwc / upsample2x_nhwc     the raw NHWC bfloat16 operators (v2v_amd/nhwc_ops.py, re-exported here)
     conv1x1_nhwc                                           the 1x1 prediction layer on skip_sum(x, head) (ConvLayer with kernel_size 1)
     conv_head_nhwc / to_nhwc8_bf16 / pack_head_weights     the head (voxel bins -> 32 channels; ConvLayer with <= 8 input channels)
+    conv_stem_nhwc / pack_stem_weights / upsample2x_cat_nhwc   the plain UNet (EVFlowNet): its stem (voxel bins -> 64, 3x3, stride 2) and concat skips
     pack_gate_weights / pack_conv_weights                  one-off weight packing
     nchw_to_nhwc_bf16(x, relu=False)                      layout change in front of them (not needed for channels-last bf16 input)
 
@@ -24,10 +25,10 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from .nhwc_ops import (_to_nhwc_bf16, conv1x1_nhwc, conv3x3_nhwc, conv_head_nhwc, conv_nhwc, convlstm_step, nchw_to_nhwc_bf16,  # noqa: F401
-                       pack_conv3x3_weights, pack_conv_weights, pack_gate_weights, pack_head_weights, packed_weights, to_nhwc8_bf16,
-                       upsample2x_nhwc)
-from .train import ConvFn, ConvLSTMFn, HeadFn, PredFn, ResidualBlockFn, UpConvFn
+from .nhwc_ops import (_to_nhwc_bf16, conv1x1_nhwc, conv3x3_nhwc, conv_head_nhwc, conv_nhwc, conv_stem_nhwc, convlstm_step, nchw_to_nhwc_bf16,  # noqa: F401
+                       pack_conv3x3_weights, pack_conv_weights, pack_gate_weights, pack_head_weights, pack_stem_weights, packed_weights,
+                       to_nhwc8_bf16, upsample2x_cat_nhwc, upsample2x_nhwc)
+from .train import ConvFn, ConvLSTMFn, HeadFn, PredFn, ResidualBlockFn, StemFn, UpCatConvFn, UpConvFn
 
 
 def _training(layer, x) -> bool:
@@ -184,7 +185,8 @@ class ConvLayer(nn.Module):
     UpsampleConvLayer (:68-96).  Inference by default, trainable=True records its backward under grad; bfloat16 operands, fp32 accumulation; channels-last bfloat16
     inputs are consumed and produced in place, anything else goes through the layout-change kernel and comes back NCHW in the
     input's dtype.  in_channels % 64 == 0 and out_channels in {32, 64, 128, 256k}; in_channels 32 with 64 / 128 outputs (the first
-    encoder); <= 8 input channels with 32 outputs = the head; kernel_size 1 = the prediction layer; else ValueError (no fallback)."""
+    encoder); <= 8 input channels with 32 outputs, stride 1 = the head, with 64 outputs, kernel_size 3, stride 2 = the plain UNet's stem;
+    kernel_size 1 = the prediction layer; else ValueError (no fallback)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, activation="relu", norm=None, BN_momentum=0.1,
                  upsample=False, trainable: bool = False):
@@ -195,10 +197,13 @@ class ConvLayer(nn.Module):
                              "kernel_size // 2, stride 1 or 2, and the 1x1 prediction layer (stride 1, no activation, <= 3 outputs)")
         self.conv2d = nn.Conv2d(in_channels, out_channels, kernel_size, stride, padding, bias=True)
         self.relu, self.upsample = activation == "relu", upsample
-        self.head = in_channels <= 8 and kernel_size in (3, 5)                  # the UNet's head: voxel bins -> 32 channels
+        # the plain UNet's stem (model/unet.py:320-326): voxel bins -> 64 channels, 3x3, stride 2
+        self.stem = in_channels <= 8 and kernel_size == 3 and stride == 2 and out_channels == 64 and not upsample
+        self.head = in_channels <= 8 and kernel_size in (3, 5) and not self.stem   # the recurrent UNet's head: voxel bins -> 32 channels
         if self.head and (out_channels != 32 or stride != 1 or upsample):
-            raise ValueError("with <= 8 input channels the fused ConvLayer is the UNet's head: 32 output channels, stride 1")
-        self.force_channels_last = False          # head only: hand out the kernel's NHWC buffer as a channels-last view whatever came in
+            raise ValueError("with <= 8 input channels the fused ConvLayer is the recurrent UNet's head (32 output channels, stride 1) or the "
+                             "plain UNet's stem (64 output channels, kernel_size 3, stride 2)")
+        self.force_channels_last = False          # head / stem only: hand out the kernel's NHWC buffer as a channels-last view whatever came in
         self._packed = {}                         # nhwc_ops.packed_weights' cache
         self.trainable = trainable                # True: under grad, forward records a v2v_amd.train Function (ConvFn / UpConvFn / HeadFn / PredFn)
 
@@ -206,24 +211,25 @@ class ConvLayer(nn.Module):
         """Everything forward needs packed, now (on the current stream): the convolution's packed stream (None for the 1x1 prediction
         layer: its kernel reads the float32 weight)."""
         w = self.conv2d.weight
-        if self.head:
-            return packed_weights(self._packed, "conv2d", w, pack_head_weights)
+        if self.head or self.stem:
+            return packed_weights(self._packed, "conv2d", w, pack_head_weights if self.head else pack_stem_weights)
         return packed_weights(self._packed, "conv2d", w, pack_conv_weights) if w.shape[2] != 1 else None
 
-    def forward(self, x, skip=None, scales=None):
+    def forward(self, x, skip=None, scales=None, skip_type="sum"):
         """skip (upsample=True only): the sum skip connection model/unet.py:304 adds in front of the decoder, folded into the
         upsampling kernel -- layer(x, skip) == layer(x + skip).  Under training the fusions are differentiated as fused (the skip into
-        the upsampling, pred(x + head))."""
+        the upsampling, pred(x + head)).  skip_type "concat" (upsample=True only): layer(x, skip) == layer(cat(x, skip)), the plain UNet's
+        concat skip (model/unet.py:350) -- each source is upsampled into its channel slice, the low-resolution cat is never written."""
         train = _training(self, x)
         conv = self.conv2d
-        if scales is not None and not self.head:
+        if skip_type not in ("sum", "concat") or (skip_type == "concat" and (not self.upsample or skip is None)):
+            raise ValueError("skip_type is 'sum' or 'concat'; 'concat' is the decoder's (upsample=True) skip and needs one")
+        if scales is not None and not (self.head or self.stem):
             # only the head kernel (<= 8 input channels, 3x3 / 5x5) divides by normalize_batch_voxel's scales while it reads; anything else
             # would silently run on raw, un-normalised events (RingLoader(normalize='scales') hands out raw voxels)
             raise ValueError("`scales` is applied by the head kernel only (in_channels <= 8, kernel 3 or 5): normalise the events first "
                              "(v2v_amd.postops.apply_scales / RingLoader(normalize=True)) for this layer")
         if conv.kernel_size[0] == 1:                                                   # prediction layer: pred(skip_sum(x, head)), model/unet.py:307
-            if train and conv.out_channels != 1:
-                raise ValueError("the trainable prediction layer has one output channel (model/unet.py:263)")
             nhwc = all(v is None or _is_nhwc_bf16(v) for v in (x, skip))
             if not nhwc:
                 x, skip = (x if skip is None else x + skip), None
@@ -235,16 +241,24 @@ class ConvLayer(nn.Module):
             return _nchw_out(out, x, nhwc)
         if skip is not None and not self.upsample:
             raise ValueError("skip is the decoder's (upsample=True) sum skip connection")
-        if self.head:                                                                  # model/unet.py:77-78: any float layout in, bf16 out
+        if self.head or self.stem:                                                     # model/unet.py:77-78 / :320-326: any float layout in, bf16 out
             if train and x.requires_grad:
-                raise ValueError("the trainable head computes no gradient for its input (the voxel grid)")
+                raise ValueError("the trainable head / stem computes no gradient for its input (the voxel grid)")
             low = x.dtype == torch.bfloat16 or (x.is_cuda and torch.is_autocast_enabled())
             # channels-last out when the input or (as torch's own convolution decides) the weight is channels-last
             cl = self.force_channels_last or _is_channels_last(x) or _is_channels_last(conv.weight)
             x8 = to_nhwc8_bf16(x.detach().float(), scales)
-            out = (HeadFn.apply(x8, conv.weight, conv.bias, self) if train else HeadFn.kernels(x8, self)).permute(0, 3, 1, 2)
+            fn = HeadFn if self.head else StemFn
+            out = (fn.apply(x8, conv.weight, conv.bias, self) if train else fn.kernels(x8, self)).permute(0, 3, 1, 2)
             out = out if cl else out.contiguous()
             return out if low else out.to(x.dtype)
+        if skip_type == "concat":
+            if conv.in_channels != x.shape[1] + skip.shape[1]:
+                raise ValueError(f"concat skip: conv2d.in_channels {conv.in_channels} != {x.shape[1]} + {skip.shape[1]}")
+            nhwc_io = _is_nhwc_bf16(x) and _is_nhwc_bf16(skip)
+            xn, sn = _nhwc_in(x, _is_nhwc_bf16(x), train), _nhwc_in(skip, _is_nhwc_bf16(skip), train)
+            out = UpCatConvFn.apply(xn, sn, conv.weight, conv.bias, self) if train else UpCatConvFn.kernels(xn, sn, self)[0]
+            return _nchw_out(out, x, nhwc_io)
         nhwc_io = _is_nhwc_bf16(x)
         if skip is not None and not (nhwc_io and _is_nhwc_bf16(skip)):
             x, skip = x + skip, None

@@ -123,10 +123,16 @@ hipError_t launch_upsample2x_bwd(const uint16_t *dout, uint16_t *dx, int B, int 
 hipError_t launch_conv1x1_bwd(const float *dy, const uint16_t *x, const uint16_t *skip, const float *w, uint16_t *dx, float *dw, float *db, float *ws,
                               int64_t M, int C, hipStream_t s);
 int64_t conv1x1_bwd_slabs(int64_t M);
-hipError_t launch_conv_nhwc(const ConvLstmArgs &a, int tile_rows, hipStream_t s);
+hipError_t launch_conv_nhwc(const ConvLstmArgs &a, int tile_rows, hipStream_t s, int64_t like_b = 0);   // like_b: batch the automatic tile is chosen for (0: a.B)
 int conv_tile_cols(int Cout);             // columns per tile of the instance launch_conv_nhwc takes for Cout (0: unsupported)
 hipError_t launch_conv_head(const uint16_t *x8, const uint16_t *wp, const float *bias, uint16_t *out, int B, int H, int W, int ks, int relu, hipStream_t s);
 hipError_t launch_conv_head_pack(const float *w, uint16_t *wp, int Cin, int ks, hipStream_t s);
+hipError_t launch_conv_stem(const uint16_t *x8, const uint16_t *wp, const float *bias, uint16_t *out, int B, int H, int W, int relu, hipStream_t s);
+hipError_t launch_conv_stem_pack(const float *w, uint16_t *wp, int Cin, hipStream_t s);
+hipError_t launch_upsample2x_cat_nhwc(const uint16_t *x, int C1, const uint16_t *skip, int C2, uint16_t *out, int B, int H, int W, hipStream_t s);
+hipError_t launch_upsample2x_cat_bwd(const uint16_t *dout, uint16_t *dx, int B, int H, int W, int Ctot, int c0, int C, hipStream_t s);
+hipError_t launch_conv1x1_bwd_cout(const float *dy, const uint16_t *x, const uint16_t *skip, const float *w, uint16_t *dx, float *dw, float *db, float *ws,
+                                   int64_t M, int C, int Cout, hipStream_t s);
 hipError_t launch_to_nhwc8_bf16(const float *src, int64_t sb, int64_t sc, int64_t sh, int64_t sw, uint16_t *dst, int B, int C, int H, int W, const float *scales, hipStream_t s);
 hipError_t launch_conv1x1_nhwc(const uint16_t *x, const uint16_t *skip, const float *w, const float *bias, void *out, int out_bf16, int64_t M,
                                int C, int Cout, hipStream_t s);

@@ -1138,4 +1138,96 @@ int v2v_conv1x1_bwd_nhwc_hip(const float *dy, const void *x, const void *skip, c
     return e == hipSuccess ? V2V_OK : hip_fail(e, "conv1x1_bwd_kernel launch");
 }
 
+// ---- the plain UNet (EVFlowNet): stem, concat-skip upsampling and its adjoint, the prediction backward for 1..3 outputs ----------------
+int64_t v2v_conv_stem_packed_elems(void) { return 2 * 64 * 64; }
+
+int v2v_conv_stem_pack_weights_hip(const float *weight, int64_t Cin, void *packed, void *stream)
+{
+    if (!weight || !packed) return fail(V2V_ERR_NULL, "v2v_conv_stem_pack_weights_hip: weight/packed is NULL");
+    if (Cin < 1 || Cin > 8) return fail(V2V_ERR_SHAPE, "need 1 <= Cin <= 8 (64 output channels, 3x3)");
+    if (!aligned(weight, 4) || !aligned(packed, 16)) return fail(V2V_ERR_ALIGN, "weight needs 4-byte, packed 16-byte alignment");
+    const hipError_t e = v2v::launch_conv_stem_pack(weight, static_cast<uint16_t *>(packed), (int)Cin, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv_stem_pack_kernel launch");
+}
+
+int v2v_conv_stem_nhwc_hip(const void *x8, const void *packed, const float *bias, int relu, int64_t B, int64_t H, int64_t W, void *out, void *stream)
+{
+    if (!x8 || !packed || !bias || !out) return fail(V2V_ERR_NULL, "v2v_conv_stem_nhwc_hip: x8/packed/bias/out is NULL");
+    if (B < 1 || H < 16 || W < 16 || H % 16 != 0 || W % 16 != 0 || B * H * W * 16 > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need B >= 1, H and W multiples of 16, output below 2^31 elements");
+    if (!aligned(x8, 16) || !aligned(packed, 16) || !aligned(out, 2) || !aligned(bias, 4)) return fail(V2V_ERR_ALIGN, "x8/packed need 16-byte alignment");
+    if (out == x8) return fail(V2V_ERR_PARAM, "out must not alias x8");
+    const hipError_t e = v2v::launch_conv_stem(static_cast<const uint16_t *>(x8), static_cast<const uint16_t *>(packed), bias, static_cast<uint16_t *>(out),
+                                               (int)B, (int)H, (int)W, relu ? 1 : 0, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv_stem_kernel launch");
+}
+
+int v2v_upsample2x_cat_nhwc_hip(const void *x, int64_t C1, const void *skip, int64_t C2, int64_t B, int64_t H, int64_t W, void *out, void *stream)
+{
+    if (!x || !out || (C2 > 0 && !skip)) return fail(V2V_ERR_NULL, "v2v_upsample2x_cat_nhwc_hip: x/out (or skip with C2 > 0) is NULL");
+    if (B < 1 || H < 1 || W < 1 || C1 < 8 || C1 % 8 != 0 || C2 < 0 || C2 % 8 != 0 || B * 4 * H * W * (C1 + C2) > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C1 %% 8 == 0, C2 %% 8 == 0 and an output below 2^31 elements");
+    if (skip && C2 == 0) return fail(V2V_ERR_PARAM, "skip given with C2 == 0");
+    if (!aligned(x, 16) || !aligned(out, 16) || !aligned(skip, 16)) return fail(V2V_ERR_ALIGN, "x/skip/out need 16-byte alignment");
+    if (out == x || out == skip) return fail(V2V_ERR_PARAM, "out must not alias x or skip");
+    const hipError_t e = v2v::launch_upsample2x_cat_nhwc(static_cast<const uint16_t *>(x), (int)C1, static_cast<const uint16_t *>(skip), (int)C2,
+                                                         static_cast<uint16_t *>(out), (int)B, (int)H, (int)W, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "upsample2x_cat_nhwc_bf16_kernel launch");
+}
+
+int v2v_upsample2x_cat_bwd_nhwc_hip(const void *dout, int64_t B, int64_t H, int64_t W, int64_t Ctot, int64_t c0, int64_t C, void *dx, void *stream)
+{
+    if (!dout || !dx) return fail(V2V_ERR_NULL, "v2v_upsample2x_cat_bwd_nhwc_hip: dout/dx is NULL");
+    if (B < 1 || H < 1 || W < 1 || C < 8 || C % 8 != 0 || Ctot % 8 != 0 || c0 < 0 || c0 % 8 != 0 || c0 + C > Ctot || B * 4 * H * W * Ctot > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C, c0 and Ctot multiples of 8, c0 + C <= Ctot, tensors below 2^31 elements");
+    if (!aligned(dout, 16) || !aligned(dx, 16)) return fail(V2V_ERR_ALIGN, "dout/dx need 16-byte alignment");
+    if (dx == dout) return fail(V2V_ERR_PARAM, "dx must not alias dout");
+    const hipError_t e = v2v::launch_upsample2x_cat_bwd(static_cast<const uint16_t *>(dout), static_cast<uint16_t *>(dx), (int)B, (int)H, (int)W, (int)Ctot,
+                                                        (int)c0, (int)C, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "upsample2x_cat_bwd_kernel launch");
+}
+
+int64_t v2v_conv1x1_bwd_cout_workspace_bytes(int64_t M, int64_t C, int64_t Cout)
+{
+    if (M < 1 || C < 8 || C > 128 || (C & (C - 1)) != 0 || Cout < 1 || Cout > 3) return -1;
+    return v2v::conv1x1_bwd_slabs(M) * Cout * (C + 1) * 4;
+}
+
+int v2v_conv1x1_bwd_cout_nhwc_hip(const float *dy, const void *x, const void *skip, const float *weight, int64_t M, int64_t C, int64_t Cout, void *dx,
+                                  float *dw, float *db, void *workspace, void *stream)
+{
+    if (!dy || !x || !weight || !dx || !dw || !db || !workspace) return fail(V2V_ERR_NULL, "v2v_conv1x1_bwd_cout_nhwc_hip: a required pointer is NULL");
+    if (M < 1 || C < 8 || C > 128 || (C & (C - 1)) != 0 || Cout < 1 || Cout > 3 || M * C > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need M >= 1, C a power of two in 8..128, Cout 1..3");
+    if (!aligned(dy, 4) || !aligned(x, 16) || !aligned(skip, 16) || !aligned(dx, 16) || !aligned(weight, 4) || !aligned(workspace, 4) || !aligned(dw, 4)
+        || !aligned(db, 4))
+        return fail(V2V_ERR_ALIGN, "x/skip/dx need 16-byte alignment, dy/weight/dw/db/workspace 4-byte");
+    const hipError_t e = v2v::launch_conv1x1_bwd_cout(dy, static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(skip), weight,
+                                                      static_cast<uint16_t *>(dx), dw, db, static_cast<float *>(workspace), M, (int)C, (int)Cout,
+                                                      static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv1x1_bwd_cout_kernel launch");
+}
+
+int v2v_conv_nhwc_like_hip(const void *x, const void *packed, const float *bias, const void *residual, int relu, int64_t B, int64_t Hin, int64_t Win,
+                           int64_t Cin, int64_t Cout, int ks, int stride, void *out, int64_t B_like, void *stream)
+{
+    if (!x || !packed || !bias || !out) return fail(V2V_ERR_NULL, "v2v_conv_nhwc_like_hip: x/packed/bias/out is NULL");
+    if ((ks != 3 && ks != 5) || (stride != 1 && stride != 2) || B_like < 0) return fail(V2V_ERR_PARAM, "ks must be 3 or 5, stride 1 or 2, B_like >= 0");
+    if (B < 1 || Hin < 1 || Win < 1 || v2v_conv_packed_elems(Cin, Cout, ks) < 0)
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, Cin %% 64 == 0 (or Cin 32 with Cout 64 / 128), Cout in {32, 64, 128} or a multiple of 256");
+    const int64_t H = (Hin - 1) / stride + 1, W = (Win - 1) / stride + 1;
+    if ((H * W) % 4 != 0 || B * Hin * Win * Cin > 0x7FFFFFFFLL || B * H * W * Cout > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "conv kernel needs (Hout*Wout) %% 4 == 0 and tensors below 2^31 elements");
+    if (out == x) return fail(V2V_ERR_PARAM, "out must not alias x (neighbouring tiles read it)");
+    if (!aligned(x, 16) || !aligned(packed, 16) || !aligned(out, 2) || !aligned(residual, 2) || !aligned(bias, 4))
+        return fail(V2V_ERR_ALIGN, "x/packed need 16-byte alignment");
+    v2v::ConvLstmArgs a{};
+    a.x = static_cast<const uint16_t *>(x); a.wp = static_cast<const uint16_t *>(packed); a.bias = bias;
+    a.residual = static_cast<const uint16_t *>(residual); a.out_nhwc = static_cast<uint16_t *>(out);
+    a.n_cols = (int)Cout; a.relu = relu ? 1 : 0; a.ks = ks; a.stride = stride; a.Hin = (int)Hin; a.Win = (int)Win;
+    a.B = (int)B; a.H = (int)H; a.W = (int)W; a.C = (int)Cin;
+    const hipError_t e = v2v::launch_conv_nhwc(a, 0, static_cast<hipStream_t>(stream), B_like);
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv (convlstm_step_kernel, EPI = 1) launch");
+}
+
 }  // extern "C"

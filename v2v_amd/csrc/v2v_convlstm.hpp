@@ -884,4 +884,135 @@ __global__ void __launch_bounds__(256) conv_pack_kernel(const float *w, uint16_t
     wp[i] = f32_to_bf16_rne(w[((int64_t)(ct * bn + col) * Cin + cc * kClBK + k) * taps + tap]);
 }
 
+// ---- the stem of the plain UNet (EVFlowNet): few input channels (the voxel bins, <= 8) -> 64 channels, 3x3, STRIDE 2 (UNet.encoders[0],
+// model/unet.py:320-326: there is no head, the first encoder reads the events) ---------------------------------------------------------
+// Built like conv_head_kernel: input NHWC padded to 8 channels, K packed tap-major (9 taps -> 2 chunks of 64, 7 zero slots that read the
+// zero slot of the patch), one 16-byte LDS read per lane and k-step, patch + all weights staged once, one barrier.  What differs: the
+// workgroup owns an 8 x 8 OUTPUT tile (H, W multiples of 16 make the output a multiple of 8) and stages its INPUT footprint, 17 x 17
+// pixels from (16 ty - 1, 16 tx - 1); output pixel (py, px) reads patch pixel (2 py + dy, 2 px + dx) for tap (dy, dx); the four waves
+// are the 2 x 2 (32-pixel fragment, 32-column fragment) pairs of the 64 pixels x 64 columns.  Bias (+ ReLU) -> bf16 NHWC [B,H/2,W/2,64].
+// HBM-bound on the output write: per output pixel 128 bytes written against 64 read (4 input pixels of 16 bytes).
+constexpr int kStemT = 8, kStemPW = 2 * kStemT + 1, kStemNP = kStemPW * kStemPW;
+constexpr int kStemPatchBytes = (kStemNP * 16 + 16 + 127) & ~127;
+constexpr int kStemLdsBytes = kStemPatchBytes + 2 * 64 * 128;
+
+__global__ void __launch_bounds__(256) conv_stem_kernel(const uint16_t *x8, const uint16_t *wp, const float *bias, uint16_t *out, int B, int H, int W, int relu)
+{
+    extern __shared__ __attribute__((aligned(128))) unsigned char cl_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, mf = wave >> 1, nf = wave & 1;
+    unsigned char *const patch = cl_lds;                              // kStemNP pixels x 16 B, then one zero slot
+    unsigned char *const wl = cl_lds + kStemPatchBytes;               // 2 chunks x 64 columns x 128 B, slot-swizzled rows
+    const int Ho = H >> 1, Wo = W >> 1, tiles_x = Wo / kStemT, tiles_y = Ho / kStemT;
+    const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, bimg = blockIdx.x / (tiles_x * tiles_y);
+    for (int i = threadIdx.x; i <= kStemNP; i += 256) {               // input footprint (+ the zero slot at index kStemNP)
+        const int hy = i / kStemPW, hx = i - hy * kStemPW;
+        const int iy = ty * 2 * kStemT + hy - 1, ix = tx * 2 * kStemT + hx - 1;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (i < kStemNP && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
+            v = *reinterpret_cast<const uint4 *>(x8 + (((int64_t)bimg * H + iy) * W + ix) * 8);
+        *reinterpret_cast<uint4 *>(patch + i * 16) = v;
+    }
+    for (int i = threadIdx.x; i < 2 * 64 * 8; i += 256) {             // weights: row = chunk * 64 + column, 16-byte slots, XOR swizzle on the slot
+        const int row = i >> 3, slot = i & 7, col = row & 63;
+        *reinterpret_cast<uint4 *>(wl + row * 128 + ((slot ^ ((col >> 1) & 7)) << 4)) = *reinterpret_cast<const uint4 *>(wp + (int64_t)row * 64 + slot * 8);
+    }
+    __syncthreads();
+    const int fr = lane & 31, fh = lane >> 5;
+    const int hr_base = 2 * (mf * 4 + (fr >> 3)) * kStemPW + 2 * (fr & 7);   // patch pixel of this lane's output pixel for tap (0, 0)
+    const int col = nf * 32 + fr;
+    const uint32_t b_sw = (uint32_t)((col >> 1) & 7);
+    cl_f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+#pragma unroll
+    for (int ck = 0; ck < 2; ++ck) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int tap = ck * 8 + 2 * s + fh;                      // this lane's tap in k-step s
+            const int dy = tap / 3, dx = tap - dy * 3;
+            const cl_bf16x8 bf = *reinterpret_cast<const cl_bf16x8 *>(wl + (ck * 64 + col) * 128 + (((uint32_t)(2 * s + fh) ^ b_sw) << 4));
+            const int hr = tap < 9 ? hr_base + dy * kStemPW + dx : kStemNP;
+            const cl_bf16x8 af = *reinterpret_cast<const cl_bf16x8 *>(patch + hr * 16);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf, acc, 0, 0, 0);
+        }
+    }
+    const float bv = bias[col];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * fh;              // pixel of the fragment: tile row mf * 4 + (row >> 3), column row & 7
+        const int py = mf * 4 + (row >> 3), px = row & 7;
+        float v = acc[r] + bv;
+        if (relu) v = v > 0.0f ? v : (v != v ? v : 0.0f);
+        out[((((int64_t)bimg * Ho + ty * kStemT + py) * Wo) + tx * kStemT + px) * 64 + col] = f32_to_bf16_rne(v);
+    }
+}
+
+// nn.Conv2d weight fp32 [64, Cin <= 8, 3, 3] -> [2 chunks][64 columns][64 k], k = 8 slot + c <-> tap 8 chunk + slot, channel c (zero beyond)
+__global__ void __launch_bounds__(256) conv_stem_pack_kernel(const float *w, uint16_t *wp, int Cin)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 2 * 64 * 64) return;
+    const int k = i & 63, col = (i >> 6) & 63, ck = i >> 12;
+    const int tap = ck * 8 + (k >> 3), c = k & 7;
+    wp[i] = (tap < 9 && c < Cin) ? f32_to_bf16_rne(w[((int64_t)col * Cin + c) * 9 + tap]) : (uint16_t)0;
+}
+
+// ---- the concat skip in front of a decoder: out[B,2H,2W,C1+C2] = cat(up2(x), up2(skip)) along the channels, which IS
+// f.interpolate(cat(x, skip), scale_factor=2, mode='bilinear', align_corners=False) (skip_concat, model/model_util.py:10, at
+// model/unet.py:350): bilinear interpolation works per channel, so each source is interpolated straight into its channel slice and no
+// low-resolution cat tensor exists.  upsample2x_nhwc_bf16_kernel's work-item (same expressions in the same order: horizontal 0.25 / 0.75,
+// then vertical, fp32, one bf16 rounding; `rs` input rows walked, each loaded once) over the (C1 + C2) / 8 channel groups of the OUTPUT:
+// group c8 reads x (pixel pitch C1) when 8 c8 < C1, else skip (pitch C2) at channel 8 c8 - C1, and writes at pixel pitch C1 + C2.
+__global__ void __launch_bounds__(256) upsample2x_cat_nhwc_bf16_kernel(const uint16_t *x, int C1, const uint16_t *skip, int C2, uint16_t *out, int B, int H, int W, int rs)
+{
+    const int C = C1 + C2;
+    const uint32_t c8n = (uint32_t)C >> 3, segs = (uint32_t)(H + rs - 1) / (uint32_t)rs;
+    const uint32_t n = (uint32_t)B * segs * (uint32_t)W * c8n;   // < 2^31: checked by the launcher (32-bit divisions below)
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    uint32_t r = i / c8n;
+    const int c8 = (int)(i - r * c8n);
+    const uint32_t r2 = r / (uint32_t)W;
+    const int ix = (int)(r - r2 * (uint32_t)W);
+    const int b = (int)(r2 / segs), seg = (int)(r2 - (uint32_t)b * segs);
+    const bool first = c8 * 8 < C1;
+    const uint16_t *const src = first ? x + c8 * 8 : skip + (c8 * 8 - C1);
+    const int cs = first ? C1 : C2;                               // the source's pixel pitch
+    const int xs[3] = {ix > 0 ? ix - 1 : 0, ix, ix < W - 1 ? ix + 1 : ix};
+    float L[3][8], R[3][8];                                       // rows iy - 1, iy, iy + 1: the left (2 ix) and right (2 ix + 1) output column
+    auto hrow = [&](int y, float (&l)[8], float (&rr)[8]) __attribute__((always_inline)) {
+        float v[3][8];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cl_unpack8(*reinterpret_cast<const uint4 *>(src + (((int64_t)b * H + y) * W + xs[k]) * cs), v[k]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float mid = 0.75f * v[1][e];
+            l[e] = 0.25f * v[0][e] + mid;
+            rr[e] = mid + 0.25f * v[2][e];
+        }
+    };
+    auto put = [&](int oy, int ox, const float (&top)[8], float wt, const float (&bot)[8], float wb) __attribute__((always_inline)) {
+        uint32_t w[4];
+#pragma unroll
+        for (int e = 0; e < 8; e += 2) w[e >> 1] = cl_pack_bf16(wt * top[e] + wb * bot[e], wt * top[e + 1] + wb * bot[e + 1]);
+        *reinterpret_cast<uint4 *>(out + ((((int64_t)b * 2 * H + oy) * 2 * W + ox) * C + c8 * 8)) = make_uint4(w[0], w[1], w[2], w[3]);
+    };
+    const int y0 = seg * rs, y1 = min(y0 + rs, H);
+    hrow(y0 > 0 ? y0 - 1 : 0, L[0], R[0]);
+    hrow(y0, L[1], R[1]);
+    for (int iy = y0; iy < y1; ++iy) {
+        if (iy < H - 1) hrow(iy + 1, L[2], R[2]);
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { L[2][e] = L[1][e]; R[2][e] = R[1][e]; }
+        }
+        put(2 * iy, 2 * ix, L[0], 0.25f, L[1], 0.75f);
+        put(2 * iy, 2 * ix + 1, R[0], 0.25f, R[1], 0.75f);
+        put(2 * iy + 1, 2 * ix, L[1], 0.75f, L[2], 0.25f);
+        put(2 * iy + 1, 2 * ix + 1, R[1], 0.75f, R[2], 0.25f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { L[0][e] = L[1][e]; R[0][e] = R[1][e]; L[1][e] = L[2][e]; R[1][e] = R[2][e]; }
+    }
+}
+
 }  // namespace v2v

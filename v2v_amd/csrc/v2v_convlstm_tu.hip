@@ -60,9 +60,11 @@ hipError_t launch_convlstm_step_bwd(const ConvLstmArgs &a, hipStream_t s) { retu
 // 128 / 64 / 32 a 256-pixel tile of 4 waves with 4 / 2 / 1 column fragments per wave
 int conv_tile_cols(int Cout) { return Cout % 256 == 0 ? 256 : (Cout == 128 || Cout == 64 || Cout == 32) ? Cout : 0; }
 
-hipError_t launch_conv_nhwc(const ConvLstmArgs &a, int tile_rows, hipStream_t s)
+// like_b > 0: the automatic tile is chosen as for a batch of like_b images (a time-folded batch then runs the per-step launch's instance:
+// the same summation order per image, bit for bit)
+hipError_t launch_conv_nhwc(const ConvLstmArgs &a, int tile_rows, hipStream_t s, int64_t like_b)
 {
-    const int64_t m = (int64_t)a.B * a.H * a.W;
+    const int64_t m = (like_b > 0 ? like_b : (int64_t)a.B) * a.H * a.W;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     // halo tiles (conv_halo_kernel): the 16 x 16 patch with its halo staged once per 64-channel chunk.  One patch buffer + two
@@ -196,6 +198,30 @@ hipError_t launch_conv1x1_nhwc(const uint16_t *x, const uint16_t *skip, const fl
     case 3: hipLaunchKernelGGL(conv1x1_nhwc_kernel<3>, grid, block, 0, s, x, skip, w, bias, out, out_bf16, M, C); break;
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_conv_stem(const uint16_t *x8, const uint16_t *wp, const float *bias, uint16_t *out, int B, int H, int W, int relu, hipStream_t s)
+{
+    hipLaunchKernelGGL(conv_stem_kernel, dim3((unsigned)(B * (H / (2 * kStemT)) * (W / (2 * kStemT)))), dim3(256), kStemLdsBytes, s, x8, wp, bias, out, B, H, W, relu);
+    return hipGetLastError();
+}
+
+hipError_t launch_conv_stem_pack(const float *w, uint16_t *wp, int Cin, hipStream_t s)
+{
+    hipLaunchKernelGGL(conv_stem_pack_kernel, dim3(2 * 64 * 64 / 256), dim3(256), 0, s, w, wp, Cin);
+    return hipGetLastError();
+}
+
+hipError_t launch_upsample2x_cat_nhwc(const uint16_t *x, int C1, const uint16_t *skip, int C2, uint16_t *out, int B, int H, int W, hipStream_t s)
+{
+    // launch_upsample2x_nhwc's work split over the C1 + C2 output channels (same rs rule; the values do not depend on rs)
+    const int64_t cols = (int64_t)B * W * ((C1 + C2) / 8);
+    int rs = 4;
+    if (cols * ((H + rs - 1) / rs) < 2048 * 64) rs = 1;
+    const int64_t n = cols * ((H + rs - 1) / rs);
+    if (n >= (int64_t)1 << 31) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(upsample2x_cat_nhwc_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, C1, skip, C2, out, B, H, W, rs);
     return hipGetLastError();
 }
 

@@ -319,4 +319,144 @@ hipError_t launch_conv1x1_bwd(const float *dy, const uint16_t *x, const uint16_t
     return hipGetLastError();
 }
 
+// ---- adjoint of the concat-skip upsampling (upsample2x_cat_nhwc_bf16_kernel): one channel slice [c0, c0 + C) of dout [B,2H,2W,Ctot] ->
+// dx [B,H,W,C].  upsample2x_bwd_kernel's gather (same weights, same order of the fp32 sums, one bf16 rounding) reading at pixel pitch Ctot;
+// called once for the gradient of x (c0 = 0) and once for the skip's (c0 = C1).  c0 = 0, C = Ctot is upsample2x_bwd_kernel bit for bit.
+__global__ void __launch_bounds__(256) upsample2x_cat_bwd_kernel(const uint16_t *dout, uint16_t *dx, int B, int H, int W, int Ctot, int c0, int C)
+{
+    const int G = C / 8;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)B * H * W * G) return;
+    const int g = (int)(i % G);
+    const int64_t pix = i / G;
+    const int kx = (int)(pix % W), ky = (int)((pix / W) % H), b = (int)(pix / ((int64_t)W * H));
+    const int H2 = 2 * H, W2 = 2 * W;
+    float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (int jy = 2 * ky - 1; jy <= 2 * ky + 2; ++jy) {
+        if (jy < 0 || jy >= H2) continue;
+        const float wy = up_w(jy, ky, H);
+        float row[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        for (int jx = 2 * kx - 1; jx <= 2 * kx + 2; ++jx) {
+            if (jx < 0 || jx >= W2) continue;
+            const float wx = up_w(jx, kx, W);
+            const uint4 v = *reinterpret_cast<const uint4 *>(dout + (((int64_t)b * H2 + jy) * W2 + jx) * Ctot + c0 + g * 8);
+            const uint32_t *vv = reinterpret_cast<const uint32_t *>(&v);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                row[2 * j] += wx * tr_f32((uint16_t)(vv[j] & 0xFFFFu));
+                row[2 * j + 1] += wx * tr_f32((uint16_t)(vv[j] >> 16));
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] += wy * row[j];
+    }
+    uint4 o;
+    uint32_t *oo = reinterpret_cast<uint32_t *>(&o);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) oo[j] = (uint32_t)tr_bf16(acc[2 * j]) | ((uint32_t)tr_bf16(acc[2 * j + 1]) << 16);
+    *reinterpret_cast<uint4 *>(dx + pix * C + g * 8) = o;
+}
+
+hipError_t launch_upsample2x_cat_bwd(const uint16_t *dout, uint16_t *dx, int B, int H, int W, int Ctot, int c0, int C, hipStream_t s)
+{
+    const int64_t n = (int64_t)B * H * W * (C / 8);
+    hipLaunchKernelGGL(upsample2x_cat_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dout, dx, B, H, W, Ctot, c0, C);
+    return hipGetLastError();
+}
+
+// ---- the prediction layer's backward for COUT = 1..3 outputs (EVFlowNet's flow: 2) ----------------------------------------------------
+// dy fp32 [M][COUT]; dx[m][c] = bf16(sum_o dy[m][o] * bf16(w[o][c])) (o ascending); dW[o][c] = sum_m dy[m][o] * bf16(x + skip)[m][c],
+// db[o] = sum_m dy[m][o].  conv1x1_bwd_kernel's slabs and orders per output channel: ws[slab][o][C + 1], slabs added in slab order, no
+// float atomics.  COUT = 1 gives conv1x1_bwd_kernel's results bit for bit.
+template <int COUT>
+__global__ void __launch_bounds__(256) conv1x1_bwd_cout_kernel(const float *dy, const uint16_t *x, const uint16_t *skip, const float *w, uint16_t *dx,
+                                                               float *ws, int64_t M, int C)
+{
+    __shared__ float red[COUT][256 * 9];
+    const int G = C / 8, rows = 256 / G;
+    const int g = threadIdx.x % G, pr = threadIdx.x / G;
+    float wb[COUT][8], acc[COUT][8], accb[COUT];
+#pragma unroll
+    for (int o = 0; o < COUT; ++o) {
+        accb[o] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { wb[o][j] = tr_f32(tr_bf16(w[o * C + g * 8 + j])); acc[o][j] = 0.0f; }
+    }
+    const int64_t p0 = (int64_t)blockIdx.x * kC1x1Slab, p1 = p0 + kC1x1Slab < M ? p0 + kC1x1Slab : M;
+    for (int64_t p = p0 + pr; p < p1; p += rows) {
+        float d[COUT];
+#pragma unroll
+        for (int o = 0; o < COUT; ++o) d[o] = dy[p * COUT + o];
+        const uint4 xv = *reinterpret_cast<const uint4 *>(x + p * C + g * 8);
+        uint4 sv = make_uint4(0u, 0u, 0u, 0u);
+        if (skip) sv = *reinterpret_cast<const uint4 *>(skip + p * C + g * 8);
+        const uint32_t *xx = reinterpret_cast<const uint32_t *>(&xv), *ss = reinterpret_cast<const uint32_t *>(&sv);
+        uint4 ov;
+        uint32_t *oo = reinterpret_cast<uint32_t *>(&ov);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float xs0 = tr_f32((uint16_t)(xx[j] & 0xFFFFu)), xs1 = tr_f32((uint16_t)(xx[j] >> 16));
+            if (skip) {
+                xs0 = tr_f32(tr_bf16(xs0 + tr_f32((uint16_t)(ss[j] & 0xFFFFu))));
+                xs1 = tr_f32(tr_bf16(xs1 + tr_f32((uint16_t)(ss[j] >> 16))));
+            }
+            float g0 = d[0] * wb[0][2 * j], g1 = d[0] * wb[0][2 * j + 1];
+            acc[0][2 * j] += d[0] * xs0;
+            acc[0][2 * j + 1] += d[0] * xs1;
+#pragma unroll
+            for (int o = 1; o < COUT; ++o) {
+                g0 += d[o] * wb[o][2 * j];
+                g1 += d[o] * wb[o][2 * j + 1];
+                acc[o][2 * j] += d[o] * xs0;
+                acc[o][2 * j + 1] += d[o] * xs1;
+            }
+            oo[j] = (uint32_t)tr_bf16(g0) | ((uint32_t)tr_bf16(g1) << 16);
+        }
+        *reinterpret_cast<uint4 *>(dx + p * C + g * 8) = ov;
+#pragma unroll
+        for (int o = 0; o < COUT; ++o) accb[o] += d[o];
+    }
+#pragma unroll
+    for (int o = 0; o < COUT; ++o) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[o][threadIdx.x * 9 + j] = acc[o][j];
+        red[o][threadIdx.x * 9 + 8] = accb[o];
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < COUT * (C + 1); idx += 256) {   // (o, c < C): channel c of output o; (o, C): its bias (from the lanes of channel group 0)
+        const int o = idx / (C + 1), c = idx - o * (C + 1), cg = c < C ? c / 8 : 0, slot = c < C ? c % 8 : 8;
+        float s = 0.0f;
+        for (int r = 0; r < rows; ++r) s += red[o][(r * G + cg) * 9 + slot];
+        ws[((int64_t)blockIdx.x * COUT + o) * (C + 1) + c] = s;
+    }
+}
+
+__global__ void __launch_bounds__(256) conv1x1_bwd_cout_reduce_kernel(const float *ws, float *dw, float *db, int S, int C, int Cout)
+{
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= Cout * (C + 1)) return;
+    const int o = idx / (C + 1), c = idx - o * (C + 1);
+    float s = 0.0f;
+    for (int k = 0; k < S; ++k) s += ws[((int64_t)k * Cout + o) * (C + 1) + c];
+    if (c < C) dw[o * C + c] = s;
+    else db[o] = s;
+}
+
+hipError_t launch_conv1x1_bwd_cout(const float *dy, const uint16_t *x, const uint16_t *skip, const float *w, uint16_t *dx, float *dw, float *db, float *ws,
+                                   int64_t M, int C, int Cout, hipStream_t s)
+{
+    const int64_t S = conv1x1_bwd_slabs(M);
+    const dim3 grid((unsigned)S), block(256);
+    switch (Cout) {
+    case 1: hipLaunchKernelGGL(conv1x1_bwd_cout_kernel<1>, grid, block, 0, s, dy, x, skip, w, dx, ws, M, C); break;
+    case 2: hipLaunchKernelGGL(conv1x1_bwd_cout_kernel<2>, grid, block, 0, s, dy, x, skip, w, dx, ws, M, C); break;
+    case 3: hipLaunchKernelGGL(conv1x1_bwd_cout_kernel<3>, grid, block, 0, s, dy, x, skip, w, dx, ws, M, C); break;
+    default: return hipErrorInvalidValue;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(conv1x1_bwd_cout_reduce_kernel, dim3((unsigned)((Cout * (C + 1) + 255) / 256)), dim3(256), 0, s, ws, dw, db, (int)S, C, Cout);
+    return hipGetLastError();
+}
+
 }  // namespace v2v

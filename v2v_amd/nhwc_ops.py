@@ -5,14 +5,16 @@ v2v_amd/train.py builds the torch.autograd.Functions on these, v2v_amd/convlstm.
     convlstm_step / conv_nhwc / conv3x3_nhwc / upsample2x_nhwc     the forward operators
     conv1x1_nhwc                                           the 1x1 prediction layer on skip_sum(x, head)
     conv_head_nhwc / to_nhwc8_bf16 / pack_head_weights     the head (voxel bins -> 32 channels)
+    conv_stem_nhwc / pack_stem_weights / upsample2x_cat_nhwc       the plain UNet (EVFlowNet): stride-2 stem (voxel bins -> 64), concat-skip upsampling
     pack_gate_weights / pack_conv_weights / pack_dgrad_weights     one-off weight packing; packed_weights = the cache in front of them
     nchw_to_nhwc_bf16(x, relu=False)                      layout change in front of them (not needed for channels-last bf16 input)
-    relu_bwd_nhwc / conv_dgrad_nhwc / conv_wgrad_nhwc / upsample2x_bwd_nhwc / conv1x1_bwd_nhwc / convlstm_step_bwd     the backward operators
+    relu_bwd_nhwc / conv_dgrad_nhwc / conv_wgrad_nhwc / upsample2x_bwd_nhwc / upsample2x_cat_bwd_nhwc / conv1x1_bwd_nhwc / convlstm_step_bwd     the backward operators
 
 Activations are bf16 NHWC with fp32 accumulation; activation gradients bf16 NHWC, the cell-state gradient fp32, parameter gradients fp32.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import functools
 
@@ -142,6 +144,22 @@ def pack_conv_weights(weight: torch.Tensor) -> torch.Tensor:
     return packed
 
 
+_tile_like_batch = 0            # > 0 inside tile_like_batch(n): conv_nhwc's automatic tile is the one a batch of n images gets
+
+
+@contextlib.contextmanager
+def tile_like_batch(n: int):
+    """Inside, every conv_nhwc with the automatic tile runs the kernel instance a batch of `n` images would get (v2v_conv_nhwc_like_hip):
+    a batch that folds T time steps of n images then gives every image the bits of its per-step launch (the instances differ in how they
+    split K, so in their fp32 summation order)."""
+    global _tile_like_batch
+    prev, _tile_like_batch = _tile_like_batch, int(n)
+    try:
+        yield
+    finally:
+        _tile_like_batch = prev
+
+
 def conv_nhwc(x, packed, bias, ks: int, stride: int = 1, residual=None, relu=False, tile_rows: int = 0):
     """out = [relu](conv_ks(x, stride, pad ks//2) + bias [+ residual]) on NHWC bfloat16: x [B,Hin,Win,Cin] -> [B,Hout,Wout,Cout]."""
     _lib.require_gpu()
@@ -157,8 +175,12 @@ def conv_nhwc(x, packed, bias, ks: int, stride: int = 1, residual=None, relu=Fal
         raise ValueError("residual must be a contiguous bfloat16 tensor [B,Hout,Wout,Cout] on x's device")
     out = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_conv_nhwc_hip(_ptr(x), _ptr(packed), _ptr(bias.detach().contiguous()), _ptr(residual), int(bool(relu)),
-                                                b, hin, win, cin, cout, ks, stride, _ptr(out), tile_rows, _lib.stream_ptr()))
+        if tile_rows == 0 and _tile_like_batch > 0 and _tile_like_batch != b:
+            _lib.check(_lib.lib().v2v_conv_nhwc_like_hip(_ptr(x), _ptr(packed), _ptr(bias.detach().contiguous()), _ptr(residual), int(bool(relu)),
+                                                         b, hin, win, cin, cout, ks, stride, _ptr(out), _tile_like_batch, _lib.stream_ptr()))
+        else:
+            _lib.check(_lib.lib().v2v_conv_nhwc_hip(_ptr(x), _ptr(packed), _ptr(bias.detach().contiguous()), _ptr(residual), int(bool(relu)),
+                                                    b, hin, win, cin, cout, ks, stride, _ptr(out), tile_rows, _lib.stream_ptr()))
     return out
 
 
@@ -239,6 +261,52 @@ def conv_head_nhwc(x8, packed, bias, ks: int, relu=True):
     return out
 
 
+def pack_stem_weights(weight):
+    """nn.Conv2d(Cin <= 8, 64, 3, stride=2, padding=1).weight float32 -> the stem kernel's packed bfloat16 stream (taps along K)."""
+    _lib.require_gpu()
+    if not weight.is_cuda or weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[0] != 64 \
+            or weight.shape[1] > 8:
+        raise ValueError("weight must be a float32 CUDA tensor [64, Cin <= 8, 3, 3]")
+    packed = torch.empty((_lib.lib().v2v_conv_stem_packed_elems(),), dtype=torch.bfloat16, device=weight.device)
+    with torch.cuda.device(weight.device):
+        _lib.check(_lib.lib().v2v_conv_stem_pack_weights_hip(_ptr(weight.detach().contiguous()), weight.shape[1], _ptr(packed), _lib.stream_ptr()))
+    return packed
+
+
+def conv_stem_nhwc(x8, packed, bias, relu=True):
+    """out = [relu](conv3x3(x, stride 2, pad 1) + bias): x8 [B,H,W,8] bfloat16 (to_nhwc8_bf16) -> [B,H/2,W/2,64] bfloat16; the plain UNet's
+    first encoder ConvLayer(num_bins, 64, 3, stride 2, padding 1) (model/unet.py:320-326).  H and W multiples of 16."""
+    _lib.require_gpu()
+    if not x8.is_cuda or x8.dtype != torch.bfloat16 or x8.dim() != 4 or x8.shape[3] != 8 or not x8.is_contiguous():
+        raise ValueError("x8 must be a contiguous bfloat16 CUDA tensor [B,H,W,8]")
+    if bias.numel() != 64 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_conv_stem_packed_elems():
+        raise ValueError("bias must be [64] and packed the output of pack_stem_weights")
+    b, h, w, _ = x8.shape
+    out = torch.empty((b, h // 2, w // 2, 64), dtype=torch.bfloat16, device=x8.device)
+    with torch.cuda.device(x8.device):
+        _lib.check(_lib.lib().v2v_conv_stem_nhwc_hip(_ptr(x8), _ptr(packed), _ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w,
+                                                     _ptr(out), _lib.stream_ptr()))
+    return out
+
+
+def upsample2x_cat_nhwc(x, skip=None):
+    """out = cat(bilinear_x2(x), bilinear_x2(skip)) along the channels on NHWC bfloat16 ([B,H,W,C1], [B,H,W,C2] -> [B,2H,2W,C1+C2]):
+    f.interpolate(skip_concat(x, skip), scale_factor=2, mode='bilinear', align_corners=False) (model/model_util.py:10, model/unet.py:350,
+    model/submodules.py:86-87) without the low-resolution cat tensor."""
+    _lib.require_gpu()
+    for name, v in (("x", x), ("skip", skip)):
+        if v is not None and (not v.is_cuda or v.dtype != torch.bfloat16 or v.dim() != 4 or not v.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous bfloat16 CUDA tensor [B,H,W,C]")
+    if skip is not None and (skip.shape[:3] != x.shape[:3] or skip.device != x.device):
+        raise ValueError("skip must have x's batch and spatial size and device")
+    b, h, w, c1 = x.shape
+    c2 = 0 if skip is None else skip.shape[3]
+    out = torch.empty((b, 2 * h, 2 * w, c1 + c2), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_upsample2x_cat_nhwc_hip(_ptr(x), c1, _ptr(skip), c2, b, h, w, _ptr(out), _lib.stream_ptr()))
+    return out
+
+
 # ---- backward: the data gradient of a convolution is the stride-1 convolution of the output gradient (spread onto the input grid for
 # stride 2) with the flipped, transposed weights on the forward convolution kernel; the weight / bias gradient is an MFMA GEMM over the
 # pixels (slabs + a fixed-order sum); the ConvLSTM step recomputes its gate GEMM and runs the cell backward on the accumulators -------------
@@ -312,6 +380,33 @@ def upsample2x_bwd_nhwc(dout):
     with torch.cuda.device(dout.device):
         _lib.check(_lib.lib().v2v_upsample2x_bwd_nhwc_hip(_ptr(dout), b, h2 // 2, w2 // 2, c, _ptr(dx), _lib.stream_ptr()))
     return dx
+
+
+def upsample2x_cat_bwd_nhwc(dout, c0: int, c: int):
+    """Adjoint of upsample2x_cat_nhwc for the channel slice [c0, c0 + c): [B,2H,2W,Ctot] -> [B,H,W,c] bf16."""
+    dout = _nhwc_bf16(dout)
+    b, h2, w2, ctot = dout.shape
+    dx = torch.empty((b, h2 // 2, w2 // 2, c), dtype=torch.bfloat16, device=dout.device)
+    with torch.cuda.device(dout.device):
+        _lib.check(_lib.lib().v2v_upsample2x_cat_bwd_nhwc_hip(_ptr(dout), b, h2 // 2, w2 // 2, ctot, c0, c, _ptr(dx), _lib.stream_ptr()))
+    return dx
+
+
+def conv1x1_bwd_cout_nhwc(dy, x, skip, weight):
+    """Prediction layer with Cout = 1..3 outputs: dy [B,H,W,Cout] (read as float32) -> (dx [B,H,W,C] bf16, dW [Cout,C,1,1], db [Cout])."""
+    dy = dy.float().contiguous()
+    b, h, w, c = x.shape
+    m, cout = b * h * w, weight.shape[0]
+    if dy.numel() != m * cout:
+        raise ValueError("dy must be [B,H,W,Cout]")
+    ws = _workspace(_lib.lib().v2v_conv1x1_bwd_cout_workspace_bytes(m, c, cout), x.device)
+    dx = torch.empty_like(x)
+    dw = torch.empty((cout, c), dtype=torch.float32, device=x.device)
+    db = torch.empty((cout,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_conv1x1_bwd_cout_nhwc_hip(_ptr(dy), _ptr(x), _ptr(skip), _ptr(weight.detach().float().reshape(cout, c).contiguous()),
+                                                            m, c, cout, _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), _lib.stream_ptr()))
+    return dx, dw.reshape(weight.shape), db
 
 
 def conv1x1_bwd_nhwc(dy, x, skip, weight):

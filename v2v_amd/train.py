@@ -14,8 +14,9 @@ from __future__ import annotations
 
 import torch
 
-from .nhwc_ops import (conv1x1_bwd_nhwc, conv1x1_nhwc, conv_dgrad_nhwc, conv_head_nhwc, conv_nhwc, conv_wgrad_nhwc, convlstm_step,
-                       convlstm_step_bwd, pack_dgrad_weights, packed_weights, relu_bwd_nhwc, upsample2x_bwd_nhwc, upsample2x_nhwc)
+from .nhwc_ops import (conv1x1_bwd_cout_nhwc, conv1x1_bwd_nhwc, conv1x1_nhwc, conv_dgrad_nhwc, conv_head_nhwc, conv_nhwc, conv_stem_nhwc,
+                       conv_wgrad_nhwc, convlstm_step, convlstm_step_bwd, pack_dgrad_weights, packed_weights, relu_bwd_nhwc,
+                       upsample2x_bwd_nhwc, upsample2x_cat_bwd_nhwc, upsample2x_cat_nhwc, upsample2x_nhwc)
 
 
 def dgrad_weights(layer, name: str) -> torch.Tensor:
@@ -81,6 +82,61 @@ class UpConvFn(torch.autograd.Function):
         return dsum, dsum if ctx.has_skip else None, dw, db, None
 
 
+class UpCatConvFn(torch.autograd.Function):
+    """[relu](conv_ks(up2(cat(x, skip))) + bias) (UpsampleConvLayer behind the plain UNet's concat skip, model/unet.py:350)."""
+
+    @staticmethod
+    def kernels(x, skip, layer):
+        """-> (out, u = the upsampled concat buffer the convolution read)."""
+        conv = layer.conv2d
+        u = upsample2x_cat_nhwc(x, skip)
+        return conv_nhwc(u, layer._weights(), conv.bias.detach().float(), conv.kernel_size[0], conv.stride[0], relu=layer.relu), u
+
+    @staticmethod
+    def forward(ctx, x, skip, weight, bias, layer):
+        out, u = UpCatConvFn.kernels(x, skip, layer)
+        ctx.layer, ctx.c1 = layer, x.shape[3]
+        ctx.save_for_backward(u, out, weight)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        u, out, _ = ctx.saved_tensors
+        layer, c1 = ctx.layer, ctx.c1
+        ks, stride = layer.conv2d.kernel_size[0], layer.conv2d.stride[0]
+        dz = relu_bwd_nhwc(dout, out if layer.relu else None)
+        dx = dskip = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            du = conv_dgrad_nhwc(dz, dgrad_weights(layer, "conv2d"), u.shape[3], ks, stride, u.shape[1], u.shape[2])
+            dx = upsample2x_cat_bwd_nhwc(du, 0, c1) if ctx.needs_input_grad[0] else None
+            dskip = upsample2x_cat_bwd_nhwc(du, c1, u.shape[3] - c1) if ctx.needs_input_grad[1] else None
+        dw, db = conv_wgrad_nhwc(dz, u, ks=ks, stride=stride)
+        return dx, dskip, dw, db, None
+
+
+class StemFn(torch.autograd.Function):
+    """The plain UNet's stem (voxel bins -> 64 channels, 3x3, stride 2): x8 = the input as bf16 NHWC padded to 8 channels; no input gradient."""
+
+    @staticmethod
+    def kernels(x8, layer):
+        return conv_stem_nhwc(x8, layer._weights(), layer.conv2d.bias, relu=layer.relu)
+
+    @staticmethod
+    def forward(ctx, x8, weight, bias, layer):
+        out = StemFn.kernels(x8, layer)
+        ctx.layer = layer
+        ctx.save_for_backward(x8, out, weight)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x8, out, weight = ctx.saved_tensors
+        layer = ctx.layer
+        dz = relu_bwd_nhwc(dout, out if layer.relu else None)
+        dw, db = conv_wgrad_nhwc(dz, x8, cin_out=weight.shape[1], ks=3, stride=2)
+        return None, dw, db, None
+
+
 class HeadFn(torch.autograd.Function):
     """The head (voxel bins -> 32 channels): x8 = the input as bf16 NHWC padded to 8 channels; no input gradient (the voxel grid is data)."""
 
@@ -106,7 +162,8 @@ class HeadFn(torch.autograd.Function):
 
 
 class PredFn(torch.autograd.Function):
-    """The 1x1 prediction layer pred(x + skip), one output channel: [B,H,W,C] bf16 (+ skip) -> [B,H,W,1] float32 holding the values of
+    """The 1x1 prediction layer pred(x + skip), 1..3 output channels (more than one: the backward kernel for Cout outputs): [B,H,W,C] bf16
+    (+ skip) -> [B,H,W,Cout] float32 holding the values of
     the kernel's output in out_dtype (bf16: widened exactly), so that the loss gradient reaches the backward kernel unrounded (an
     L1 gradient sign / N is not a bf16 value for N = 12 x 128^2: rounding it would scale every gradient of the network by ~1 + 2e-3)."""
 
@@ -124,7 +181,7 @@ class PredFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, skip, weight = ctx.saved_tensors
-        dx, dw, db = conv1x1_bwd_nhwc(dout, x, skip, weight)
+        dx, dw, db = (conv1x1_bwd_nhwc if weight.shape[0] == 1 else conv1x1_bwd_cout_nhwc)(dout, x, skip, weight)
         return dx, dx if ctx.has_skip else None, dw, db, None, None
 
 

@@ -13,6 +13,12 @@ Configuration covered = what config/train_v2v_e2vid_10k.yaml:21-30 instantiates:
 there is no stock-layer fallback inside this module).  Inference by default; trainable=True adds the backward kernels of
 v2v_amd/train.py (back-propagation through time through the ConvLSTM states when grad is enabled).
 
+    EVFlowNet(unet_kwargs)                 model/model.py:226-261          keys  unet.*
+    UNet(unet_kwargs)                      model/unet.py:313-352           keys  encoders.N.conv2d.*, resblocks.N.conv1.* / conv2.*,
+                                                                                 decoders.N.conv2d.*, pred.conv2d.*
+(the stateless flow network of config/train_v2v_evflow_10k.yaml / config/test_evflow_original.yaml: skip_type 'concat', kernel_size 3,
+norm none, use_upsample_conv true, base 32, 4 encoders, multiplier 2; anything else raises).
+
 Inside forward() everything runs in bfloat16 NHWC (torch.channels_last views of the kernels' own buffers): the head takes
 the float voxel grid in any layout, every later layer consumes and produces NHWC in place, the cell states stay float32, and
 the prediction comes back in the input's dtype.  Parity: golden G18 = the reference's modules run in float32 on seeded
@@ -24,6 +30,7 @@ import torch
 import torch.nn as nn
 
 from .convlstm import ConvLayer, ConvLSTM, ResidualBlock
+from .nhwc_ops import tile_like_batch
 
 
 class UpsampleConvLayer(ConvLayer):
@@ -303,3 +310,126 @@ class E2VIDRecurrent(nn.Module):
         g.replay()
         self.unetrecurrent.states = list(states)                # the graph's own state tensors: what the last captured step wrote
         return res
+
+
+class UNet(nn.Module):
+    """model/unet.py:313-352 (+ BaseUNet :13-64): the plain (stateless) UNet with concat skips, no head -- the first encoder reads the
+    events.  Same attribute names (`encoders`, `resblocks`, `decoders`, `pred`), so a reference state_dict loads with strict=True.
+    Covered: skip_type 'concat', kernel_size 3, norm none, use_upsample_conv true, base_num_channels 32, 4 encoders, channel_multiplier
+    2, <= 8 bins, 1..3 outputs (what EVFlowNet hard-codes); anything else raises.  trainable=True records every layer's backward."""
+
+    def __init__(self, unet_kwargs, trainable: bool = False):
+        super().__init__()
+        self.trainable = bool(trainable)
+        kw = dict(unet_kwargs)
+        self.base_num_channels = kw["base_num_channels"]
+        self.num_encoders = kw["num_encoders"]
+        self.num_residual_blocks = kw["num_residual_blocks"]
+        self.num_output_channels = kw["num_output_channels"]
+        self.kernel_size = kw.get("kernel_size", 5)
+        self.skip_type = kw["skip_type"]
+        self.norm = kw.get("norm", None)
+        self.num_bins = kw["num_bins"]
+        mult = kw.get("channel_multiplier", 2)
+        if self.norm in ("none", "None", ""):
+            self.norm = None
+        if self.skip_type != "concat" or not kw.get("use_upsample_conv", True) or self.norm is not None or self.kernel_size != 3 \
+                or self.base_num_channels != 32 or self.num_encoders != 4 or mult != 2 or not 1 <= self.num_bins <= 8 \
+                or not 1 <= self.num_output_channels <= 3:
+            raise ValueError("the device kernels cover the plain UNet as EVFlowNet builds it: skip_type 'concat', kernel_size 3, norm none, "
+                             "use_upsample_conv true, base_num_channels 32, num_encoders 4, channel_multiplier 2, num_bins <= 8, <= 3 outputs "
+                             "(model/model.py:234-245)")
+        self.encoder_input_sizes = [int(self.base_num_channels * pow(mult, i)) for i in range(self.num_encoders)]
+        self.encoder_output_sizes = [int(self.base_num_channels * pow(mult, i + 1)) for i in range(self.num_encoders)]
+        self.max_num_channels = self.encoder_output_sizes[-1]
+        k = self.kernel_size
+        self.encoders = nn.ModuleList(
+            ConvLayer(self.num_bins if n == 0 else i, o, kernel_size=k, stride=2, padding=k // 2, norm=self.norm, trainable=trainable)
+            for n, (i, o) in enumerate(zip(self.encoder_input_sizes, self.encoder_output_sizes)))   # encoders[0] = the stem (:322)
+        self.encoders[0].force_channels_last = True        # NHWC from the first layer on, whatever layout the voxel grid arrives in
+        self.resblocks = nn.ModuleList(ResidualBlock(self.max_num_channels, self.max_num_channels, norm=self.norm, trainable=trainable)
+                                       for _ in range(self.num_residual_blocks))
+        self.decoders = nn.ModuleList(UpsampleConvLayer(2 * i, o, kernel_size=k, padding=k // 2, norm=self.norm, trainable=trainable)
+                                      for i, o in zip(reversed(self.encoder_output_sizes), reversed(self.encoder_input_sizes)))
+        self.pred = ConvLayer(self.base_num_channels, self.num_output_channels, 1, activation=None, trainable=trainable)
+
+    def check_size(self, h: int, w: int):
+        """H and W multiples of 16 with whole groups of 4 pixels per image at the deepest level (the convolution kernels' rule; every
+        shallower level then has them too): raises before anything is launched."""
+        depth = 1 << self.num_encoders
+        if h % depth != 0 or w % depth != 0 or h < depth or w < depth:
+            raise ValueError(f"UNet needs H and W multiples of {depth} (got {h} x {w}): pad the events first")
+        hl, wl = h // depth, w // depth
+        if (hl * wl) % 4 != 0:
+            raise ValueError(f"UNet at {h} x {w}: level {self.num_encoders} is {hl} x {wl} = {hl * wl} pixels per image, and the convolution "
+                             "kernels need whole groups of 4 ((H/16) * (W/16) % 4 == 0)")
+
+    def forward(self, x, event_scales=None):
+        """x: [N, num_bins, H, W] float voxel grid (any layout) -> [N, num_output_channels, H, W] (contiguous, x's dtype; bfloat16 under
+        autocast; float32 under training: the values of the bfloat16 kernel output widened exactly).  event_scales as in UNetRecurrent."""
+        self.check_size(x.shape[-2], x.shape[-1])
+        out_dtype = torch.bfloat16 if (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()) else x.dtype
+        with torch.autocast("cuda", dtype=torch.bfloat16):      # the stem hands out bfloat16; every later layer keeps it
+            x = self.encoders[0](x, scales=event_scales)
+        blocks = [x]
+        for encoder in self.encoders[1:]:
+            x = encoder(x)
+            blocks.append(x)
+        for resblock in self.resblocks:
+            x = resblock(x)
+        for i, decoder in enumerate(self.decoders):
+            x = decoder(x, blocks[self.num_encoders - i - 1], skip_type="concat")   # skip_concat + upsampling in one kernel (:350)
+        flow = self.pred(x)                                     # no skip on the prediction (:352)
+        if self.trainable and torch.is_grad_enabled():
+            return flow.contiguous()                            # float32 (PredFn): the loss gradient reaches the backward kernel unrounded
+        return flow.to(out_dtype, memory_format=torch.contiguous_format)
+
+
+class EVFlowNet(nn.Module):
+    """model/model.py:226-261: `unet` = UNet with EVFlowNet's hard-coded kwargs applied over what the YAML gives; stateless."""
+
+    HARD_CODED = dict(base_num_channels=32, num_encoders=4, num_residual_blocks=2, num_output_channels=2, skip_type="concat", norm=None,
+                      use_upsample_conv=True, kernel_size=3, channel_multiplier=2)        # model/model.py:234-245
+
+    def __init__(self, unet_kwargs, trainable: bool = False):
+        super().__init__()
+        kw = dict(unet_kwargs)
+        kw.update(self.HARD_CODED)
+        self.num_bins = kw["num_bins"]
+        self.num_encoders = kw["num_encoders"]
+        self.trainable = bool(trainable)           # the YAML switch: model: {target: ..EVFlowNet, params: {unet_kwargs: .., trainable: true}}
+        self.unet = UNet(kw, trainable=trainable)
+
+    def reset_states(self):
+        pass
+
+    def forward(self, event_tensor, event_scales=None):
+        """[N, num_bins, H, W] -> {'flow': [N,2,H,W] (x, y) displacement, 'image': 0 * flow[..., 0:1, :, :]} (model/model.py:259-261)."""
+        flow = self.unet(event_tensor, event_scales)
+        return {"flow": flow, "image": 0 * flow[..., 0:1, :, :]}
+
+    def default_chunk(self, h: int, w: int) -> int:
+        """Images per launch of forward_sequence: the largest tensor of an image is the last decoder's upsampled concat buffer,
+        H x W x 4 * base_num_channels elements (128 per pixel), and the kernels index tensors below 2^31 elements -- 1023 images at 128 x 128."""
+        return max(1, 0x7FFFFFFF // (h * w * 4 * self.unet.base_num_channels))
+
+    def forward_sequence(self, events, event_scales=None, chunk=None):
+        """The reference's time loop (model/train_flow_utils.py:343-352) as one call: events [N,T,num_bins,H,W] -> flow [N,T,2,H,W].  The
+        network has no state, so the loop is the same network on N*T images: time is folded into the batch, `chunk` images per launch
+        (default: default_chunk, from the kernels' 2^31-element limit).  Every convolution runs the kernel instance the per-step batch of
+        N images gets (nhwc_ops.tile_like_batch), so the result equals the per-step loop bit for bit.  Inference only."""
+        if events.dim() != 5:
+            raise ValueError("events must be [N, T, num_bins, H, W]")
+        if self.trainable and torch.is_grad_enabled():
+            raise ValueError("forward_sequence is inference only: train with the per-step loop or forward() on a folded batch")
+        n, t_steps = events.shape[:2]
+        self.unet.check_size(events.shape[-2], events.shape[-1])
+        chunk = self.default_chunk(events.shape[-2], events.shape[-1]) if chunk is None else max(1, int(chunk))
+        ev = events.reshape((n * t_steps,) + tuple(events.shape[2:]))                  # n-major: image i = (i // T, i % T); a view when contiguous
+        sc = event_scales.repeat_interleave(t_steps, dim=0) if event_scales is not None else None
+        flows = []
+        with torch.no_grad(), tile_like_batch(n):
+            for i in range(0, n * t_steps, chunk):
+                flows.append(self.unet(ev[i:i + chunk], None if sc is None else sc[i:i + chunk]))
+        flow = flows[0] if len(flows) == 1 else torch.cat(flows)
+        return flow.reshape((n, t_steps) + tuple(flow.shape[1:]))

@@ -36,7 +36,7 @@ extern "C" {
  * 3: v2v_esim_extras grew two trailing fields (stored_frames, frames_elems: the bounds of the frame_index gather).  Every function
  *    signature and every result of ABI 2 is unchanged; a caller that fills v2v_esim_extras must be recompiled (or zero the struct at
  *    its new size): an ABI-2 struct is 16 bytes shorter. */
-#define V2V_ABI_VERSION 3
+#define V2V_ABI_VERSION 4
 
 typedef enum v2v_status {
     V2V_OK = 0,
@@ -495,6 +495,29 @@ int v2v_conv1x1_bwd_cout_nhwc_hip(const float *dy, const void *x, const void *sk
  * images runs the instance a single step would, so every image comes out bit-identical to the per-step launch. */
 int v2v_conv_nhwc_like_hip(const void *x, const void *packed, const float *bias, const void *residual, int relu, int64_t B, int64_t Hin, int64_t Win,
                            int64_t Cin, int64_t Cout, int ks, int stride, void *out, int64_t B_like, void *stream);
+
+/* ---- HyperE2VID's per-pixel dynamic decoder (model/hyper_model.py:33-60, model/hyper/hyper_dynamic.py), inference ------------------------
+ * Context staging (ConvolutionalContextFusion.forward up to its convolution): cat(events [B,C,H,W] float32 of any element strides, prev
+ * [B,1,H,W] float32 contiguous) bilinearly downsampled by 4 (align_corners = false: the mean of the central 2 x 2 of every 4 x 4 block)
+ * -> dst bf16 [B,H/4,W/4,8], channels C + 1 .. 7 zero: the input layout of v2v_conv_head_nhwc_hip.  1 <= C <= 7, H and W multiples of 4. */
+int v2v_hyper_context_hip(const float *events, int64_t stride_b, int64_t stride_c, int64_t stride_h, int64_t stride_w, const float *prev, int64_t B,
+                          int64_t C, int64_t H, int64_t W, void *dst, void *stream);
+/* context_fusion.conv on that layout: x8 bf16 [B,h,w,8] -> out bf16 [B,h,w,32] = conv3x3(x, pad 1) + bias; weight float32 [32,Cin,3,3] (rounded
+ * to bf16 while it is read), 1 <= Cin <= 8, any h, w >= 1 (the head entry above needs multiples of 16). */
+int v2v_hyper_context_conv_hip(const void *x8, const float *weight, const float *bias, int64_t B, int64_t h, int64_t w, int64_t Cin, void *out, void *stream);
+/* Element-wise tanh on n bf16 values (bases_net's first activation); n % 8 == 0, out may be x. */
+int v2v_tanh_bf16_hip(const void *x, int64_t n, void *out, void *stream);
+/* Atoms (DynamicAtomGeneration.forward's tanh + einsum): coeff bf16 [M,128] = the 72 pre-activation coefficients of a pixel (index
+ * m * 12 + k; columns 72..127 ignored), bases float32 [12,25] -> atoms float32 [M,25,6]: atoms[p][l][m] = sum_k tanh(coeff[p][m*12+k]) * bases[k][l]. */
+int v2v_hyper_atoms_hip(const void *coeff, const float *bases, int64_t M, float *atoms, void *stream);
+/* The dynamic convolution (DynamicConv.forward + bias [+ ReLU]) without the unfolded tensor: x bf16 [B,H,W,256], atoms float32 [B,H,W,25,6],
+ * out bf16 [B,H,W,128]: out[p][o] = [relu](bias[o] + sum_{c,m} W[o][c*6+m] * bf16(sum_l atoms[p][l][m] * x[p + offset_l][c])) over the
+ * zero-padded 5 x 5 window, float32 accumulation.  weight float32 [Cout, Cin * atoms] (compositional_coefficients) is packed once into
+ * v2v_hyper_dynconv_packed_elems bf16 elements.  Shapes taken: Cin 256, Cout 128, 6 atoms, ks 5; anything else: -1 / V2V_ERR_SHAPE. */
+int64_t v2v_hyper_dynconv_packed_elems(int64_t Cin, int64_t Cout, int atoms, int ks);
+int v2v_hyper_dynconv_pack_weights_hip(const float *weight, int64_t Cin, int64_t Cout, int atoms, void *packed, void *stream);
+int v2v_hyper_dynconv_nhwc_hip(const void *x, const float *atoms, const void *packed, const float *bias, int relu, int64_t B, int64_t H, int64_t W,
+                               int64_t Cin, int64_t Cout, int n_atoms, int ks, void *out, void *stream);
 
 #ifdef __cplusplus
 }

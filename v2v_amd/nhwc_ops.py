@@ -436,3 +436,100 @@ def convlstm_step_bwd(x, h_prev, c_prev, packed, bias, dh, dc):
         _lib.check(_lib.lib().v2v_convlstm_step_bwd_hip(_ptr(x), _ptr(h_prev), _ptr(c_prev), _ptr(packed), _ptr(bias), _ptr(dh), _ptr(dc), b, h, w, c,
                                                         _ptr(dgates), _ptr(dc_prev), _lib.stream_ptr()))
     return dgates, dc_prev
+
+
+# ---- HyperE2VID's dynamic decoder (v2v_amd/hyper.py; kernels in v2v_amd/csrc/v2v_hyper.hpp) ---------------------------------------------
+def hyper_context_nhwc8(events, prev):
+    """cat(events [B, C <= 7, H, W] float32 of any strides, prev [B,1,H,W] float32) bilinearly downsampled by 4 -> bfloat16 [B,H/4,W/4,8],
+    channels zero-padded to 8: f.interpolate(cat, scale_factor=0.25, mode='bilinear', align_corners=False) of
+    ConvolutionalContextFusion.forward (model/hyper/hyper_dynamic.py:19-21) in the head kernels' 8-channel input layout (context_conv_nhwc reads it)."""
+    _lib.require_gpu()
+    if not events.is_cuda or events.dtype != torch.float32 or events.dim() != 4 or events.shape[1] > 7:
+        raise ValueError("events must be a float32 CUDA tensor [B, C <= 7, H, W]")
+    b, c, h, w = events.shape
+    if prev.dtype != torch.float32 or tuple(prev.shape) != (b, 1, h, w) or not prev.is_contiguous() or prev.device != events.device:
+        raise ValueError(f"prev must be a contiguous float32 [{b},1,{h},{w}] tensor on events' device")
+    if h % 4 != 0 or w % 4 != 0:
+        raise ValueError("H and W must be multiples of 4")
+    out = torch.empty((b, h // 4, w // 4, 8), dtype=torch.bfloat16, device=events.device)
+    with torch.cuda.device(events.device):
+        _lib.check(_lib.lib().v2v_hyper_context_hip(_ptr(events), *events.stride(), _ptr(prev), b, c, h, w, _ptr(out), _lib.stream_ptr()))
+    return out
+
+
+def context_conv_nhwc(x8, weight, bias):
+    """out = conv3x3(x8, pad 1) + bias: x8 [B,h,w,8] bfloat16 (hyper_context_nhwc8) -> [B,h,w,32] bfloat16, any h and w;
+    ConvolutionalContextFusion.conv (model/hyper/hyper_dynamic.py:22).  weight float32 [32, Cin <= 8, 3, 3], read as it is (no packing)."""
+    _lib.require_gpu()
+    if not x8.is_cuda or x8.dtype != torch.bfloat16 or x8.dim() != 4 or x8.shape[3] != 8 or not x8.is_contiguous():
+        raise ValueError("x8 must be a contiguous bfloat16 CUDA tensor [B,h,w,8]")
+    if weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[0] != 32 or weight.shape[1] > 8 or tuple(weight.shape[2:]) != (3, 3) \
+            or bias.numel() != 32 or weight.device != x8.device:
+        raise ValueError("weight must be float32 [32, Cin <= 8, 3, 3] on x8's device, bias [32]")
+    b, h, w, _ = x8.shape
+    out = torch.empty((b, h, w, 32), dtype=torch.bfloat16, device=x8.device)
+    with torch.cuda.device(x8.device):
+        _lib.check(_lib.lib().v2v_hyper_context_conv_hip(_ptr(x8), _ptr(weight.detach().contiguous()), _ptr(bias.detach().float().contiguous()), b, h, w,
+                                                         weight.shape[1], _ptr(out), _lib.stream_ptr()))
+    return out
+
+
+def tanh_bf16_(x):
+    """In-place tanh of a contiguous bfloat16 CUDA tensor (numel % 8 == 0): the activation the convolution kernel's epilogue does not have."""
+    _lib.require_gpu()
+    if not x.is_cuda or x.dtype != torch.bfloat16 or not x.is_contiguous() or x.numel() % 8 != 0:
+        raise ValueError("x must be a contiguous bfloat16 CUDA tensor with a multiple of 8 elements")
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_tanh_bf16_hip(_ptr(x), x.numel(), _ptr(x), _lib.stream_ptr()))
+    return x
+
+
+def hyper_atoms(coeff, bases):
+    """coeff bfloat16 [B,h,w,128] (the 72 PRE-activation basis coefficients of bases_net's last convolution + BatchNorm, index m * 12 + k,
+    zero-padded to the convolution kernel's 128 columns), bases float32 [12,25] -> atoms float32 [B,h,w,25,6]:
+    atoms[..., l, m] = sum_k tanh(coeff[..., m * 12 + k]) * bases[k, l] (DynamicAtomGeneration.forward, model/hyper/hyper_dynamic.py:54-56)."""
+    _lib.require_gpu()
+    if not coeff.is_cuda or coeff.dtype != torch.bfloat16 or coeff.dim() != 4 or coeff.shape[3] != 128 or not coeff.is_contiguous():
+        raise ValueError("coeff must be a contiguous bfloat16 CUDA tensor [B,h,w,128]")
+    if bases.dtype != torch.float32 or tuple(bases.shape) != (12, 25) or not bases.is_contiguous() or bases.device != coeff.device:
+        raise ValueError("bases must be a contiguous float32 [12,25] tensor on coeff's device")
+    b, h, w, _ = coeff.shape
+    atoms = torch.empty((b, h, w, 25, 6), dtype=torch.float32, device=coeff.device)
+    with torch.cuda.device(coeff.device):
+        _lib.check(_lib.lib().v2v_hyper_atoms_hip(_ptr(coeff), _ptr(bases), b * h * w, _ptr(atoms), _lib.stream_ptr()))
+    return atoms
+
+
+def pack_dynconv_weights(weight):
+    """DynamicConv.compositional_coefficients float32 [128, 256 * 6, 1, 1] -> the dynamic-convolution kernel's packed bfloat16 stream
+    (atom-major K: every 64-wide chunk is one atom over 64 channels)."""
+    _lib.require_gpu()
+    if not weight.is_cuda or weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[2:]) != (1, 1):
+        raise ValueError("weight must be a float32 CUDA tensor [Cout, Cin * atoms, 1, 1]")
+    cout, k = weight.shape[0], weight.shape[1]
+    n = _lib.lib().v2v_hyper_dynconv_packed_elems(k // 6, cout, 6, 5) if k % 6 == 0 else -1
+    if n < 0:
+        raise ValueError(f"the dynamic convolution takes 256 -> 128 channels with 6 atoms (got weight {tuple(weight.shape)})")
+    packed = torch.empty((n,), dtype=torch.bfloat16, device=weight.device)
+    with torch.cuda.device(weight.device):
+        _lib.check(_lib.lib().v2v_hyper_dynconv_pack_weights_hip(_ptr(weight.detach().contiguous()), k // 6, cout, 6, _ptr(packed), _lib.stream_ptr()))
+    return packed
+
+
+def dynconv_nhwc(x, atoms, packed, bias, relu=True):
+    """out = [relu](DynamicConv(x, atoms) + bias) on NHWC bfloat16: x [B,H,W,256], atoms float32 [B,H,W,25,6] (hyper_atoms) -> [B,H,W,128];
+    neither the unfolded input nor the intermediate features of model/hyper/hyper_dynamic.py:87-91 are written anywhere."""
+    _lib.require_gpu()
+    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("x must be a contiguous bfloat16 CUDA tensor [B,H,W,Cin]")
+    b, h, w, cin = x.shape
+    cout = bias.numel()
+    if atoms.dtype != torch.float32 or tuple(atoms.shape) != (b, h, w, 25, 6) or not atoms.is_contiguous() or atoms.device != x.device:
+        raise ValueError(f"atoms must be a contiguous float32 [{b},{h},{w},25,6] tensor on x's device")
+    if bias.dtype != torch.float32 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_hyper_dynconv_packed_elems(cin, cout, 6, 5):
+        raise ValueError("bias must be float32 [128] and packed the output of pack_dynconv_weights (256 -> 128 channels, 6 atoms)")
+    out = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_hyper_dynconv_nhwc_hip(_ptr(x), _ptr(atoms), _ptr(packed), _ptr(bias.detach().contiguous()), int(bool(relu)), b, h, w,
+                                                         cin, cout, 6, 5, _ptr(out), _lib.stream_ptr()))
+    return out

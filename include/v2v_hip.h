@@ -36,7 +36,7 @@ extern "C" {
  * 3: v2v_esim_extras grew two trailing fields (stored_frames, frames_elems: the bounds of the frame_index gather).  Every function
  *    signature and every result of ABI 2 is unchanged; a caller that fills v2v_esim_extras must be recompiled (or zero the struct at
  *    its new size): an ABI-2 struct is 16 bytes shorter. */
-#define V2V_ABI_VERSION 4
+#define V2V_ABI_VERSION 5
 
 typedef enum v2v_status {
     V2V_OK = 0,
@@ -303,6 +303,25 @@ int v2v_convlstm_pack_weights_hip(const float *gates_weight, int64_t C, void *pa
 int v2v_convlstm_step_hip(const void *x, const void *h_prev, const float *c_prev, const void *packed, const float *gates_bias,
                           int64_t B, int64_t H, int64_t W, int64_t C, void *h_state, float *c_state, void *h_nchw, int h_nchw_dtype, int tile_rows,
                           void *stream);
+/* The other recurrent cell, ConvGRU.forward (model/submodules.py:260-278), as TWO launches on the same main loop (the candidate reads
+ * h * reset through a 3x3 window, so it cannot share a tile's accumulators with the gates):
+ *   gates:      u = sigmoid(update_gate(cat(x, h))), r = sigmoid(reset_gate(cat(x, h)))  ->  u_ws fp32 [B,H,W,C], hr_ws = rne_bf16(h_f32 * r) bf16
+ *   candidate:  o = tanh(out_gate(cat(x, hr)));  h'_f32 = h_f32 * (1 - u) + o * u  ->  h_state_f32 fp32 and its bf16 copy h_state
+ * bf16 operands, fp32 accumulation, and the hidden state carried in fp32 (h_prev_f32 / h_state_f32) beside the bf16 copy the convolutions
+ * read (h_prev / h_state): a precision choice of THIS kernel, as the LSTM's fp32 cell state is.  All NHWC [B,H,W,C]; h_nchw (optional) as
+ * in v2v_convlstm_step_hip.  h_prev == NULL and h_prev_f32 == NULL (together) mean the zero state.  The caller owns the u_ws (B*H*W*C
+ * floats) and hr_ws (B*H*W*C bf16) workspaces; the library allocates nothing.  h_state_f32 may alias h_prev_f32; h_state / hr_ws must
+ * not alias x, h_prev or each other.  gates_bias = update_gate.bias | reset_gate.bias [2C], out_bias = out_gate.bias [C].
+ * tile_gates / tile_cand: kernel instance codes 1..5 (pixels x columns per workgroup; gates 64x128, 128x128, 128x256, 256x256, 64x256 K-split;
+ * candidate 128x64, 128x128 K-split, 128x256, 256x256, 64x128 K-split), 0 = pick by shape; a code whose columns do not divide C (gates: 2C
+ * per 64 / 128 channels) is V2V_ERR_PARAM.  Shape rules are the ConvLSTM step's (else V2V_ERR_SHAPE): C % 64 == 0, (H*W) % 4 == 0, any B*H*W. */
+int v2v_convgru_packed_bytes(int64_t C, uint64_t *gates_bytes, uint64_t *cand_bytes);   /* 2C*2C*9 and C*2C*9 bf16 */
+/* the module's update_gate.weight, reset_gate.weight, out_gate.weight, fp32 [C, 2C, 3, 3] each on the device -> the two packed bf16 streams */
+int v2v_convgru_pack_weights_hip(const float *update_weight, const float *reset_weight, const float *out_weight, int64_t C, void *packed_gates,
+                                 void *packed_cand, void *stream);
+int v2v_convgru_step_hip(const void *x, const void *h_prev, const float *h_prev_f32, const void *packed_gates, const void *packed_cand,
+                         const float *gates_bias, const float *out_bias, int64_t B, int64_t H, int64_t W, int64_t C, float *u_ws, void *hr_ws,
+                         void *h_state, float *h_state_f32, void *h_nchw, int h_nchw_dtype, int tile_gates, int tile_cand, void *stream);
 /* The residual blocks of the same encoder (ResidualBlock.forward, model/submodules.py:143-177, norm=None as E2VID instantiates
  * it at model/unet.py:48): a 3x3, stride-1, pad-1 convolution on the matrix cores with the same tiles and pipeline as the
  * ConvLSTM step -- out = [relu]( conv(x) + bias [+ residual] ), x [B,H,W,Cin] / residual, out [B,H,W,Cout] bf16 NHWC,

@@ -8,7 +8,10 @@ v2v_upsample2x_nhwc_hip.
     ConvLayer(in, out, kernel_size, stride, padding, activation, norm=None, upsample=False)
                                                           model/submodules.py:6-33, and :68-96 (UpsampleConvLayer) with
                                                           upsample=True; `conv2d`; forward(x, skip=None) folds the sum skip
+    ConvGRU(input_size, hidden_size, kernel_size)         model/submodules.py:238-278 -- same constructor, same `reset_gate` / `update_gate` /
+                                                          `out_gate` parameters, forward(input_, prev_state) -> new_state; inference only
     convlstm_step / conv_nhwc / conv3x3_nhwc / upsample2x_nhwc     the raw NHWC bfloat16 operators (v2v_amd/nhwc_ops.py, re-exported here)
+    convgru_step / pack_gru_weights                        the ConvGRU step (two launches: gates, candidate) and its packing
     conv1x1_nhwc                                           the 1x1 prediction layer on skip_sum(x, head) (ConvLayer with kernel_size 1)
     conv_head_nhwc / to_nhwc8_bf16 / pack_head_weights     the head (voxel bins -> 32 channels; ConvLayer with <= 8 input channels)
     conv_stem_nhwc / pack_stem_weights / upsample2x_cat_nhwc   the plain UNet (EVFlowNet): its stem (voxel bins -> 64, 3x3, stride 2) and concat skips
@@ -25,8 +28,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from .nhwc_ops import (_to_nhwc_bf16, conv1x1_nhwc, conv3x3_nhwc, conv_head_nhwc, conv_nhwc, conv_stem_nhwc, convlstm_step, nchw_to_nhwc_bf16,  # noqa: F401
-                       pack_conv3x3_weights, pack_conv_weights, pack_gate_weights, pack_head_weights, pack_stem_weights, packed_weights,
+from .nhwc_ops import (_to_nhwc_bf16, conv1x1_nhwc, conv3x3_nhwc, conv_head_nhwc, conv_nhwc, conv_stem_nhwc, convgru_step, convlstm_step, nchw_to_nhwc_bf16,  # noqa: F401
+                       pack_conv3x3_weights, pack_conv_weights, pack_gate_weights, pack_gru_weights, pack_head_weights, pack_stem_weights, packed_weights,
                        to_nhwc8_bf16, upsample2x_cat_nhwc, upsample2x_nhwc)
 from .train import ConvFn, ConvLSTMFn, HeadFn, PredFn, ResidualBlockFn, StemFn, UpCatConvFn, UpConvFn
 
@@ -142,6 +145,80 @@ class ConvLSTM(nn.Module):
         wants_skip_twin), `hidden` itself otherwise.  Same values either way."""
         tw = self._skip_twin
         return tw[1] if tw is not None and tw[0] is hidden else hidden
+
+
+def clone_state(t: torch.Tensor) -> torch.Tensor:
+    """detach().clone() of one state tensor that keeps what a ConvGRU state carries beside its values: the float32 master (and its bfloat16
+    NHWC twin), cloned too, so that a state read through a network's `states` property and assigned back continues bit for bit."""
+    out = t.detach().clone()
+    tag = getattr(t, "_v2v_gru", None)
+    if tag is not None and tag[2] == t._version:
+        out._v2v_gru = (tag[0].clone(), tag[1].clone(), out._version)
+    return out
+
+
+class ConvGRU(nn.Module):
+    """Drop-in for model/submodules.py:ConvGRU (:238-278) on the two-launch matrix-core step (v2v_amd/csrc/v2v_convgru.hpp).
+
+    forward(input_, prev_state) -> new_state, logically [B,C,H,W] as in the reference, handed out as ConvLSTM hands out its hidden output:
+    a contiguous NCHW tensor in the input's dtype (float32, or bfloat16 under autocast), or -- for a channels-last bfloat16 input -- a
+    channels-last view of the kernel's own NHWC buffer.  The hidden state is carried in float32 (a precision choice of this kernel, as the
+    LSTM's float32 cell state is): the returned tensor carries that master and its bfloat16 NHWC twin as an attribute, and a state that
+    comes back untouched continues from them.  Any other prev_state (cloned, loaded, edited in place) is taken at its own values: widened
+    to float32, which for a float32 state gives the same bits (v2v_amd.convlstm.clone_state / v2v_amd.unet.copy_states keep the master).
+    Inference only: the step has no backward kernel yet (trainable=True raises)."""
+
+    def __init__(self, input_size, hidden_size, kernel_size, trainable: bool = False):
+        super().__init__()
+        if kernel_size != 3 or input_size != hidden_size:
+            raise ValueError("the fused ConvGRU covers the configuration the reference instantiates "
+                             "(model/submodules.py:112: input_size == hidden_size, kernel_size=3)")
+        if trainable:
+            raise ValueError("ConvGRU is inference-only: the ConvGRU step has no backward kernel (train with recurrent_block_type 'convlstm')")
+        self.input_size, self.hidden_size = input_size, hidden_size
+        pad = kernel_size // 2
+        self.reset_gate = nn.Conv2d(input_size + hidden_size, hidden_size, kernel_size, padding=pad)
+        self.update_gate = nn.Conv2d(input_size + hidden_size, hidden_size, kernel_size, padding=pad)
+        self.out_gate = nn.Conv2d(input_size + hidden_size, hidden_size, kernel_size, padding=pad)
+        for conv in (self.reset_gate, self.update_gate, self.out_gate):          # the reference's initialisation (:253-258)
+            nn.init.orthogonal_(conv.weight)
+            nn.init.constant_(conv.bias, 0.0)
+        self._packed = {}
+        self.trainable = False
+        self.wants_skip_twin = False                                           # ConvLSTM's training-only switch: nothing to do here
+
+    def _weights(self):
+        """Everything forward needs packed, now (on the current stream): ((gates stream, candidate stream), gates bias [2C], out bias [C]),
+        repacked when any of the six parameters changed (another tensor, an in-place update, another device)."""
+        ps = (self.update_gate.weight, self.reset_gate.weight, self.out_gate.weight, self.update_gate.bias, self.reset_gate.bias, self.out_gate.bias)
+        key = tuple((p.data_ptr(), p._version, p.device) for p in ps)
+        hit = self._packed.get("gru")
+        if hit is None or hit[0] != key:
+            w_u, w_r, w_o, b_u, b_r, b_o = (p.detach() for p in ps)
+            hit = self._packed["gru"] = (key, (pack_gru_weights(w_u, w_r, w_o), torch.cat([b_u, b_r]).float().contiguous(), b_o.float().contiguous()))
+        return hit[1]
+
+    def forward(self, input_, prev_state=None, input_relu: bool = False):
+        """input_relu=True takes the PRE-activation output of the convolution in front and applies its ReLU on the way in (as ConvLSTM)."""
+        _training(self, input_)                                                # raises under grad: inference only
+        nhwc_io = _is_nhwc_bf16(input_)
+        x = _nhwc_in(input_, nhwc_io, False, relu=input_relu)
+        h_prev = h_prev32 = None
+        if prev_state is not None:
+            tag = getattr(prev_state, "_v2v_gru", None)
+            if tag is not None and tag[2] == prev_state._version and tag[0].device == x.device and tuple(tag[0].shape) == tuple(x.shape):
+                h_prev32, h_prev = tag[0], tag[1]
+            else:
+                h_prev32 = prev_state.detach().permute(0, 2, 3, 1).float().contiguous()
+                h_prev = h_prev32.to(torch.bfloat16)
+        packed, b_gates, b_out = self._weights()
+        outs = convgru_step(x, h_prev, h_prev32, packed, b_gates, b_out, nchw_dtype=None if nhwc_io else input_.dtype)
+        state = outs[0].permute(0, 3, 1, 2) if nhwc_io else outs[4]
+        state._v2v_gru = (outs[1], outs[0], state._version)
+        return state
+
+    def skip_twin(self, hidden):
+        return hidden
 
 
 class ResidualBlock(nn.Module):

@@ -113,6 +113,11 @@ struct ConvLstmArgs {
 hipError_t launch_convlstm_step(const ConvLstmArgs &a, int tile_rows, hipStream_t s);   // tile_rows: 0 auto, 64, 128 or 256
 hipError_t launch_convlstm_pack(const float *w, uint16_t *wp, int C, hipStream_t s);
 hipError_t launch_convlstm_step_bwd(const ConvLstmArgs &a, hipStream_t s);
+// the ConvGRU step (v2v_convgru_tu.hip; how the two launches read ConvLstmArgs: v2v_convgru.hpp).  tile: instance code, 0 = auto
+hipError_t launch_convgru_gates(const ConvLstmArgs &a, int tile, hipStream_t s);
+hipError_t launch_convgru_candidate(const ConvLstmArgs &a, int tile, hipStream_t s);
+hipError_t launch_convgru_pack(const float *w_u, const float *w_r, const float *w_o, uint16_t *wp_gates, uint16_t *wp_cand, int C, hipStream_t s);
+bool convgru_tile_ok(int C, int tile_gates, int tile_cand);
 // backward passes of the recurrent UNet (v2v_train_tu.hip)
 int64_t wgrad_slabs(int64_t M, int Cout, int64_t N);
 hipError_t launch_conv_wgrad(const uint16_t *dy, const uint16_t *x1, int C1, const uint16_t *x2, int C2, int Cin_out, float *dw, float *db, float *ws,

@@ -50,6 +50,11 @@ typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 cl_bf16x8;
 typedef __attribute__((__vector_size__(16 * sizeof(float)))) float cl_f32x16;
 
 
+// V2V_CL_STEP_ONLY: defined by a SECOND translation unit that instantiates convlstm_step_kernel (v2v_convgru_tu.hip) -- it gets a zero line
+// of its own with internal linkage and none of the non-template kernels below the step kernel (one definition each, in v2v_convlstm_tu.hip)
+#ifdef V2V_CL_STEP_ONLY
+static
+#endif
 __device__ __attribute__((aligned(128))) unsigned char g_cl_zero_line[128];      // zero-initialised: the padding source
 
 // float -> bf16, round to nearest even, NaN stays NaN: gfx950's v_cvt_pk_bf16_f32 (two values per instruction)
@@ -101,6 +106,12 @@ __device__ __forceinline__ void cl_epilogue_conv(const ConvLstmArgs &a, cl_f32x1
     }
 }
 
+// the ConvGRU epilogues (EPI = 3 / 4): defined in v2v_convgru.hpp, which only the ConvGRU translation unit includes
+template <int MF, int NF>
+__device__ __forceinline__ void gru_epilogue_gates(const ConvLstmArgs &a, cl_f32x16 (&acc)[MF][NF], int64_t mw0, int ch0, int fh, int64_t M);
+template <int MF, int NF>
+__device__ __forceinline__ void gru_epilogue_candidate(const ConvLstmArgs &a, cl_f32x16 (&acc)[MF][NF], int64_t mw0, int col0, int fh, int64_t M);
+
 // EPI = 0: ConvLSTM step (two inputs x|h, 4C gate columns, gate/cell epilogue).  EPI = 2: the step's BACKWARD on the same main loop
 // (the gate GEMM recomputed from the saved x, h_prev; the cell backward on the accumulators, epilogue below).  EPI = 1: plain 3x3 convolution of x with
 // n_cols output channels (a multiple of 256), epilogue bias (+ residual) (+ ReLU) -> bf16 NHWC: the residual blocks of the same
@@ -114,11 +125,15 @@ __device__ __forceinline__ void cl_epilogue_conv(const ConvLstmArgs &a, cl_f32x1
 // KS = 2 (EPI = 1, three stages): the workgroup is TWO wave groups that walk alternate K chunks of the SAME tile (each with its own
 // LDS stages), i.e. twice the waves, LDS-DMA in flight and MFMA issue per CU for the small layers that cannot fill the chip with
 // more tiles; group 1's accumulators meet group 0's through LDS before the epilogue.
+// EPI = 3 / 4: the two launches of the ConvGRU step (v2v_convgru_tu.hip; epilogues and argument aliases in v2v_convgru.hpp).  Both walk
+// K over two inputs like the step (x | h_prev, h_prev null = zero state) on weights packed in tiles of a.pack_cols columns.
+// EPI = 3, gates: 2C columns, fragment pairs (update, reset) of 32 hidden channels (NF = 2 or 4 -> 32 or 64 channels per wave).
+// EPI = 4, candidate: C columns laid out like EPI = 1's (fragment g of a wave = channels col0 + 32 g ..).
 template <int MF, int WM, int STAGES = 2, int EPI = 0, int WN = 2, int NF = 4, int TPC = 1, int KS = 1>
 __global__ void __launch_bounds__(64 * WM * WN * KS, KS == 2 || WM * WN == 16 ? 1 : (STAGES == 2 && MF == 1) || WM * WN == 8 || NF < 4 ? 2 : 1) convlstm_step_kernel(const ConvLstmArgs a)
 {
     static_assert(KS == 1 || KS == 2, "one or two K groups");
-    static_assert(EPI == 1 || NF == 4, "the gate epilogue needs the four gates of a channel in one wave");
+    static_assert(EPI == 1 || EPI == 4 || NF == 4 || (EPI == 3 && NF == 2), "the gate epilogue needs the four (GRU: two) gates of a channel in one wave");
     static_assert(TPC == 1 || (TPC == 2 && EPI == 1), "two taps per chunk: plain convolution of 32 input channels");
     constexpr int kBN = WN * NF * 32, kBBytes = kBN * kClBK * 2;
     constexpr int kClBM = 32 * MF * WM, kClABytes = kClBM * kClBK * 2, kClStage = kClABytes + kBBytes;
@@ -132,7 +147,7 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, KS == 2 || WM * WN == 16 ? 
     const int C = a.C, HW = a.H * a.W;
     const int ks = EPI != 1 ? 3 : a.ks, pad = ks >> 1, n_taps = ks * ks, stride = EPI != 1 ? 1 : a.stride;
     const int Hin = EPI != 1 ? a.H : a.Hin, Win = EPI != 1 ? a.W : a.Win;
-    constexpr int kStepCh = WN * 32;                              // hidden channels per column tile of the step (64, or 32 with one wave column)
+    constexpr int kStepCh = EPI == 3 ? kBN / 2 : EPI == 4 ? kBN : WN * 32;   // hidden channels per column tile of the step (64, or 32 with one wave column)
     const int n_ct = EPI != 1 ? C / kStepCh : a.n_cols / kBN;     // column tiles
     const int ct = blockIdx.x % n_ct;
     const int64_t m0 = (int64_t)(blockIdx.x / n_ct) * kClBM;      // first pixel of the tile (flattened b,y,x)
@@ -167,7 +182,7 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, KS == 2 || WM * WN == 16 ? 
         boff[j] = (uint32_t)(row * kClBK + (sslot ^ ((row >> 1) & 7)) * 8);
     }
     // a column tile narrower than the packed one (EPI = 1, 128-column instances on 256-column packing): sub-tile `ct % per`
-    const int pcols = EPI != 1 ? kClBN : a.pack_cols ? a.pack_cols : kBN, per = pcols / kBN;   // the step's weights are packed per 64 channels
+    const int pcols = (EPI == 0 || EPI == 2) ? kClBN : a.pack_cols ? a.pack_cols : kBN, per = pcols / kBN;   // the step's weights are packed per 64 channels
     const uint16_t *wtile = a.wp + (int64_t)(ct / per) * (TPC == 2 ? n_chunks : n_taps * cc_all) * (pcols * kClBK) + (ct % per) * (kBN * kClBK);
 
     // LDS-DMA of chunk ck into buffer buf (part / nparts: a subset of the pieces, j % nparts == part).  The main loop issues
@@ -378,6 +393,8 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, KS == 2 || WM * WN == 16 ? 
         }
     }
     }
+    if constexpr (EPI == 3) { gru_epilogue_gates<MF, NF>(a, acc, m0 + wm * 32 * MF, ct * kStepCh + wn * 16 * NF + fr, fh, M); return; }
+    if constexpr (EPI == 4) { gru_epilogue_candidate<MF, NF>(a, acc, m0 + wm * 32 * MF, ct * kBN + wn * 32 * NF + fr, fh, M); return; }
     if constexpr (EPI == 2) {
     // ---- backward epilogue: the forward's gate / cell values recomputed on the accumulators (same expressions), then
     //   tc = tanh(c);  dc_tot = dc + dh * o * (1 - tc^2);  d_o = dh * tc;  d_i = dc_tot * g;  d_g = dc_tot * i;  d_r = dc_tot * c_prev
@@ -416,6 +433,7 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, KS == 2 || WM * WN == 16 ? 
     }
 }
 
+#ifndef V2V_CL_STEP_ONLY
 // fp32 or bf16 NCHW -> bf16 NHWC (optionally through a ReLU): the layout change between the stock convolution upstream and the
 // fused step.  One workgroup moves 64 pixels x 64 channels through LDS so that both sides are full-line accesses.
 __device__ __forceinline__ float cl_load_f32(const float *p, int64_t i) { return p[i]; }
@@ -1014,5 +1032,7 @@ __global__ void __launch_bounds__(256) upsample2x_cat_nhwc_bf16_kernel(const uin
         for (int e = 0; e < 8; ++e) { L[0][e] = L[1][e]; R[0][e] = R[1][e]; L[1][e] = L[2][e]; R[1][e] = R[2][e]; }
     }
 }
+
+#endif  // V2V_CL_STEP_ONLY
 
 }  // namespace v2v

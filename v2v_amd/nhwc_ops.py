@@ -3,6 +3,7 @@
 v2v_amd/train.py builds the torch.autograd.Functions on these, v2v_amd/convlstm.py the layers.
 
     convlstm_step / conv_nhwc / conv3x3_nhwc / upsample2x_nhwc     the forward operators
+    convgru_step / pack_gru_weights                        the ConvGRU step (gates launch + candidate launch) and its packing
     conv1x1_nhwc                                           the 1x1 prediction layer on skip_sum(x, head)
     conv_head_nhwc / to_nhwc8_bf16 / pack_head_weights     the head (voxel bins -> 32 channels)
     conv_stem_nhwc / pack_stem_weights / upsample2x_cat_nhwc       the plain UNet (EVFlowNet): stride-2 stem (voxel bins -> 64), concat-skip upsampling
@@ -126,6 +127,58 @@ def convlstm_step(x, h_prev, c_prev, packed, bias, nchw_dtype=torch.float32, til
                                                     b, h, w, c, _ptr(h_state), _ptr(c_state), _ptr(h_nchw), _DTYPES.get(nchw_dtype, _lib.F32), tile_rows,
                                                     _lib.stream_ptr()))
     return h_state, c_state, h_nchw
+
+
+# ---- the ConvGRU step (model/submodules.py:260-278): two launches behind one call ---------------------------------------------------------
+def pack_gru_weights(update_weight, reset_weight, out_weight):
+    """update_gate.weight, reset_gate.weight, out_gate.weight (float32 [C, 2C, 3, 3] each) -> (packed gates stream, packed candidate
+    stream), flat bfloat16 tensors (layout: v2v_amd/csrc/v2v_convgru.hpp)."""
+    _lib.require_gpu()
+    ws = (update_weight, reset_weight, out_weight)
+    c = update_weight.shape[0] if update_weight.dim() == 4 else 0
+    for w in ws:
+        if not w.is_cuda or w.dtype != torch.float32 or tuple(w.shape) != (c, 2 * c, 3, 3) or w.device != update_weight.device:
+            raise ValueError("the three gate weights must be float32 CUDA tensors [C, 2C, 3, 3] on one device")
+    ng, nc = C.c_uint64(0), C.c_uint64(0)
+    _lib.check(_lib.lib().v2v_convgru_packed_bytes(c, C.byref(ng), C.byref(nc)))
+    pg = torch.empty((ng.value // 2,), dtype=torch.bfloat16, device=update_weight.device)
+    pc = torch.empty((nc.value // 2,), dtype=torch.bfloat16, device=update_weight.device)
+    with torch.cuda.device(update_weight.device):
+        _lib.check(_lib.lib().v2v_convgru_pack_weights_hip(*(_ptr(w.detach().contiguous()) for w in ws), c, _ptr(pg), _ptr(pc), _lib.stream_ptr()))
+    return pg, pc
+
+
+def convgru_step(x, h_prev, h_prev_f32, packed, gates_bias, out_bias, nchw_dtype=None, tile_gates: int = 0, tile_cand: int = 0, h_f32_out=None):
+    """One ConvGRU step on NHWC state.  x, h_prev: bfloat16 [B,H,W,C]; h_prev_f32: the float32 master of h_prev; both None = zero state.
+    packed = pack_gru_weights(...), gates_bias float32 [2C] = update | reset, out_bias float32 [C].
+    Returns (h_bf16, h_f32, u, hr[, h as [B,C,H,W] in nchw_dtype when that is not None]): the new state in bfloat16 (what the next step's
+    convolutions and the layers downstream read) and float32 (the master the next step's blend reads), the update gate (float32) and
+    rne_bf16(h_prev_f32 * reset) -- the two workspaces between the launches.  h_f32_out may be h_prev_f32 (updated in place).
+    tile_gates / tile_cand: kernel instance codes 1..5 (include/v2v_hip.h), 0 = by shape."""
+    _lib.require_gpu()
+    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("x must be a contiguous bfloat16 CUDA tensor [B,H,W,C]")
+    b, h, w, c = x.shape
+    if (h_prev is None) != (h_prev_f32 is None):
+        raise ValueError("h_prev and h_prev_f32 come together (both None: the zero state)")
+    for name, t, dt in (("h_prev", h_prev, torch.bfloat16), ("h_prev_f32", h_prev_f32, torch.float32)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (b, h, w, c) or not t.is_contiguous() or t.device != x.device):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor [B,H,W,C] on x's device")
+    pg, pc = packed
+    if gates_bias.dtype != torch.float32 or gates_bias.numel() != 2 * c or out_bias.dtype != torch.float32 or out_bias.numel() != c \
+            or pg.dtype != torch.bfloat16 or pg.numel() != 2 * c * 2 * c * 9 or pc.dtype != torch.bfloat16 or pc.numel() != c * 2 * c * 9:
+        raise ValueError("gates_bias must be float32 [2C], out_bias float32 [C] and packed the output of pack_gru_weights for the same C")
+    if nchw_dtype is not None and nchw_dtype not in _DTYPES:
+        raise ValueError("nchw_dtype must be torch.float32, torch.bfloat16 or None")
+    h_bf16, hr = torch.empty_like(x), torch.empty_like(x)
+    u = torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
+    h_f32 = h_f32_out if h_f32_out is not None else torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
+    h_nchw = torch.empty((b, c, h, w), dtype=nchw_dtype, device=x.device) if nchw_dtype is not None else None
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_convgru_step_hip(_ptr(x), _ptr(h_prev), _ptr(h_prev_f32), _ptr(pg), _ptr(pc), _ptr(gates_bias.detach().contiguous()),
+                                                   _ptr(out_bias.detach().contiguous()), b, h, w, c, _ptr(u), _ptr(hr), _ptr(h_bf16), _ptr(h_f32),
+                                                   _ptr(h_nchw), _DTYPES.get(nchw_dtype, _lib.F32), tile_gates, tile_cand, _lib.stream_ptr()))
+    return (h_bf16, h_f32, u, hr) if nchw_dtype is None else (h_bf16, h_f32, u, hr, h_nchw)
 
 
 # ---- the convolutions (ConvLayer / UpsampleConvLayer / ResidualBlock, model/submodules.py:6-96, :143-177) on the same matrix-core kernel ---

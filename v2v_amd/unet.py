@@ -8,8 +8,11 @@ v2v_amd/convlstm.py under the REFERENCE'S OWN module tree, so that a reference c
                                                                                  decoders.N.conv2d.*, pred.conv2d.*
     RecurrentConvLayer / UpsampleConvLayer model/submodules.py:99-119 / :68-96
 
-Configuration covered = what config/train_v2v_e2vid_10k.yaml:21-30 instantiates: skip_type 'sum', recurrent_block_type
-'convlstm', use_upsample_conv true, norm none, kernel_size 5, base_num_channels 32, channel_multiplier 2 (anything else raises:
+    FlowNet(unet_kwargs)                   model/model.py:111-139          keys  unetflow.*   (E2VID+: {'image', 'flow'})
+    UNetFlow(unet_kwargs)                  model/unet.py:133-194           UNetRecurrent's body at prediction width 3
+
+Configuration covered = what config/train_v2v_e2vid_10k.yaml:21-30 / config/test_e2vid++_original.yaml instantiate: skip_type 'sum',
+recurrent_block_type 'convlstm' or (E2VIDRecurrent / FlowNet, inference only) 'convgru', use_upsample_conv true, norm none, kernel_size 5, base_num_channels 32, channel_multiplier 2 (anything else raises:
 there is no stock-layer fallback inside this module).  Inference by default; trainable=True adds the backward kernels of
 v2v_amd/train.py (back-propagation through time through the ConvLSTM states when grad is enabled).
 
@@ -29,7 +32,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from .convlstm import ConvLayer, ConvLSTM, ResidualBlock
+from .convlstm import ConvGRU, ConvLayer, ConvLSTM, ResidualBlock, clone_state
 from .nhwc_ops import tile_like_batch
 
 
@@ -42,36 +45,46 @@ class UpsampleConvLayer(ConvLayer):
 
 
 class RecurrentConvLayer(nn.Module):
-    """model/submodules.py:99-119: ConvLayer followed by the ConvLSTM; same attribute names (`conv`, `recurrent_block`)."""
+    """model/submodules.py:99-119: ConvLayer followed by the ConvLSTM or the ConvGRU; same attribute names (`conv`, `recurrent_block`).
+    forward returns (x, state): state = (hidden, cell) and x = hidden for 'convlstm', state = x = the new hidden state for 'convgru' (:117)."""
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=0, recurrent_block_type="convlstm",
                  activation="relu", norm=None, BN_momentum=0.1, trainable: bool = False):
         super().__init__()
-        if recurrent_block_type != "convlstm":
-            raise ValueError("only recurrent_block_type 'convlstm' runs on the device kernels")
+        if recurrent_block_type not in ("convlstm", "convgru"):
+            raise ValueError("recurrent_block_type is 'convlstm' or 'convgru' (model/submodules.py:104)")
+        if recurrent_block_type == "convgru" and trainable:
+            raise ValueError("trainable=True with recurrent_block_type 'convgru': the ConvGRU step has no backward kernel yet "
+                             "(train with 'convlstm', or build the network with trainable=False)")
         self.recurrent_block_type = recurrent_block_type
         self.conv = ConvLayer(in_channels, out_channels, kernel_size, stride, padding, activation, norm, trainable=trainable)
-        self.recurrent_block = ConvLSTM(input_size=out_channels, hidden_size=out_channels, kernel_size=3, trainable=trainable)
+        block = ConvLSTM if recurrent_block_type == "convlstm" else ConvGRU
+        self.recurrent_block = block(input_size=out_channels, hidden_size=out_channels, kernel_size=3, trainable=trainable)
 
     def forward(self, x, prev_state, conv_out=None):
         """conv_out (this implementation only): self.conv(x) when the caller has it already -- the convolution does not touch the state,
         so UNetRecurrent.forward_sequence runs the first encoder's for all time steps in one launch."""
         x = self.conv(x) if conv_out is None else conv_out  # ReLU in the convolution's epilogue
         state = self.recurrent_block(x, prev_state)
-        return state[0], state
+        return (state[0] if self.recurrent_block_type == "convlstm" else state), state
 
 
 class UNetRecurrent(nn.Module):
     """model/unet.py:252-310 (+ BaseUNet :13-64).  `unet_kwargs` as the reference's YAML gives them.  trainable=True: every layer records
     its backward (v2v_amd/train.py) when grad is enabled; with grad disabled, or trainable=False, the network is the inference one."""
 
-    def __init__(self, unet_kwargs, trainable: bool = False):
+    NUM_OUTPUT_CHANNELS = 1                                # :263 -- the prediction width (UNetFlow: 3)
+
+    def __init__(self, unet_kwargs, trainable: bool = False, convgru: bool = False):
+        """convgru: recurrent_block_type 'convgru' is an opt-in of the caller.  This class on its own keeps refusing it, as it always has
+        (a ConvGRU state is one tensor carrying a float32 master, not the (hidden, cell) pair code written against this class expects);
+        the model classes E2VIDRecurrent and FlowNet, which own the states and copy them with their masters, opt in."""
         super().__init__()
         self.trainable = bool(trainable)
         kw = dict(unet_kwargs)
         final_activation = kw.pop("final_activation", "none")
         self.final_activation = getattr(torch, final_activation, None) if final_activation else None
-        kw["num_output_channels"] = 1                      # :263
+        kw["num_output_channels"] = self.NUM_OUTPUT_CHANNELS
         self.base_num_channels = kw["base_num_channels"]
         self.num_encoders = kw["num_encoders"]
         self.num_residual_blocks = kw["num_residual_blocks"]
@@ -81,6 +94,9 @@ class UNetRecurrent(nn.Module):
         self.norm = kw.get("norm", None)
         self.num_bins = kw["num_bins"]
         self.recurrent_block_type = kw.get("recurrent_block_type", None)
+        if self.recurrent_block_type == "convgru" and not convgru:
+            raise ValueError("recurrent_block_type 'convgru' runs through the model classes (E2VIDRecurrent, FlowNet), or with convgru=True: "
+                             "its state is one tensor with a float32 master (v2v_amd.unet.copy_states keeps it)")
         mult = kw.get("channel_multiplier", 2)
         if self.norm in ("none", "None", ""):
             self.norm = None
@@ -142,12 +158,12 @@ class UNetRecurrent(nn.Module):
         pack kernels have written them (and the packed tensors would live in one side stream's allocator pool while every stream reads
         them).  Packed here, they are ordered before every side stream by the wait_stream() that follows."""
         for m in self.modules():
-            if isinstance(m, (ConvLayer, ConvLSTM, ResidualBlock)):
+            if isinstance(m, (ConvLayer, ConvLSTM, ConvGRU, ResidualBlock)):
                 m._weights()
 
     def forward_sequence(self, events, event_scales=None, out=None, overlap=True):
         """The time loop of model/train_utils.py:339-345 (`for t in range(T): pred = model(events[:, t]); pred_imgs[:, t] = pred['image']`)
-        as ONE call: events [N,T,num_bins,H,W] -> images [N,T,1,H,W] (events' dtype, or `out`), the states advanced by T steps.
+        as ONE call: events [N,T,num_bins,H,W] -> predictions [N,T,num_output_channels,H,W] (events' dtype, or `out`), the states advanced by T steps.
 
         The recurrence only runs through the encoders' ConvLSTM states; residual blocks, decoders and prediction of step t are stateless.
         With overlap they are issued on side HIP streams (overlap=True: three, taken in turn by consecutive steps; an int: that many),
@@ -229,38 +245,67 @@ class UNetRecurrent(nn.Module):
 
 
 def copy_states(states):
-    """model/model.py:17-24 copy_states: clone every state tensor (a list of None stays a list of None)."""
+    """model/model.py:17-24 copy_states: clone every state tensor (a list of None stays a list of None)
+    (a ConvGRU state -- a single tensor -- keeps its float32 master: convlstm.clone_state)."""
     if states[0] is None:
         return list(states)
-    return [tuple(s.detach().clone() for s in st) if isinstance(st, tuple) else st.detach().clone() for st in states]
+    return [tuple(s.detach().clone() for s in st) if isinstance(st, tuple) else clone_state(st) for st in states]
 
 
-class E2VIDRecurrent(nn.Module):
-    """model/model.py:194-223: `unetrecurrent` + the states property / reset_states the training loop uses."""
+class UNetFlow(UNetRecurrent):
+    """model/unet.py:133-194: the recurrent UNet with a 3-channel prediction -- UNetRecurrent's body at prediction width 3 (same module tree,
+    same keys) -- returning {'image': [:, 0:1], 'flow': [:, 1:3]}.  (img_3c and final_activation are not part of it: :140-159.)"""
+
+    NUM_OUTPUT_CHANNELS = 3                                # :141
+
+    def __init__(self, unet_kwargs, trainable: bool = False, convgru: bool = True):
+        if "final_activation" in unet_kwargs:
+            raise ValueError("UNetFlow takes no final_activation (model/unet.py:140-142 passes its kwargs to BaseUNet, which has none)")
+        super().__init__(unet_kwargs, trainable=trainable, convgru=convgru)
+
+    @staticmethod
+    def split(img_flow):
+        """[..., 3, H, W] -> {'image': [..., 0:1, H, W], 'flow': [..., 1:3, H, W]} (:192), views of the prediction."""
+        return {"image": img_flow[..., 0:1, :, :], "flow": img_flow[..., 1:3, :, :]}
+
+    def forward(self, x, event_scales=None):
+        return self.split(super().forward(x, event_scales)["image"])
+
+
+class _RecurrentModel(nn.Module):
+    """What the reference's recurrent model classes share (model/model.py:194-223, :111-139): the network under its own attribute name
+    (`NET`), the states property / reset_states the training loop uses, the sequence call and its hipGraph capture."""
+
+    NET = None                                             # attribute (and state_dict prefix) of the network
+    NET_CLASS = None
 
     def __init__(self, unet_kwargs, trainable: bool = False):
         super().__init__()
         self.num_bins = unet_kwargs["num_bins"]
         self.num_encoders = unet_kwargs["num_encoders"]
-        self.trainable = bool(trainable)           # the YAML switch: model: {target: ..E2VIDRecurrent, params: {unet_kwargs: .., trainable: true}}
-        self.unetrecurrent = UNetRecurrent(unet_kwargs, trainable=trainable)
+        self.trainable = bool(trainable)           # the YAML switch: model: {target: .., params: {unet_kwargs: .., trainable: true}}
+        setattr(self, self.NET, self.NET_CLASS(unet_kwargs, trainable=trainable, convgru=True))
+
+    @property
+    def net(self):
+        return getattr(self, self.NET)
 
     @property
     def states(self):
-        return copy_states(self.unetrecurrent.states)
+        return copy_states(self.net.states)
 
     @states.setter
     def states(self, states):
-        self.unetrecurrent.states = states
+        self.net.states = states
 
     def reset_states(self):
-        self.unetrecurrent.states = [None] * self.unetrecurrent.num_encoders
+        self.net.states = [None] * self.net.num_encoders
 
     def forward(self, event_tensor, event_scales=None):
-        return self.unetrecurrent.forward(event_tensor, event_scales)
+        return self.net.forward(event_tensor, event_scales)
 
     def forward_sequence(self, events, event_scales=None, out=None, overlap=True, graph=False):
-        """[N,T,num_bins,H,W] -> [N,T,1,H,W]: the reference's time loop (model/train_utils.py:339-345) in one call, decoder half of step t
+        """[N,T,num_bins,H,W] -> [N,T,num_output_channels,H,W]: the reference's time loop (model/train_utils.py:339-345) in one call, decoder half of step t
         under the encoder half of step t+1 (UNetRecurrent.forward_sequence).
 
         graph=True: the whole sequence -- reset_states() first, as forward_sequence(reset_states=True) does (model/train_utils.py:309-313),
@@ -270,7 +315,7 @@ class E2VIDRecurrent(nn.Module):
         the next call with the same shapes -- clone it to keep it); the states after the call are those of the sequence's last step.
         Inference only (with trainable=True and grad enabled: ValueError)."""
         if not graph:
-            return self.unetrecurrent.forward_sequence(events, event_scales, out=out, overlap=overlap)
+            return self.net.forward_sequence(events, event_scales, out=out, overlap=overlap)
         if self.trainable and torch.is_grad_enabled():
             raise ValueError("graph=True captures inference only: run training steps with graph=False (or under torch.no_grad())")
         if out is not None:
@@ -287,7 +332,7 @@ class E2VIDRecurrent(nn.Module):
 
             def run():
                 self.reset_states()
-                return self.unetrecurrent.forward_sequence(ev, sc, overlap=overlap)
+                return self.net.forward_sequence(ev, sc, overlap=overlap)
             ev.copy_(events)
             if sc is not None:
                 sc.copy_(event_scales)
@@ -302,14 +347,32 @@ class E2VIDRecurrent(nn.Module):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     res = run()
-            entry = cache[key] = (g, ev, sc, res, tuple(self.unetrecurrent.states))   # an immutable copy: eager calls between two replays
+            entry = cache[key] = (g, ev, sc, res, tuple(self.net.states))   # an immutable copy: eager calls between two replays
         g, ev, sc, res, states = entry                                                # assign into the live list (self.states[i] = state)
         ev.copy_(events)
         if sc is not None:
             sc.copy_(event_scales)
         g.replay()
-        self.unetrecurrent.states = list(states)                # the graph's own state tensors: what the last captured step wrote
+        self.net.states = list(states)                          # the graph's own state tensors: what the last captured step wrote
         return res
+
+
+class E2VIDRecurrent(_RecurrentModel):
+    """model/model.py:194-223: `unetrecurrent` + the states property / reset_states the training loop uses.  Both recurrent block types;
+    'convgru' is inference-only."""
+
+    NET, NET_CLASS = "unetrecurrent", UNetRecurrent
+
+
+class FlowNet(_RecurrentModel):
+    """model/model.py:111-139: `unetflow` = UNetFlow, the E2VID+ network of config/test_e2vid++_original.yaml; keys unetflow.*.
+    forward -> {'image': [N,1,H,W], 'flow': [N,2,H,W]}; forward_sequence -> {'image': [N,T,1,H,W], 'flow': [N,T,2,H,W]} (views of one
+    [N,T,3,H,W] tensor; graph=True: of the captured graph's static output).  Both recurrent block types; trainable=True with 'convlstm'."""
+
+    NET, NET_CLASS = "unetflow", UNetFlow
+
+    def forward_sequence(self, events, event_scales=None, out=None, overlap=True, graph=False):
+        return UNetFlow.split(super().forward_sequence(events, event_scales, out=out, overlap=overlap, graph=graph))
 
 
 class UNet(nn.Module):

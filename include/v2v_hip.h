@@ -35,8 +35,10 @@ extern "C" {
  *    native noise.  Replay-mode (V2V_RNG_REPLAY) results are unchanged.
  * 3: v2v_esim_extras grew two trailing fields (stored_frames, frames_elems: the bounds of the frame_index gather).  Every function
  *    signature and every result of ABI 2 is unchanged; a caller that fills v2v_esim_extras must be recompiled (or zero the struct at
- *    its new size): an ABI-2 struct is 16 bytes shorter. */
-#define V2V_ABI_VERSION 5
+ *    its new size): an ABI-2 struct is 16 bytes shorter.
+ * 6: nine new entry points, the 16-channel layer family (FireNet): v2v_convgru16_*, v2v_resblock16_*, v2v_conv_head16_*.  Every signature and
+ *    result of ABI 5 is unchanged. */
+#define V2V_ABI_VERSION 6
 
 typedef enum v2v_status {
     V2V_OK = 0,
@@ -322,6 +324,34 @@ int v2v_convgru_pack_weights_hip(const float *update_weight, const float *reset_
 int v2v_convgru_step_hip(const void *x, const void *h_prev, const float *h_prev_f32, const void *packed_gates, const void *packed_cand,
                          const float *gates_bias, const float *out_bias, int64_t B, int64_t H, int64_t W, int64_t C, float *u_ws, void *hr_ws,
                          void *h_state, float *h_state_f32, void *h_nchw, int h_nchw_dtype, int tile_gates, int tile_cand, void *stream);
+/* The 16-channel layer family (FireNet, model/model.py:264-311; kernels in v2v_amd/csrc/v2v_narrow.hpp).  All activations NHWC bf16
+ * [B,H,W,16], bf16 operands, fp32 accumulation on the matrix cores, ANY B, H, W >= 1 (tensors below 2^31 elements, else V2V_ERR_SHAPE).
+ * Each layer is ONE launch that runs two dependent 3x3 convolutions through LDS on 16 x 16 pixel tiles; the intermediate never reaches
+ * memory.  Asynchronous on `stream`, nothing is allocated.  x / h_prev / packed / out need 16-byte alignment (V2V_ERR_ALIGN).
+ *
+ * ConvGRU(16, 16, 3) step (model/submodules.py:260-278): the precision contract of v2v_convgru_step_hip -- u in fp32,
+ * hr = rne_bf16(h_f32 * r), h'_f32 = h_f32 (1 - u) + tanh(.) u stored as fp32 (h_state_f32) and as its bf16 RNE copy (h_state), plus the
+ * optional [B,16,H,W] copy h_nchw in h_nchw_dtype -- without the u / hr workspaces.  h_prev == NULL and h_prev_f32 == NULL (together): the zero
+ * state.  gates_bias = update_gate.bias | reset_gate.bias [32], out_bias = out_gate.bias [16].  h_state must not alias h_prev or x, and
+ * h_state_f32 must not alias h_prev_f32 (neighbouring tiles read both). */
+int64_t v2v_convgru16_packed_elems(void);                                         /* bf16 elements of the packed stream (3 * 16 * 32 * 9) */
+/* update_gate.weight, reset_gate.weight, out_gate.weight: fp32 [16, 32, 3, 3] each on the device */
+int v2v_convgru16_pack_weights_hip(const float *update_weight, const float *reset_weight, const float *out_weight, void *packed, void *stream);
+int v2v_convgru16_step_hip(const void *x, const void *h_prev, const float *h_prev_f32, const void *packed, const float *gates_bias,
+                           const float *out_bias, int64_t B, int64_t H, int64_t W, void *h_state, float *h_state_f32, void *h_nchw,
+                           int h_nchw_dtype, void *stream);
+/* ResidualBlock(16, 16) (model/submodules.py:143-177, norm=None): out = relu(conv2(relu(conv1(x) + b1)) + b2 + x), one rounding to bf16.
+ * w1 / w2: conv1.weight / conv2.weight fp32 [16, 16, 3, 3].  out must not alias x. */
+int64_t v2v_resblock16_packed_elems(void);
+int v2v_resblock16_pack_weights_hip(const float *w1, const float *w2, void *packed, void *stream);
+int v2v_resblock16_nhwc_hip(const void *x, const void *packed, const float *b1, const float *b2, int64_t B, int64_t H, int64_t W, void *out,
+                            void *stream);
+/* The head ConvLayer(Cin <= 8, 16, 3, padding 1): x8 [B,H,W,8] bf16 (v2v_to_nhwc8_bf16[_scaled]_hip) -> [relu](conv3x3 + bias) [B,H,W,16] bf16.
+ * weight: fp32 [16, Cin, 3, 3]. */
+int64_t v2v_conv_head16_packed_elems(void);
+int v2v_conv_head16_pack_weights_hip(const float *weight, int64_t Cin, void *packed, void *stream);
+int v2v_conv_head16_nhwc_hip(const void *x8, const void *packed, const float *bias, int relu, int64_t B, int64_t H, int64_t W, void *out,
+                             void *stream);
 /* The residual blocks of the same encoder (ResidualBlock.forward, model/submodules.py:143-177, norm=None as E2VID instantiates
  * it at model/unet.py:48): a 3x3, stride-1, pad-1 convolution on the matrix cores with the same tiles and pipeline as the
  * ConvLSTM step -- out = [relu]( conv(x) + bias [+ residual] ), x [B,H,W,Cin] / residual, out [B,H,W,Cout] bf16 NHWC,

@@ -18,7 +18,7 @@ FLAG_NO_NOISE = 0x2
 FLAG_SYMMETRIC = 0x4
 FLAG_MAP_4PX, FLAG_MAP_1PX, FLAG_MAP_2PX = 0x8, 0x10, 0x20
 OK, ERR_NULL, ERR_SHAPE, ERR_BINS, ERR_DTYPE, ERR_MODE, ERR_ALIGN, ERR_HIP, ERR_PARAM = 0, -1, -2, -3, -4, -5, -6, -7, -8
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 EXPORTS = ("v2v_version", "v2v_last_error", "v2v_device_count", "v2v_lut_get", "v2v_lut_set",
            "v2v_esim_voxel_hip", "v2v_esim_voxel_keyed_hip", "v2v_esim_voxel_bytes", "v2v_synth_clips_hip", "v2v_events_to_voxel_hip", "v2v_events_to_voxel_segmented_hip",
@@ -35,7 +35,9 @@ EXPORTS = ("v2v_version", "v2v_last_error", "v2v_device_count", "v2v_lut_get", "
            "v2v_upsample2x_cat_bwd_nhwc_hip", "v2v_conv1x1_bwd_cout_workspace_bytes", "v2v_conv1x1_bwd_cout_nhwc_hip", "v2v_conv_nhwc_like_hip",
            "v2v_hyper_context_hip", "v2v_hyper_context_conv_hip", "v2v_tanh_bf16_hip", "v2v_hyper_atoms_hip", "v2v_hyper_dynconv_packed_elems", "v2v_hyper_dynconv_pack_weights_hip",
            "v2v_hyper_dynconv_nhwc_hip",
-           "v2v_convgru_packed_bytes", "v2v_convgru_pack_weights_hip", "v2v_convgru_step_hip")
+           "v2v_convgru_packed_bytes", "v2v_convgru_pack_weights_hip", "v2v_convgru_step_hip",
+           "v2v_convgru16_packed_elems", "v2v_convgru16_pack_weights_hip", "v2v_convgru16_step_hip", "v2v_resblock16_packed_elems", "v2v_resblock16_pack_weights_hip",
+           "v2v_resblock16_nhwc_hip", "v2v_conv_head16_packed_elems", "v2v_conv_head16_pack_weights_hip", "v2v_conv_head16_nhwc_hip")
 EV_MAKE_VOXEL_DISCRETE, EV_MAKE_VOXEL_INTERP, EV_BILINEAR = 0, 1, 2
 NORM_NONE, NORM_RADIX, NORM_COUNT = 0, 1, 2
 VOXEL_STATS_WORDS = 516
@@ -231,7 +233,17 @@ def lib():
             # the ConvGRU step (two launches behind one call)
             ("v2v_convgru_packed_bytes", C.c_int, [I64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
             ("v2v_convgru_pack_weights_hip", C.c_int, [P, P, P, I64, P, P, P]),
-            ("v2v_convgru_step_hip", C.c_int, [P] * 7 + [I64] * 4 + [P] * 5 + [C.c_int] * 3 + [P])):
+            ("v2v_convgru_step_hip", C.c_int, [P] * 7 + [I64] * 4 + [P] * 5 + [C.c_int] * 3 + [P]),
+            # the 16-channel layer family (FireNet): one launch per layer
+            ("v2v_convgru16_packed_elems", I64, []),
+            ("v2v_convgru16_pack_weights_hip", C.c_int, [P] * 5),
+            ("v2v_convgru16_step_hip", C.c_int, [P] * 6 + [I64] * 3 + [P] * 3 + [C.c_int, P]),
+            ("v2v_resblock16_packed_elems", I64, []),
+            ("v2v_resblock16_pack_weights_hip", C.c_int, [P] * 4),
+            ("v2v_resblock16_nhwc_hip", C.c_int, [P] * 4 + [I64] * 3 + [P, P]),
+            ("v2v_conv_head16_packed_elems", I64, []),
+            ("v2v_conv_head16_pack_weights_hip", C.c_int, [P, I64, P, P]),
+            ("v2v_conv_head16_nhwc_hip", C.c_int, [P] * 3 + [C.c_int] + [I64] * 3 + [P, P])):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     if L.v2v_version() != ABI_VERSION:

@@ -14,6 +14,8 @@ v2v_upsample2x_nhwc_hip.
     convgru_step / pack_gru_weights                        the ConvGRU step (two launches: gates, candidate) and its packing
     conv1x1_nhwc                                           the 1x1 prediction layer on skip_sum(x, head) (ConvLayer with kernel_size 1)
     conv_head_nhwc / to_nhwc8_bf16 / pack_head_weights     the head (voxel bins -> 32 channels; ConvLayer with <= 8 input channels)
+    convgru16_step / resblock16_nhwc / conv_head16_nhwc    the 16-channel layers (FireNet): ConvGRU(16, 16, 3), ResidualBlock(16, 16) and
+                                                           ConvLayer(<= 8, 16, 3, padding=1), one launch each, any H and W
     conv_stem_nhwc / pack_stem_weights / upsample2x_cat_nhwc   the plain UNet (EVFlowNet): its stem (voxel bins -> 64, 3x3, stride 2) and concat skips
     pack_gate_weights / pack_conv_weights                  one-off weight packing
     nchw_to_nhwc_bf16(x, relu=False)                      layout change in front of them (not needed for channels-last bf16 input)
@@ -28,8 +30,9 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from .nhwc_ops import (_to_nhwc_bf16, conv1x1_nhwc, conv3x3_nhwc, conv_head_nhwc, conv_nhwc, conv_stem_nhwc, convgru_step, convlstm_step, nchw_to_nhwc_bf16,  # noqa: F401
-                       pack_conv3x3_weights, pack_conv_weights, pack_gate_weights, pack_gru_weights, pack_head_weights, pack_stem_weights, packed_weights,
+from .nhwc_ops import (_to_nhwc_bf16, conv1x1_nhwc, conv3x3_nhwc, conv_head16_nhwc, conv_head_nhwc, conv_nhwc, conv_stem_nhwc, convgru16_step, convgru_step,  # noqa: F401
+                       convlstm_step, nchw_to_nhwc_bf16, pack_conv3x3_weights, pack_conv_weights, pack_gate_weights, pack_gru16_weights, pack_gru_weights,
+                       pack_head16_weights, pack_head_weights, pack_resblock16_weights, pack_stem_weights, packed_weights, resblock16_nhwc,
                        to_nhwc8_bf16, upsample2x_cat_nhwc, upsample2x_nhwc)
 from .train import ConvFn, ConvLSTMFn, HeadFn, PredFn, ResidualBlockFn, StemFn, UpCatConvFn, UpConvFn
 
@@ -186,6 +189,7 @@ class ConvGRU(nn.Module):
         self._packed = {}
         self.trainable = False
         self.wants_skip_twin = False                                           # ConvLSTM's training-only switch: nothing to do here
+        self.narrow = hidden_size == 16                                        # FireNet's width: the one-launch step (convgru16_step)
 
     def _weights(self):
         """Everything forward needs packed, now (on the current stream): ((gates stream, candidate stream), gates bias [2C], out bias [C]),
@@ -195,7 +199,8 @@ class ConvGRU(nn.Module):
         hit = self._packed.get("gru")
         if hit is None or hit[0] != key:
             w_u, w_r, w_o, b_u, b_r, b_o = (p.detach() for p in ps)
-            hit = self._packed["gru"] = (key, (pack_gru_weights(w_u, w_r, w_o), torch.cat([b_u, b_r]).float().contiguous(), b_o.float().contiguous()))
+            pack = pack_gru16_weights if self.narrow else pack_gru_weights
+            hit = self._packed["gru"] = (key, (pack(w_u, w_r, w_o), torch.cat([b_u, b_r]).float().contiguous(), b_o.float().contiguous()))
         return hit[1]
 
     def forward(self, input_, prev_state=None, input_relu: bool = False):
@@ -212,6 +217,11 @@ class ConvGRU(nn.Module):
                 h_prev32 = prev_state.detach().permute(0, 2, 3, 1).float().contiguous()
                 h_prev = h_prev32.to(torch.bfloat16)
         packed, b_gates, b_out = self._weights()
+        if self.narrow:
+            outs = convgru16_step(x.contiguous(), h_prev, h_prev32, packed, b_gates, b_out, nchw_dtype=None if nhwc_io else input_.dtype)
+            state = outs[0].permute(0, 3, 1, 2) if nhwc_io else outs[2]
+            state._v2v_gru = (outs[1], outs[0], state._version)
+            return state
         outs = convgru_step(x, h_prev, h_prev32, packed, b_gates, b_out, nchw_dtype=None if nhwc_io else input_.dtype)
         state = outs[0].permute(0, 3, 1, 2) if nhwc_io else outs[4]
         state._v2v_gru = (outs[1], outs[0], state._version)
@@ -236,10 +246,20 @@ class ResidualBlock(nn.Module):
         self.conv1 = nn.Conv2d(in_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=True)
         self.conv2 = nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=True)
         self._packed = {}
+        self.narrow = in_channels == 16                                # FireNet's width: both convolutions in one launch (resblock16_nhwc)
+        if self.narrow and trainable:
+            raise ValueError("ResidualBlock(16, 16) is inference-only: the one-launch 16-channel block has no backward kernel")
         self.trainable = trainable                                     # True: under grad, forward records v2v_amd.train.ResidualBlockFn
 
     def _weights(self):
-        """Everything forward needs packed, now (on the current stream): (conv1's, conv2's) packed streams."""
+        """Everything forward needs packed, now (on the current stream): (conv1's, conv2's) packed streams (16 channels: one stream of both)."""
+        if self.narrow:
+            ws = (self.conv1.weight, self.conv2.weight)
+            key = tuple((p.data_ptr(), p._version, p.device) for p in ws)
+            hit = self._packed.get("both")
+            if hit is None or hit[0] != key:
+                hit = self._packed["both"] = (key, pack_resblock16_weights(*(p.detach() for p in ws)))
+            return hit[1]
         return (packed_weights(self._packed, "conv1", self.conv1.weight, pack_conv_weights),
                 packed_weights(self._packed, "conv2", self.conv2.weight, pack_conv_weights))
 
@@ -247,7 +267,9 @@ class ResidualBlock(nn.Module):
         train = _training(self, x)
         nhwc_io = _is_nhwc_bf16(x)
         xn = _nhwc_in(x, nhwc_io, train)
-        if train:
+        if self.narrow:
+            out = resblock16_nhwc(xn.contiguous(), self._weights(), self.conv1.bias, self.conv2.bias)
+        elif train:
             out = ResidualBlockFn.apply(xn, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias, self)
         else:
             out = ResidualBlockFn.kernels(xn, self)[0]
@@ -262,7 +284,7 @@ class ConvLayer(nn.Module):
     UpsampleConvLayer (:68-96).  Inference by default, trainable=True records its backward under grad; bfloat16 operands, fp32 accumulation; channels-last bfloat16
     inputs are consumed and produced in place, anything else goes through the layout-change kernel and comes back NCHW in the
     input's dtype.  in_channels % 64 == 0 and out_channels in {32, 64, 128, 256k}; in_channels 32 with 64 / 128 outputs (the first
-    encoder); <= 8 input channels with 32 outputs, stride 1 = the head, with 64 outputs, kernel_size 3, stride 2 = the plain UNet's stem;
+    encoder); <= 8 input channels with 32 outputs, stride 1 = the head (with 16 outputs, kernel_size 3 = FireNet's head, any H and W), with 64 outputs, kernel_size 3, stride 2 = the plain UNet's stem;
     kernel_size 1 = the prediction layer; else ValueError (no fallback)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, activation="relu", norm=None, BN_momentum=0.1,
@@ -277,9 +299,12 @@ class ConvLayer(nn.Module):
         # the plain UNet's stem (model/unet.py:320-326): voxel bins -> 64 channels, 3x3, stride 2
         self.stem = in_channels <= 8 and kernel_size == 3 and stride == 2 and out_channels == 64 and not upsample
         self.head = in_channels <= 8 and kernel_size in (3, 5) and not self.stem   # the recurrent UNet's head: voxel bins -> 32 channels
-        if self.head and (out_channels != 32 or stride != 1 or upsample):
+        self.head16 = self.head and kernel_size == 3 and out_channels == 16 and stride == 1 and not upsample   # FireNet's head: voxel bins -> 16
+        if self.head and not self.head16 and (out_channels != 32 or stride != 1 or upsample):
             raise ValueError("with <= 8 input channels the fused ConvLayer is the recurrent UNet's head (32 output channels, stride 1) or the "
                              "plain UNet's stem (64 output channels, kernel_size 3, stride 2)")
+        if self.head16 and trainable:
+            raise ValueError("ConvLayer(<= 8, 16, 3) is inference-only: the 16-channel head has no backward kernel")
         self.force_channels_last = False          # head / stem only: hand out the kernel's NHWC buffer as a channels-last view whatever came in
         self._packed = {}                         # nhwc_ops.packed_weights' cache
         self.trainable = trainable                # True: under grad, forward records a v2v_amd.train Function (ConvFn / UpConvFn / HeadFn / PredFn)
@@ -288,6 +313,8 @@ class ConvLayer(nn.Module):
         """Everything forward needs packed, now (on the current stream): the convolution's packed stream (None for the 1x1 prediction
         layer: its kernel reads the float32 weight)."""
         w = self.conv2d.weight
+        if self.head16:
+            return packed_weights(self._packed, "conv2d", w, pack_head16_weights)
         if self.head or self.stem:
             return packed_weights(self._packed, "conv2d", w, pack_head_weights if self.head else pack_stem_weights)
         return packed_weights(self._packed, "conv2d", w, pack_conv_weights) if w.shape[2] != 1 else None
@@ -326,7 +353,10 @@ class ConvLayer(nn.Module):
             cl = self.force_channels_last or _is_channels_last(x) or _is_channels_last(conv.weight)
             x8 = to_nhwc8_bf16(x.detach().float(), scales)
             fn = HeadFn if self.head else StemFn
-            out = (fn.apply(x8, conv.weight, conv.bias, self) if train else fn.kernels(x8, self)).permute(0, 3, 1, 2)
+            if self.head16:
+                out = conv_head16_nhwc(x8, self._weights(), conv.bias, relu=self.relu).permute(0, 3, 1, 2)
+            else:
+                out = (fn.apply(x8, conv.weight, conv.bias, self) if train else fn.kernels(x8, self)).permute(0, 3, 1, 2)
             out = out if cl else out.contiguous()
             return out if low else out.to(x.dtype)
         if skip_type == "concat":

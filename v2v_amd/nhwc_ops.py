@@ -4,6 +4,8 @@ v2v_amd/train.py builds the torch.autograd.Functions on these, v2v_amd/convlstm.
 
     convlstm_step / conv_nhwc / conv3x3_nhwc / upsample2x_nhwc     the forward operators
     convgru_step / pack_gru_weights                        the ConvGRU step (gates launch + candidate launch) and its packing
+    convgru16_step / resblock16_nhwc / conv_head16_nhwc    the 16-channel layers (FireNet), one launch each; pack_gru16_weights /
+                                                           pack_resblock16_weights / pack_head16_weights
     conv1x1_nhwc                                           the 1x1 prediction layer on skip_sum(x, head)
     conv_head_nhwc / to_nhwc8_bf16 / pack_head_weights     the head (voxel bins -> 32 channels)
     conv_stem_nhwc / pack_stem_weights / upsample2x_cat_nhwc       the plain UNet (EVFlowNet): stride-2 stem (voxel bins -> 64), concat-skip upsampling
@@ -179,6 +181,104 @@ def convgru_step(x, h_prev, h_prev_f32, packed, gates_bias, out_bias, nchw_dtype
                                                    _ptr(out_bias.detach().contiguous()), b, h, w, c, _ptr(u), _ptr(hr), _ptr(h_bf16), _ptr(h_f32),
                                                    _ptr(h_nchw), _DTYPES.get(nchw_dtype, _lib.F32), tile_gates, tile_cand, _lib.stream_ptr()))
     return (h_bf16, h_f32, u, hr) if nchw_dtype is None else (h_bf16, h_f32, u, hr, h_nchw)
+
+
+# ---- the 16-channel layer family (FireNet, model/model.py:264-311; v2v_amd/csrc/v2v_narrow.hpp): one launch per layer, any B, H, W ---------
+def _is_f32_weight(w, shape):
+    return w.is_cuda and w.dtype == torch.float32 and tuple(w.shape) == shape
+
+
+def pack_gru16_weights(update_weight, reset_weight, out_weight):
+    """update_gate.weight, reset_gate.weight, out_gate.weight (float32 [16, 32, 3, 3] each) -> the packed bfloat16 stream of convgru16_step."""
+    _lib.require_gpu()
+    ws = (update_weight, reset_weight, out_weight)
+    if any(not _is_f32_weight(w, (16, 32, 3, 3)) or w.device != update_weight.device for w in ws):
+        raise ValueError("the three gate weights must be float32 CUDA tensors [16, 32, 3, 3] on one device")
+    packed = torch.empty((_lib.lib().v2v_convgru16_packed_elems(),), dtype=torch.bfloat16, device=update_weight.device)
+    with torch.cuda.device(packed.device):
+        _lib.check(_lib.lib().v2v_convgru16_pack_weights_hip(*(_ptr(w.detach().contiguous()) for w in ws), _ptr(packed), _lib.stream_ptr()))
+    return packed
+
+
+def convgru16_step(x, h_prev, h_prev_f32, packed, gates_bias, out_bias, nchw_dtype=None):
+    """One ConvGRU(16, 16, 3) step in ONE launch (gates and candidate through LDS; no u / hr workspaces).  x, h_prev: bfloat16 [B,H,W,16];
+    h_prev_f32: the float32 master of h_prev; both None = zero state.  gates_bias float32 [32] = update | reset, out_bias float32 [16].
+    Returns (h_bf16, h_f32[, h as [B,16,H,W] in nchw_dtype when that is not None]): convgru_step's precision contract."""
+    _lib.require_gpu()
+    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4 or x.shape[3] != 16 or not x.is_contiguous():
+        raise ValueError("x must be a contiguous bfloat16 CUDA tensor [B,H,W,16]")
+    b, h, w, c = x.shape
+    if (h_prev is None) != (h_prev_f32 is None):
+        raise ValueError("h_prev and h_prev_f32 come together (both None: the zero state)")
+    for name, t, dt in (("h_prev", h_prev, torch.bfloat16), ("h_prev_f32", h_prev_f32, torch.float32)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (b, h, w, c) or not t.is_contiguous() or t.device != x.device):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor [B,H,W,16] on x's device")
+    if gates_bias.dtype != torch.float32 or gates_bias.numel() != 32 or out_bias.dtype != torch.float32 or out_bias.numel() != 16 \
+            or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_convgru16_packed_elems():
+        raise ValueError("gates_bias must be float32 [32], out_bias float32 [16] and packed the output of pack_gru16_weights")
+    if nchw_dtype is not None and nchw_dtype not in _DTYPES:
+        raise ValueError("nchw_dtype must be torch.float32, torch.bfloat16 or None")
+    h_bf16 = torch.empty_like(x)
+    h_f32 = torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
+    h_nchw = torch.empty((b, c, h, w), dtype=nchw_dtype, device=x.device) if nchw_dtype is not None else None
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_convgru16_step_hip(_ptr(x), _ptr(h_prev), _ptr(h_prev_f32), _ptr(packed), _ptr(gates_bias.detach().contiguous()),
+                                                     _ptr(out_bias.detach().contiguous()), b, h, w, _ptr(h_bf16), _ptr(h_f32), _ptr(h_nchw),
+                                                     _DTYPES.get(nchw_dtype, _lib.F32), _lib.stream_ptr()))
+    return (h_bf16, h_f32) if nchw_dtype is None else (h_bf16, h_f32, h_nchw)
+
+
+def pack_resblock16_weights(w1, w2):
+    """conv1.weight, conv2.weight (float32 [16, 16, 3, 3] each) -> the packed bfloat16 stream of resblock16_nhwc."""
+    _lib.require_gpu()
+    if not _is_f32_weight(w1, (16, 16, 3, 3)) or not _is_f32_weight(w2, (16, 16, 3, 3)) or w1.device != w2.device:
+        raise ValueError("w1 and w2 must be float32 CUDA tensors [16, 16, 3, 3] on one device")
+    packed = torch.empty((_lib.lib().v2v_resblock16_packed_elems(),), dtype=torch.bfloat16, device=w1.device)
+    with torch.cuda.device(w1.device):
+        _lib.check(_lib.lib().v2v_resblock16_pack_weights_hip(_ptr(w1.detach().contiguous()), _ptr(w2.detach().contiguous()), _ptr(packed), _lib.stream_ptr()))
+    return packed
+
+
+def resblock16_nhwc(x, packed, b1, b2):
+    """out = relu(conv2(relu(conv1(x) + b1)) + b2 + x) on NHWC bfloat16 [B,H,W,16] in ONE launch (ResidualBlock(16, 16), norm=None)."""
+    _lib.require_gpu()
+    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4 or x.shape[3] != 16 or not x.is_contiguous():
+        raise ValueError("x must be a contiguous bfloat16 CUDA tensor [B,H,W,16]")
+    if b1.numel() != 16 or b2.numel() != 16 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_resblock16_packed_elems():
+        raise ValueError("b1 and b2 must be [16] and packed the output of pack_resblock16_weights")
+    b, h, w, _ = x.shape
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().v2v_resblock16_nhwc_hip(_ptr(x), _ptr(packed), _ptr(b1.detach().float().contiguous()), _ptr(b2.detach().float().contiguous()),
+                                                      b, h, w, _ptr(out), _lib.stream_ptr()))
+    return out
+
+
+def pack_head16_weights(weight):
+    """nn.Conv2d(Cin <= 8, 16, 3, padding=1).weight float32 -> the packed bfloat16 stream of conv_head16_nhwc."""
+    _lib.require_gpu()
+    if not weight.is_cuda or weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[0] != 16 or weight.shape[1] > 8 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError("weight must be a float32 CUDA tensor [16, Cin <= 8, 3, 3]")
+    packed = torch.empty((_lib.lib().v2v_conv_head16_packed_elems(),), dtype=torch.bfloat16, device=weight.device)
+    with torch.cuda.device(weight.device):
+        _lib.check(_lib.lib().v2v_conv_head16_pack_weights_hip(_ptr(weight.detach().contiguous()), weight.shape[1], _ptr(packed), _lib.stream_ptr()))
+    return packed
+
+
+def conv_head16_nhwc(x8, packed, bias, relu=True):
+    """out = [relu](conv3x3(x, pad 1) + bias): x8 [B,H,W,8] bfloat16 (to_nhwc8_bf16) -> [B,H,W,16] bfloat16, any H and W; FireNet's head
+    ConvLayer(num_bins, 16, 3, padding=1) (model/model.py:278)."""
+    _lib.require_gpu()
+    if not x8.is_cuda or x8.dtype != torch.bfloat16 or x8.dim() != 4 or x8.shape[3] != 8 or not x8.is_contiguous():
+        raise ValueError("x8 must be a contiguous bfloat16 CUDA tensor [B,H,W,8]")
+    if bias.numel() != 16 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_conv_head16_packed_elems():
+        raise ValueError("bias must be [16] and packed the output of pack_head16_weights")
+    b, h, w, _ = x8.shape
+    out = torch.empty((b, h, w, 16), dtype=torch.bfloat16, device=x8.device)
+    with torch.cuda.device(x8.device):
+        _lib.check(_lib.lib().v2v_conv_head16_nhwc_hip(_ptr(x8), _ptr(packed), _ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w,
+                                                       _ptr(out), _lib.stream_ptr()))
+    return out
 
 
 # ---- the convolutions (ConvLayer / UpsampleConvLayer / ResidualBlock, model/submodules.py:6-96, :143-177) on the same matrix-core kernel ---

@@ -9,6 +9,7 @@ v2v_amd/convlstm.py under the REFERENCE'S OWN module tree, so that a reference c
     RecurrentConvLayer / UpsampleConvLayer model/submodules.py:99-119 / :68-96
 
     FlowNet(unet_kwargs)                   model/model.py:111-139          keys  unetflow.*   (E2VID+: {'image', 'flow'})
+    FireNet(num_bins, base_num_channels, kernel_size, unet_kwargs)   model/model.py:264-311   keys  head / G1 / R1 / G2 / R2 / pred
     UNetFlow(unet_kwargs)                  model/unet.py:133-194           UNetRecurrent's body at prediction width 3
 
 Configuration covered = what config/train_v2v_e2vid_10k.yaml:21-30 / config/test_e2vid++_original.yaml instantiate: skip_type 'sum',
@@ -272,6 +273,44 @@ class UNetFlow(UNetRecurrent):
         return self.split(super().forward(x, event_scales)["image"])
 
 
+def _graphed_sequence(owner, events, event_scales, extra_key, run, get_states, set_states):
+    """The hipGraph capture / replay behind forward_sequence(graph=True) of the recurrent model classes: run(ev, sc) -- reset the states, then
+    the whole sequence on the graph's static input buffers -- is captured ONCE per (shape, dtype, device, extra_key, weights) and replayed
+    from then on; get_states() / set_states(list) read and assign the owner's live state list (the graph's own state tensors are what the
+    last captured step wrote).  One live graph per owner: a new shape or new weights retire the old one and its buffers."""
+    params = list(owner.parameters())
+    key = (tuple(events.shape), events.dtype, events.device, event_scales is not None, extra_key,
+           tuple(p.data_ptr() for p in params), sum(p._version for p in params))
+    cache = owner.__dict__.setdefault("_sequence_graphs", {})
+    entry = cache.get(key)
+    if entry is None:
+        cache.clear()
+        ev = torch.empty_like(events, memory_format=torch.contiguous_format)
+        sc = torch.empty_like(event_scales, memory_format=torch.contiguous_format) if event_scales is not None else None
+        ev.copy_(events)
+        if sc is not None:
+            sc.copy_(event_scales)
+        with torch.no_grad():
+            run(ev, sc)                                         # eager once: weight packing, LDS-size attributes, allocator warm-up
+            torch.cuda.synchronize(events.device)
+            warm = torch.cuda.Stream(device=events.device)
+            warm.wait_stream(torch.cuda.current_stream(events.device))
+            with torch.cuda.stream(warm):
+                run(ev, sc)
+            torch.cuda.current_stream(events.device).wait_stream(warm)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                res = run(ev, sc)
+        entry = cache[key] = (g, ev, sc, res, tuple(get_states()))   # an immutable copy: eager calls between two replays assign into the live list
+    g, ev, sc, res, states = entry
+    ev.copy_(events)
+    if sc is not None:
+        sc.copy_(event_scales)
+    g.replay()
+    set_states(list(states))                                    # the graph's own state tensors: what the last captured step wrote
+    return res
+
+
 class _RecurrentModel(nn.Module):
     """What the reference's recurrent model classes share (model/model.py:194-223, :111-139): the network under its own attribute name
     (`NET`), the states property / reset_states the training loop uses, the sequence call and its hipGraph capture."""
@@ -320,41 +359,10 @@ class _RecurrentModel(nn.Module):
             raise ValueError("graph=True captures inference only: run training steps with graph=False (or under torch.no_grad())")
         if out is not None:
             raise ValueError("graph=True returns the captured graph's own output buffer; `out` is not supported")
-        params = list(self.parameters())
-        key = (tuple(events.shape), events.dtype, events.device, event_scales is not None, overlap,
-               tuple(p.data_ptr() for p in params), sum(p._version for p in params))
-        cache = self.__dict__.setdefault("_sequence_graphs", {})
-        entry = cache.get(key)
-        if entry is None:
-            cache.clear()                                       # one live graph: a new shape or new weights retire the old one and its buffers
-            ev = torch.empty_like(events, memory_format=torch.contiguous_format)
-            sc = torch.empty_like(event_scales, memory_format=torch.contiguous_format) if event_scales is not None else None
-
-            def run():
-                self.reset_states()
-                return self.net.forward_sequence(ev, sc, overlap=overlap)
-            ev.copy_(events)
-            if sc is not None:
-                sc.copy_(event_scales)
-            with torch.no_grad():
-                run()                                           # eager once: weight packing, LDS-size attributes, allocator warm-up
-                torch.cuda.synchronize(events.device)
-                warm = torch.cuda.Stream(device=events.device)
-                warm.wait_stream(torch.cuda.current_stream(events.device))
-                with torch.cuda.stream(warm):
-                    run()
-                torch.cuda.current_stream(events.device).wait_stream(warm)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    res = run()
-            entry = cache[key] = (g, ev, sc, res, tuple(self.net.states))   # an immutable copy: eager calls between two replays
-        g, ev, sc, res, states = entry                                                # assign into the live list (self.states[i] = state)
-        ev.copy_(events)
-        if sc is not None:
-            sc.copy_(event_scales)
-        g.replay()
-        self.net.states = list(states)                          # the graph's own state tensors: what the last captured step wrote
-        return res
+        def run(ev, sc):
+            self.reset_states()
+            return self.net.forward_sequence(ev, sc, overlap=overlap)
+        return _graphed_sequence(self, events, event_scales, overlap, run, lambda: self.net.states, lambda st: setattr(self.net, "states", st))
 
 
 class E2VIDRecurrent(_RecurrentModel):
@@ -373,6 +381,93 @@ class FlowNet(_RecurrentModel):
 
     def forward_sequence(self, events, event_scales=None, out=None, overlap=True, graph=False):
         return UNetFlow.split(super().forward_sequence(events, event_scales, out=out, overlap=overlap, graph=graph))
+
+
+class FireNet(nn.Module):
+    """model/model.py:264-311: the reference's light reconstruction network, head ConvLayer(num_bins -> 16, 3x3, relu), G1 = ConvGRU(16, 16, 3),
+    R1 = ResidualBlock(16, 16), G2, R2, pred = ConvLayer(16 -> 1, 1x1), every layer at full resolution -- on the 16-channel kernels of
+    v2v_amd/csrc/v2v_narrow.hpp (each ConvGRU step and each residual block is ONE launch).  Same constructor (the legacy `unet_kwargs`
+    override included), same module tree: the 24 keys of a reference checkpoint load with strict=True.  Nothing leaves NHWC bfloat16 between
+    head and prediction; the two hidden states are carried in float32 beside their bfloat16 copies (ConvGRU).  Any H and W: there is no
+    stride, so frames run unpadded.  Inference only: base_num_channels != 16, kernel_size != 3 and trainable=True raise."""
+
+    def __init__(self, num_bins=5, base_num_channels=16, kernel_size=3, unet_kwargs={}, trainable: bool = False):
+        super().__init__()
+        if unet_kwargs:                                        # legacy compatibility (model/model.py:272-275)
+            num_bins = unet_kwargs.get("num_bins", num_bins)
+            base_num_channels = unet_kwargs.get("base_num_channels", base_num_channels)
+            kernel_size = unet_kwargs.get("kernel_size", kernel_size)
+        if trainable:
+            raise ValueError("FireNet is inference-only: the ConvGRU step has no backward kernel (trainable=True is not available)")
+        if base_num_channels != 16 or kernel_size != 3 or not 1 <= num_bins <= 8:
+            raise ValueError("the device kernels cover FireNet as the reference builds it: base_num_channels 16, kernel_size 3, num_bins <= 8 "
+                             f"(got {base_num_channels}, {kernel_size}, {num_bins}); there is no stock-layer fallback")
+        self.num_bins = num_bins
+        self.trainable = False
+        c = base_num_channels
+        self.head = ConvLayer(num_bins, c, kernel_size, padding=kernel_size // 2)
+        self.head.force_channels_last = True                   # NHWC from the first layer on, whatever layout the voxel grid arrives in
+        self.G1 = ConvGRU(c, c, kernel_size)
+        self.R1 = ResidualBlock(c, c)
+        self.G2 = ConvGRU(c, c, kernel_size)
+        self.R2 = ResidualBlock(c, c)
+        self.pred = ConvLayer(c, 1, 1, activation=None)
+        self.num_encoders = 0                                  # needed by the reference's image_reconstructor.py
+        self.num_recurrent_units = 2
+        self.reset_states()
+
+    @property
+    def states(self):
+        return copy_states(self._states)
+
+    @states.setter
+    def states(self, states):
+        self._states = states
+
+    def reset_states(self):
+        self._states = [None] * self.num_recurrent_units
+
+    def _head(self, x, event_scales):
+        with torch.autocast("cuda", dtype=torch.bfloat16):      # the head hands out bfloat16 NHWC; every later layer keeps it
+            return self.head(x, scales=event_scales)
+
+    def _body(self, x):
+        """Everything behind the head for one time step (:305-311), on the head's output."""
+        x = self._states[0] = self.G1(x, self._states[0])
+        x = self.R1(x)
+        x = self._states[1] = self.G2(x, self._states[1])
+        x = self.R2(x)
+        return self.pred(x)
+
+    def forward(self, x, event_scales=None):
+        """x: [N, num_bins, H, W] float voxel grid (any layout, any H and W) -> {'image': [N,1,H,W]} in x's dtype (bfloat16 under autocast).
+        event_scales as in UNetRecurrent.forward: normalize_batch_voxel applied by the input staging kernel on the RAW voxel grid."""
+        out_dtype = torch.bfloat16 if (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()) else x.dtype
+        return {"image": self._body(self._head(x, event_scales)).to(out_dtype)}
+
+    def forward_sequence(self, events, event_scales=None, graph=False):
+        """The reference's time loop (`for t in range(T): pred = model(events[:, t])`) as one call: events [N,T,num_bins,H,W] -> images
+        [N,T,1,H,W].  The head does not touch the states: it runs for all T steps in one launch (per image the kernel does the same work
+        whatever the batch is), then the step loop; the result equals the per-step loop bit for bit.  One linear stream: every layer depends
+        on the one before it through the recurrent states, so there is nothing to overlap.
+        graph=True: reset_states(), then the T steps, captured once per (shape, dtype, device, weights) into a hipGraph and replayed from
+        then on (as E2VIDRecurrent.forward_sequence): the returned tensor is the graph's static output (clone it to keep it)."""
+        if events.dim() != 5:
+            raise ValueError("events must be [N, T, num_bins, H, W]")
+        if graph:
+            def run(ev, sc):
+                self.reset_states()
+                return self.forward_sequence(ev, sc)
+            return _graphed_sequence(self, events, event_scales, None, run, lambda: self._states, lambda st: setattr(self, "_states", st))
+        n, t_steps = events.shape[:2]
+        out_dtype = torch.bfloat16 if (events.dtype == torch.bfloat16 or torch.is_autocast_enabled()) else events.dtype
+        out = torch.empty((n, t_steps, 1) + tuple(events.shape[-2:]), dtype=out_dtype, device=events.device)
+        ev_t = events.transpose(0, 1).reshape((t_steps * n,) + tuple(events.shape[2:]))              # t-major: step t = rows t*N .. (t+1)*N
+        sc_t = event_scales.repeat(t_steps, 1) if event_scales is not None else None
+        heads = self._head(ev_t, sc_t)
+        for t in range(t_steps):
+            out[:, t] = self._body(heads[t * n:(t + 1) * n])
+        return out
 
 
 class UNet(nn.Module):

@@ -12,6 +12,7 @@ v2v_amd/train.py builds the torch.autograd.Functions on these, v2v_amd/convlstm.
     pack_gate_weights / pack_conv_weights / pack_dgrad_weights     one-off weight packing; packed_weights = the cache in front of them
     nchw_to_nhwc_bf16(x, relu=False)                      layout change in front of them (not needed for channels-last bf16 input)
     relu_bwd_nhwc / conv_dgrad_nhwc / conv_wgrad_nhwc / upsample2x_bwd_nhwc / upsample2x_cat_bwd_nhwc / conv1x1_bwd_nhwc / convlstm_step_bwd     the backward operators
+                                                          (each pinned against a float64 reference of its own operation: tests/test_backward_ops.py)
 
 Activations are bf16 NHWC with fp32 accumulation; activation gradients bf16 NHWC, the cell-state gradient fp32, parameter gradients fp32.
 """

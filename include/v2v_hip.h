@@ -568,6 +568,38 @@ int v2v_hyper_dynconv_pack_weights_hip(const float *weight, int64_t Cin, int64_t
 int v2v_hyper_dynconv_nhwc_hip(const void *x, const float *atoms, const void *packed, const float *bias, int relu, int64_t B, int64_t H, int64_t W,
                                int64_t Cin, int64_t Cout, int n_atoms, int ks, void *out, void *stream);
 
+/* ---- the image losses of training (utils/loss.py:6-69 temporal consistency; model/loss.py l1_loss, l2_loss), float32 ----------------------
+ * One call serves a list of images (a, b), a < outer, b < inner: image1 / processed1 of image (a, b) start at element a * img_stride_outer +
+ * b * img_stride_inner and are contiguous [c,h,w]; the temporal term exists for b >= tc_first, and image0 / processed0 / flow ([2,h,w],
+ * strides flow_stride_*) are addressed with b - tc_first: their base pointers point at the first image that has a temporal term.  Separate
+ * [N,C,H,W] tensors: outer = N, inner = 1, tc_first = 0.  Steps of a [B,T,C,H,W] tensor: outer = B, inner = T, tc_first = L0, processed0 =
+ * processed1 + (L0 - 1) * img_stride_inner.  The flow is multiplied by flow_sign (the reference's classes pass -flow).
+ *   warp(img)[y,x] = bilinear sample at (x + flow_x, y + flow_y) through grid_sample's normalise / un-normalise roundings, zero outside
+ *   tc = mean_chw( exp(-alpha (image1 - warp(image0))^2) |processed1 - w| / (|processed1| + |w| + 1e-5) ),  w = warp(clamp(processed0, 0, 255))
+ *   l1 = mean_chw |processed1 - image1|,  l2 = mean_chw (processed1 - image1)^2
+ * losses float32 [3][outer*inner] = weight * mean, rows tc, l1, l2; a zero weight skips that loss (row 0), and with w_tc == 0 image0,
+ * processed0 and flow may be NULL.  The four map outputs are optional (NULL), dense [outer*inner,c,h,w], zero where there is no temporal term.
+ * An image's sum does not depend on what else is in the launch.  h, w >= 2, h*w <= 2^22.
+ * v2v_tc_loss_workspace_bytes(outer*inner, c, h, w, backward): bytes of workspace for the forward (0) or the backward / adjoint (1) call. */
+int64_t v2v_tc_loss_workspace_bytes(int64_t n_img, int64_t c, int64_t h, int64_t w, int backward);
+int v2v_tc_loss_fwd_hip(const float *image0, const float *image1, const float *processed0, const float *processed1, const float *flow, int64_t outer,
+                        int64_t inner, int64_t img_stride_outer, int64_t img_stride_inner, int64_t flow_stride_outer, int64_t flow_stride_inner,
+                        int64_t tc_first, int64_t c, int64_t h, int64_t w, float alpha, float flow_sign, float w_tc, float w_l1, float w_l2, float *losses,
+                        float *image0_warped, float *processed0_warped, float *visibility_mask, float *error_map, void *workspace, void *stream);
+/* Gradient of sum(gout * losses), gout float32 [3][outer*inner], to the processed images; frames and flow get none.  dprocessed1 (addressed
+ * like processed1) = the pointwise terms; the temporal term's gradient to processed0 is the bilinear adjoint of d tc / d w, accumulated in
+ * 64-bit fixed point with integer atomics (bitwise reproducible; no float atomics), then clamp-masked.  chain = 0: it goes to dprocessed0
+ * (addressed like processed0).  chain = 1: processed0 of image (a, b) is processed1 of image (a, b - 1), and dprocessed1 of that image
+ * receives it, summed in a fixed order: scatter of the next step + own temporal term + l2 + l1; dprocessed0 is not used. */
+int v2v_tc_loss_bwd_hip(const float *image0, const float *image1, const float *processed0, const float *processed1, const float *flow, int64_t outer,
+                        int64_t inner, int64_t img_stride_outer, int64_t img_stride_inner, int64_t flow_stride_outer, int64_t flow_stride_inner,
+                        int64_t tc_first, int64_t c, int64_t h, int64_t w, float alpha, float flow_sign, float w_tc, float w_l1, float w_l2, const float *gout,
+                        int chain, float *dprocessed1, float *dprocessed0, void *workspace, void *stream);
+/* The warp alone and its adjoint: img / out / dout / din float32 [n,c,h,w] contiguous, flow [n,2,h,w]; the adjoint's workspace is the
+ * backward one of v2v_tc_loss_workspace_bytes. */
+int v2v_warp_bilinear_hip(const float *img, const float *flow, int64_t n, int64_t c, int64_t h, int64_t w, float *out, void *stream);
+int v2v_warp_bilinear_adjoint_hip(const float *dout, const float *flow, int64_t n, int64_t c, int64_t h, int64_t w, float *din, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,237 @@
+"""The image losses of training on the device kernels of v2v_amd/csrc/v2v_loss.hpp: raw operators (one per C entry point), the autograd
+Functions on them, and the functional drop-in for utils/loss.py's temporal_consistency_loss.
+
+    warp_bilinear(img, flow)                        img sampled at (x + flow_x, y + flow_y): F.grid_sample(img, grid(flow), align_corners=True)
+    warp_bilinear_adjoint(dout, flow, hw)           its adjoint (the gradient to img), bitwise reproducible: 64-bit fixed point, integer atomics
+    tc_loss_fwd / tc_loss_bwd                       temporal consistency + l1 + l2 of N image pairs: weighted per-sample means [3, N], gradients
+    seq_loss_fwd / seq_loss_bwd                     the same for all T steps of [B,T,C,H,W] tensors in a fixed number of launches
+    temporal_consistency_loss(...)                  utils/loss.py:6-69, same signature and return values
+    sequence_losses(...)                            {class name: [B,T]} of v2v_amd/losses.py's classes called step by step, in one Function
+
+Everything is float32 (other dtypes are widened), on the GPU; gradients go to the processed images only, frames and flow are data.  Rows of a
+[3, N] loss tensor are temporal consistency, l1, l2; a zero weight skips that loss.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+
+TC, L1, L2 = 0, 1, 2
+MAPS = ("image0_warped_to1", "processed0_warped_to1", "visibility_mask", "error_map")
+
+
+def _ptr(t, offset_elems=0):
+    return C.c_void_p(t.data_ptr() + 4 * offset_elems) if t is not None else None
+
+
+def _f32(name, t, shape=None):
+    """t as a contiguous float32 CUDA tensor (other dtypes are widened); no CPU fallback."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name} must be a CUDA tensor (v2v_amd has no CPU fallback)")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _workspace(n_img, c, h, w, backward, device):
+    n = _lib.lib().v2v_tc_loss_workspace_bytes(n_img, c, h, w, int(backward))
+    _lib.check(min(n, 0))
+    return torch.empty((max(n, 16),), dtype=torch.uint8, device=device)
+
+
+def _weights(weights):
+    w = tuple(float(0.0 if v is None else v) for v in weights)
+    if len(w) != 3:
+        raise ValueError("weights = (temporal consistency, l1, l2)")
+    return w
+
+
+# ---- the warp alone -------------------------------------------------------------------------------------------------------------------
+def warp_bilinear(img: torch.Tensor, flow: torch.Tensor) -> torch.Tensor:
+    """img [N,C,H,W], flow [N,2,H,W] (x, y displacement in pixels) -> img sampled bilinearly at (x + flow_x, y + flow_y), zero outside."""
+    _lib.require_gpu()
+    if img.dim() != 4:
+        raise ValueError("img must be [N,C,H,W]")
+    n, c, h, w = img.shape
+    img, flow = _f32("img", img), _f32("flow", flow, (n, 2, h, w))
+    out = torch.empty_like(img)
+    with torch.cuda.device(img.device):
+        _lib.check(_lib.lib().v2v_warp_bilinear_hip(_ptr(img), _ptr(flow), n, c, h, w, _ptr(out), _lib.stream_ptr()))
+    return out
+
+
+def warp_bilinear_adjoint(dout: torch.Tensor, flow: torch.Tensor, hw=None) -> torch.Tensor:
+    """The gradient of sum(dout * warp_bilinear(img, flow)) to img [N,C,*hw]; the warp keeps the size, so hw must be dout's."""
+    _lib.require_gpu()
+    if dout.dim() != 4:
+        raise ValueError("dout must be [N,C,H,W]")
+    n, c, h, w = dout.shape
+    if hw is not None and tuple(hw) != (h, w):
+        raise ValueError(f"the warp keeps the image size: hw {tuple(hw)} != {(h, w)}")
+    dout, flow = _f32("dout", dout), _f32("flow", flow, (n, 2, h, w))
+    din = torch.empty_like(dout)
+    ws = _workspace(n, c, h, w, True, dout.device)
+    with torch.cuda.device(dout.device):
+        _lib.check(_lib.lib().v2v_warp_bilinear_adjoint_hip(_ptr(dout), _ptr(flow), n, c, h, w, _ptr(din), _ptr(ws), _lib.stream_ptr()))
+    return din
+
+
+# ---- N image pairs --------------------------------------------------------------------------------------------------------------------
+def _pair_inputs(image0, image1, processed0, processed1, flow, weights):
+    if processed1.dim() != 4:
+        raise ValueError("processed1 must be [N,C,H,W]")
+    n, c, h, w = processed1.shape
+    image1, processed1 = _f32("image1", image1, (n, c, h, w)), _f32("processed1", processed1)
+    if weights[TC] != 0.0:
+        image0, processed0 = _f32("image0", image0, (n, c, h, w)), _f32("processed0", processed0, (n, c, h, w))
+        flow = _f32("flow", flow, (n, 2, h, w))
+    else:
+        image0 = processed0 = flow = None
+    return image0, image1, processed0, processed1, flow, (n, c, h, w)
+
+
+def tc_loss_fwd(image0, image1, processed0, processed1, flow, alpha=50.0, weights=(1.0, 0.0, 0.0), flow_sign=1.0, output_images=False):
+    """-> losses float32 [3, N] = weight * per-sample mean (rows temporal consistency, l1, l2); with output_images also the four maps
+    (image0_warped_to1, processed0_warped_to1, visibility_mask, error_map), each [N,C,H,W].  With a zero temporal weight image0, processed0
+    and flow are not read (None is fine)."""
+    _lib.require_gpu()
+    weights = _weights(weights)
+    image0, image1, processed0, processed1, flow, (n, c, h, w) = _pair_inputs(image0, image1, processed0, processed1, flow, weights)
+    dev = processed1.device
+    losses = torch.empty((3, n), dtype=torch.float32, device=dev)
+    maps = tuple(torch.empty((n, c, h, w), dtype=torch.float32, device=dev) for _ in MAPS) if output_images else (None,) * 4
+    ws = _workspace(n, c, h, w, False, dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().v2v_tc_loss_fwd_hip(_ptr(image0), _ptr(image1), _ptr(processed0), _ptr(processed1), _ptr(flow), n, 1, c * h * w, 0, 2 * h * w, 0,
+                                                  0, c, h, w, alpha, flow_sign, *weights, _ptr(losses), *(_ptr(m) for m in maps), _ptr(ws), _lib.stream_ptr()))
+    return (losses, maps) if output_images else losses
+
+
+def tc_loss_bwd(image0, image1, processed0, processed1, flow, gout, alpha=50.0, weights=(1.0, 0.0, 0.0), flow_sign=1.0):
+    """Gradient of sum(gout * losses), gout [3, N] -> (dprocessed0 or None without a temporal term, dprocessed1)."""
+    _lib.require_gpu()
+    weights = _weights(weights)
+    image0, image1, processed0, processed1, flow, (n, c, h, w) = _pair_inputs(image0, image1, processed0, processed1, flow, weights)
+    gout = _f32("gout", gout, (3, n))
+    d1 = torch.empty_like(processed1)
+    d0 = torch.empty_like(processed1) if weights[TC] != 0.0 else None
+    ws = _workspace(n, c, h, w, True, d1.device)
+    with torch.cuda.device(d1.device):
+        _lib.check(_lib.lib().v2v_tc_loss_bwd_hip(_ptr(image0), _ptr(image1), _ptr(processed0), _ptr(processed1), _ptr(flow), n, 1, c * h * w, 0, 2 * h * w, 0,
+                                                  0, c, h, w, alpha, flow_sign, *weights, _ptr(gout), 0, _ptr(d1), _ptr(d0), _ptr(ws), _lib.stream_ptr()))
+    return d0, d1
+
+
+# ---- T steps of a sequence ------------------------------------------------------------------------------------------------------------
+def _seq_inputs(pred, frame, flow, L0, weights):
+    if pred.dim() != 5:
+        raise ValueError("pred must be [B,T,C,H,W]")
+    b, t, c, h, w = pred.shape
+    L0 = int(L0)
+    if L0 < 1:
+        raise ValueError("L0 must be at least 1 (the reference asserts L0 > 0)")
+    pred, frame = _f32("pred", pred), _f32("frame", frame, (b, t, c, h, w))
+    tc = weights[TC] != 0.0 and L0 < t
+    flow = _f32("flow", flow, (b, t, 2, h, w)) if tc else None
+    chw = c * h * w
+    # image0 / processed0 / flow start at the first step that has a temporal term: frame and pred one step earlier, the flow of step L0
+    ptrs = (_ptr(frame, (L0 - 1) * chw) if tc else None, _ptr(frame), _ptr(pred, (L0 - 1) * chw) if tc else None, _ptr(pred),
+            _ptr(flow, L0 * 2 * h * w) if tc else None)
+    layout = (b, t, t * chw, chw, t * 2 * h * w, 2 * h * w, L0, c, h, w)
+    return pred, frame, flow, ptrs, layout
+
+
+def seq_loss_fwd(pred, frame, flow, L0, alpha=50.0, weights=(1.0, 1.0, 0.0)):
+    """pred / frame [B,T,C,H,W], flow [B,T,2,H,W] -> float32 [3, B, T]: what temporal_consistency_loss(weight, L0), l1_loss, l2_loss of
+    v2v_amd/losses.py return step by step with reduce_batch=False (temporal consistency: 0 for t < L0, the flow negated), in two launches."""
+    _lib.require_gpu()
+    weights = _weights(weights)
+    pred, frame, flow, ptrs, layout = _seq_inputs(pred, frame, flow, L0, weights)
+    b, t, c, h, w = pred.shape
+    losses = torch.empty((3, b, t), dtype=torch.float32, device=pred.device)
+    ws = _workspace(b * t, c, h, w, False, pred.device)
+    with torch.cuda.device(pred.device):
+        _lib.check(_lib.lib().v2v_tc_loss_fwd_hip(*ptrs, *layout, alpha, -1.0, *weights, _ptr(losses), None, None, None, None, _ptr(ws), _lib.stream_ptr()))
+    return losses
+
+
+def seq_loss_bwd(pred, frame, flow, L0, gout, alpha=50.0, weights=(1.0, 1.0, 0.0)):
+    """Gradient of sum(gout * seq_loss_fwd(...)), gout [3, B, T], to pred: bit for bit what autograd accumulates into pred when the step
+    loop calls l1_loss, l2_loss, temporal_consistency_loss in that order on pred[:, t]."""
+    _lib.require_gpu()
+    weights = _weights(weights)
+    pred, frame, flow, ptrs, layout = _seq_inputs(pred, frame, flow, L0, weights)
+    b, t, c, h, w = pred.shape
+    gout = _f32("gout", gout, (3, b, t))
+    dpred = torch.empty_like(pred)
+    ws = _workspace(b * t, c, h, w, True, pred.device)
+    with torch.cuda.device(pred.device):
+        _lib.check(_lib.lib().v2v_tc_loss_bwd_hip(*ptrs, *layout, alpha, -1.0, *weights, _ptr(gout), 1, _ptr(dpred), None, _ptr(ws), _lib.stream_ptr()))
+    return dpred
+
+
+# ---- autograd ---------------------------------------------------------------------------------------------------------------------------
+class PairLossFn(torch.autograd.Function):
+    """losses [3, N] (and the four maps, not differentiable) of N image pairs; gradients to processed0 and processed1 only."""
+
+    @staticmethod
+    def forward(ctx, processed0, processed1, image0, image1, flow, alpha, weights, flow_sign, output_images):
+        ctx.save_for_backward(*(t for t in (processed0, processed1, image0, image1, flow) if t is not None))
+        ctx.have = [t is not None for t in (processed0, processed1, image0, image1, flow)]
+        ctx.cfg = (alpha, weights, flow_sign)
+        out = tc_loss_fwd(image0, image1, processed0, processed1, flow, alpha, weights, flow_sign, output_images)
+        if not output_images:
+            return out
+        ctx.mark_non_differentiable(*out[1])
+        return (out[0],) + out[1]
+
+    @staticmethod
+    def backward(ctx, gout, *_):
+        saved = iter(ctx.saved_tensors)
+        processed0, processed1, image0, image1, flow = (next(saved) if h else None for h in ctx.have)
+        alpha, weights, flow_sign = ctx.cfg
+        d0, d1 = tc_loss_bwd(image0, image1, processed0, processed1, flow, gout, alpha, weights, flow_sign)
+        if d0 is not None:
+            d0 = d0.to(processed0.dtype)
+        return d0, d1.to(processed1.dtype), None, None, None, None, None, None, None
+
+
+class SeqLossFn(torch.autograd.Function):
+    """losses [3, B, T] of a whole sequence; gradient to pred only."""
+
+    @staticmethod
+    def forward(ctx, pred, frame, flow, L0, alpha, weights):
+        ctx.save_for_backward(pred, frame, flow)
+        ctx.cfg = (L0, alpha, weights)
+        return seq_loss_fwd(pred, frame, flow, L0, alpha, weights)
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, frame, flow = ctx.saved_tensors
+        L0, alpha, weights = ctx.cfg
+        return seq_loss_bwd(pred, frame, flow, L0, gout, alpha, weights).to(pred.dtype), None, None, None, None, None
+
+
+def temporal_consistency_loss(image0, image1, processed0, processed1, flow01, alpha=50.0, output_images=False, reduce_batch=True):
+    """utils/loss.py:6-69 on the device kernels: the warping error between processed1 and processed0 warped by flow01, weighted by the
+    visibility mask of the frames.  Same signature and return values: a scalar (reduce_batch) or [N], and with output_images also the
+    dict of image0, image1, image0_warped_to1, processed0_warped_to1, visibility_mask, error_map."""
+    out = PairLossFn.apply(processed0, processed1, image0, image1, flow01, float(alpha), (1.0, 0.0, 0.0), 1.0, bool(output_images))
+    per_sample = (out[0] if output_images else out)[TC]
+    loss = per_sample.mean() if reduce_batch else per_sample
+    if not output_images:
+        return loss
+    return loss, dict(image0=image0, image1=image1, **dict(zip(MAPS, out[1:])))
+
+
+def sequence_losses(pred, frame, flow, l1_weight, l2_weight, temporal_consistency_weight, L0, alpha=50.0):
+    """All T steps of ModelInterface.calc_loss's image losses (model/train_utils.py:402-424) at once: pred / frame [B,T,C,H,W], flow
+    [B,T,2,H,W] -> {"l1_loss" / "l2_loss" / "temporal_consistency_loss": [B,T]} for every weight that is not None, bit-identical -- values
+    and the gradient to pred -- to calling the classes of v2v_amd/losses.py step by step with reduce_batch=False."""
+    weights = (temporal_consistency_weight, l1_weight, l2_weight)
+    out = SeqLossFn.apply(pred, frame, flow, int(L0), float(alpha), _weights(weights))
+    names = ("temporal_consistency_loss", "l1_loss", "l2_loss")
+    return {names[k]: out[k] for k in (L1, L2, TC) if weights[k] is not None}

@@ -7,7 +7,7 @@ tests/hyper_stock.py restates layer and network in stock PyTorch and is pinned t
 3e-2 max / 6e-3 rms (tests/test_unet_golden.py's single-layer bar) times max(1, |y|max) as tests/test_convlstm.py scales it; the network
 at every step at most 2.5 x the reference's own CPU bf16-autocast error of that step stored in G26 (the factor tests/test_evflow.py uses
 for the same yardstick); other sizes against hyper_stock in float32 on the same weights with the same network bar.  Each GPU test prints
-its figures before it asserts."""
+its figures before it asserts.  The six kernels one by one, bit-exact at ragged shapes: tests/test_hyper_ops.py."""
 import ctypes as C
 
 import numpy as np

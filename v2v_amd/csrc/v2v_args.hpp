@@ -124,9 +124,6 @@ hipError_t launch_conv_wgrad(const uint16_t *dy, const uint16_t *x1, int C1, con
                              int B, int Hin, int Win, int Ho, int Wo, int Cout, int ks, int stride, hipStream_t s);
 hipError_t launch_relu_mask_stuff(const uint16_t *dy, const uint16_t *y, uint16_t *out, int B, int Ho, int Wo, int C, int stride, hipStream_t s);
 hipError_t launch_dgrad_flip(const float *w, float *wt, int Cout, int Cin, int ks, hipStream_t s);
-hipError_t launch_upsample2x_bwd(const uint16_t *dout, uint16_t *dx, int B, int H, int W, int C, hipStream_t s);
-hipError_t launch_conv1x1_bwd(const float *dy, const uint16_t *x, const uint16_t *skip, const float *w, uint16_t *dx, float *dw, float *db, float *ws,
-                              int64_t M, int C, hipStream_t s);
 int64_t conv1x1_bwd_slabs(int64_t M);
 hipError_t launch_conv_nhwc(const ConvLstmArgs &a, int tile_rows, hipStream_t s, int64_t like_b = 0);   // like_b: batch the automatic tile is chosen for (0: a.B)
 int conv_tile_cols(int Cout);             // columns per tile of the instance launch_conv_nhwc takes for Cout (0: unsupported)

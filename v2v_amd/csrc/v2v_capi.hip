@@ -4,7 +4,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +11,7 @@
 
 #include "../../include/v2v_hip.h"
 #include "v2v_args.hpp"
+#include "v2v_launch.hpp"
 #include "v2v_rng.hpp"
 #include "v2v_events.hpp"
 #include "v2v_frontend.hpp"
@@ -42,20 +42,8 @@ int hip_fail(hipError_t e, const char *what)
 
 bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
-// SIMDs of the current device (4 per CU), cached per device; 1024 when the query fails
-int simd_count()
-{
-    static std::atomic<int> cached[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1024;
-    int v = cached[dev].load(std::memory_order_relaxed);
-    if (!v) {
-        int cus = 0;
-        v = (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) ? 4 * cus : 1024;
-        cached[dev].store(v, std::memory_order_relaxed);       // every thread computes the same value
-    }
-    return v;
-}
+// SIMDs of the current device (4 per CU); 1024 when the query fails
+int simd_count() { return 4 * v2v::device_cus(); }
 
 }  // namespace
 
@@ -1264,9 +1252,9 @@ int v2v_upsample2x_bwd_nhwc_hip(const void *dout, int64_t B, int64_t H, int64_t 
     if (B < 1 || H < 1 || W < 1 || C < 8 || C % 8 != 0 || B * 4 * H * W * C > 0x7FFFFFFFLL)
         return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C %% 8 == 0, tensors below 2^31 elements");
     if (!aligned(dout, 16) || !aligned(dx, 16)) return fail(V2V_ERR_ALIGN, "dout/dx need 16-byte alignment");
-    const hipError_t e = v2v::launch_upsample2x_bwd(static_cast<const uint16_t *>(dout), static_cast<uint16_t *>(dx), (int)B, (int)H, (int)W, (int)C,
-                                                    static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "upsample2x_bwd_kernel launch");
+    const hipError_t e = v2v::launch_upsample2x_cat_bwd(static_cast<const uint16_t *>(dout), static_cast<uint16_t *>(dx), (int)B, (int)H, (int)W, (int)C,
+                                                        0, (int)C, static_cast<hipStream_t>(stream));    // the whole tensor as one slice
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "upsample2x_cat_bwd_kernel launch");
 }
 
 int64_t v2v_conv1x1_bwd_workspace_bytes(int64_t M, int64_t C)
@@ -1283,10 +1271,10 @@ int v2v_conv1x1_bwd_nhwc_hip(const float *dy, const void *x, const void *skip, c
         return fail(V2V_ERR_SHAPE, "need M >= 1 and C a power of two in 8..128 (one output channel)");
     if (!aligned(dy, 4) || !aligned(x, 16) || !aligned(skip, 16) || !aligned(dx, 16) || !aligned(weight, 4) || !aligned(workspace, 4))
         return fail(V2V_ERR_ALIGN, "x/skip/dx need 16-byte alignment, dy/weight/workspace 4-byte");
-    const hipError_t e = v2v::launch_conv1x1_bwd(dy, static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(skip),
-                                                 weight, static_cast<uint16_t *>(dx), dw, db, static_cast<float *>(workspace), M, (int)C,
-                                                 static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv1x1_bwd_kernel launch");
+    const hipError_t e = v2v::launch_conv1x1_bwd_cout(dy, static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(skip), weight,
+                                                      static_cast<uint16_t *>(dx), dw, db, static_cast<float *>(workspace), M, (int)C, 1,
+                                                      static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv1x1_bwd_cout_kernel launch");
 }
 
 // ---- the plain UNet (EVFlowNet): stem, concat-skip upsampling and its adjoint, the prediction backward for 1..3 outputs ----------------

@@ -1,40 +1,9 @@
 // v2v_convgru_tu.hip -- translation unit of the ConvGRU step: the EPI = 3 (gates) and EPI = 4 (candidate) instances of convlstm_step_kernel
 // and their launchers.  Kernel main loop in v2v_convlstm.hpp, epilogues / packing / layouts in v2v_convgru.hpp.
-#include <atomic>
-
 #include "v2v_convgru.hpp"
 #include "v2v_args.hpp"
 
 namespace v2v {
-
-namespace {
-template <int MF, int WM, int STAGES, int EPI, int WN, int NF, int KS = 1>
-hipError_t launch_gru_t(const ConvLstmArgs &a, hipStream_t s)
-{
-    // dynamic LDS above the default 64 KB: the limit is raised once per device, outside the launch path (a step captures as bare kernel nodes)
-    constexpr int kBN = WN * NF * 32, lds = KS * cl_lds_bytes(MF, WM, STAGES, kBN);
-    static std::atomic<bool> raised[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (dev < 0 || dev >= 64 || !raised[dev].load(std::memory_order_acquire)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&convlstm_step_kernel<MF, WM, STAGES, EPI, WN, NF, 1, KS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_release);
-    }
-    // ceil: the last pixel tile may be partial (rows past B*H*W read the zero line and are not stored)
-    const int64_t col_tiles = EPI == 3 ? 2 * a.C / kBN : a.C / kBN;
-    const int64_t tiles = (((int64_t)a.B * a.H * a.W + 32 * MF * WM - 1) / (32 * MF * WM)) * col_tiles;
-    hipLaunchKernelGGL((convlstm_step_kernel<MF, WM, STAGES, EPI, WN, NF, 1, KS>), dim3((unsigned)tiles), dim3(64 * WM * WN * KS), lds, s, a);
-    return hipGetLastError();
-}
-
-int device_cus()
-{
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return cus;
-}
-}  // namespace
 
 // Instance codes (v2v_convgru_step_hip's tile_gates / tile_cand; 0 = auto).  Pixels x columns per workgroup:
 //   gates      1: 64 x 128    2: 128 x 128 (three stages)    3: 128 x 256 (three stages)    4: 256 x 256    5: 64 x 256 as two K groups
@@ -67,11 +36,11 @@ hipError_t launch_convgru_gates(const ConvLstmArgs &a0, int tile, hipStream_t s)
         tile = (wide && m / 256 * ctw >= cus) ? 4 : (wide && m / 128 * ctw >= cus) ? 3 : 1;
     }
     switch (tile) {
-    case 1: return launch_gru_t<1, 2, 2, 3, 2, 2>(a, s);
-    case 2: return launch_gru_t<1, 4, 3, 3, 2, 2>(a, s);
-    case 3: return launch_gru_t<1, 4, 3, 3, 2, 4>(a, s);
-    case 4: return launch_gru_t<1, 8, 2, 3, 2, 4>(a, s);
-    case 5: return launch_gru_t<1, 2, 2, 3, 2, 4, 2>(a, s);
+    case 1: return launch_step_t<1, 2, 2, 3, 2, 2>(a, s);
+    case 2: return launch_step_t<1, 4, 3, 3, 2, 2>(a, s);
+    case 3: return launch_step_t<1, 4, 3, 3, 2, 4>(a, s);
+    case 4: return launch_step_t<1, 8, 2, 3, 2, 4>(a, s);
+    case 5: return launch_step_t<1, 2, 2, 3, 2, 4, 1, 2>(a, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -89,11 +58,11 @@ hipError_t launch_convgru_candidate(const ConvLstmArgs &a0, int tile, hipStream_
         else tile = 1;
     }
     switch (tile) {
-    case 1: return launch_gru_t<1, 4, 3, 4, 1, 2>(a, s);
-    case 2: return launch_gru_t<1, 4, 2, 4, 1, 4, 2>(a, s);
-    case 3: return launch_gru_t<1, 4, 3, 4, 2, 4>(a, s);
-    case 4: return launch_gru_t<1, 8, 2, 4, 2, 4>(a, s);
-    case 5: return launch_gru_t<1, 2, 3, 4, 2, 2, 2>(a, s);
+    case 1: return launch_step_t<1, 4, 3, 4, 1, 2>(a, s);
+    case 2: return launch_step_t<1, 4, 2, 4, 1, 4, 1, 2>(a, s);
+    case 3: return launch_step_t<1, 4, 3, 4, 2, 4>(a, s);
+    case 4: return launch_step_t<1, 8, 2, 4, 2, 4>(a, s);
+    case 5: return launch_step_t<1, 2, 3, 4, 2, 2, 1, 2>(a, s);
     default: return hipErrorInvalidValue;
     }
 }

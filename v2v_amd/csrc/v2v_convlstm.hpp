@@ -36,6 +36,7 @@
 #include <stdint.h>
 
 #include "v2v_args.hpp"
+#include "v2v_launch.hpp"
 
 namespace v2v {
 
@@ -433,6 +434,24 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, KS == 2 || WM * WN == 16 ? 
     }
 }
 
+// Host side: one instance of the kernel above on its grid.  Columns of the job: 4 C gate columns for the step and its backward (EPI 0 / 2),
+// n_cols for the plain convolution (EPI 1), 2 C for the ConvGRU's gates (EPI 3), C for its candidate (EPI 4); one workgroup per tile of
+// 32 MF WM pixels x 32 WN NF columns.
+template <int MF, int WM, int STAGES = 2, int EPI = 0, int WN = 2, int NF = 4, int TPC = 1, int KS = 1>
+hipError_t launch_step_t(const ConvLstmArgs &a, hipStream_t s)
+{
+    static_assert((EPI != 0 && EPI != 2) || NF == 4, "the step's tiles hold all four gates of their hidden channels: 4 column fragments per wave");
+    constexpr int lds = KS * cl_lds_bytes(MF, WM, STAGES, WN * NF * 32);       // 48-160 KB
+    static std::atomic<bool> raised[64];
+    const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(&convlstm_step_kernel<MF, WM, STAGES, EPI, WN, NF, TPC, KS>), lds, raised);
+    if (e != hipSuccess) return e;
+    const int64_t cols = EPI == 1 ? a.n_cols : EPI == 3 ? 2 * a.C : EPI == 4 ? a.C : 4 * a.C;
+    // ceil: the last pixel tile may be partial (rows past B*H*W read the zero line and are not stored)
+    const int64_t tiles = (((int64_t)a.B * a.H * a.W + 32 * MF * WM - 1) / (32 * MF * WM)) * (cols / (WN * NF * 32));
+    hipLaunchKernelGGL((convlstm_step_kernel<MF, WM, STAGES, EPI, WN, NF, TPC, KS>), dim3((unsigned)tiles), dim3(64 * WM * WN * KS), lds, s, a);
+    return hipGetLastError();
+}
+
 #ifndef V2V_CL_STEP_ONLY
 // fp32 or bf16 NCHW -> bf16 NHWC (optionally through a ReLU): the layout change between the stock convolution upstream and the
 // fused step.  One workgroup moves 64 pixels x 64 channels through LDS so that both sides are full-line accesses.
@@ -477,14 +496,16 @@ __device__ __forceinline__ void cl_unpack8(const uint4 v, float (&f)[8])
     for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(w[i] << 16); f[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u); }
 }
 
-// One work-item walks `rs` consecutive input rows of one (image, column, 8-channel group): it keeps the horizontally filtered
-// rows iy - 1, iy, iy + 1 (left / right output column) in registers and loads only row iy + 1 per step -- 3 (+3 skip) 16-byte
+// One work-item walks `rs` consecutive input rows of one (image, column, 8-channel group of the OUTPUT): it keeps the horizontally
+// filtered rows iy - 1, iy, iy + 1 (left / right output column) in registers and loads only row iy + 1 per step -- 3 (+3 skip) 16-byte
 // loads per input pixel instead of 9 (+9) when every pixel gathers its own 3 x 3 neighbourhood.  Same expressions in the
 // same order as before (horizontal 0.25 / 0.75 first, then vertical), so the output is bit-identical for any rs.
+// `load(c8, pixel, v)` gives the 8 channels of group c8 at input pixel (b * H + y) * W + x; C is the OUTPUT's pixel pitch.
 // (Round 5: with packed float32 instructions -- the compiler's SLP pass had paired these blends into v_pk_mul_f32 / v_pk_add_f32 -- this
 // kernel returned wrong values in lanes 48-63 whenever a matrix-core kernel of another stream shared its CU; the whole library is now
 // built without packed float32 instructions, see the Makefile.)
-__global__ void __launch_bounds__(256) upsample2x_nhwc_bf16_kernel(const uint16_t *x, const uint16_t *skip, uint16_t *out, int B, int H, int W, int C, int rs)
+template <typename LOAD>
+__device__ __forceinline__ void cl_upsample2x_walk(const LOAD load, uint16_t *out, int C, int B, int H, int W, int rs)
 {
     const uint32_t c8n = (uint32_t)C >> 3, segs = (uint32_t)(H + rs - 1) / (uint32_t)rs;
     const uint32_t n = (uint32_t)B * segs * (uint32_t)W * c8n;   // < 2^31: checked by the launcher (32-bit divisions below)
@@ -500,20 +521,7 @@ __global__ void __launch_bounds__(256) upsample2x_nhwc_bf16_kernel(const uint16_
     auto hrow = [&](int y, float (&l)[8], float (&rr)[8]) __attribute__((always_inline)) {
         float v[3][8];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int64_t o = (((int64_t)b * H + y) * W + xs[k]) * C + c8 * 8;
-            cl_unpack8(*reinterpret_cast<const uint4 *>(x + o), v[k]);
-            if (skip) {
-                float sk[8];
-                cl_unpack8(*reinterpret_cast<const uint4 *>(skip + o), sk);
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) {
-                    const uint32_t pk = cl_pack_bf16(v[k][e] + sk[e], v[k][e + 1] + sk[e + 1]);
-                    v[k][e] = __uint_as_float(pk << 16);
-                    v[k][e + 1] = __uint_as_float(pk & 0xFFFF0000u);
-                }
-            }
-        }
+        for (int k = 0; k < 3; ++k) load(c8, ((int64_t)b * H + y) * W + xs[k], v[k]);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float mid = 0.75f * v[1][e];
@@ -543,6 +551,32 @@ __global__ void __launch_bounds__(256) upsample2x_nhwc_bf16_kernel(const uint16_
 #pragma unroll
         for (int e = 0; e < 8; ++e) { L[0][e] = L[1][e]; R[0][e] = R[1][e]; L[1][e] = L[2][e]; R[1][e] = R[2][e]; }
     }
+}
+
+// the sum skip: bf16(x + skip), one rounding (skip null: x alone); both tensors at the output's pixel pitch C
+struct cl_up_sum_skip {
+    const uint16_t *x, *skip;
+    int C;
+    __device__ __forceinline__ void operator()(int c8, int64_t pix, float (&v)[8]) const
+    {
+        const int64_t o = pix * C + c8 * 8;
+        cl_unpack8(*reinterpret_cast<const uint4 *>(x + o), v);
+        if (skip) {
+            float sk[8];
+            cl_unpack8(*reinterpret_cast<const uint4 *>(skip + o), sk);
+#pragma unroll
+            for (int e = 0; e < 8; e += 2) {
+                const uint32_t pk = cl_pack_bf16(v[e] + sk[e], v[e + 1] + sk[e + 1]);
+                v[e] = __uint_as_float(pk << 16);
+                v[e + 1] = __uint_as_float(pk & 0xFFFF0000u);
+            }
+        }
+    }
+};
+
+__global__ void __launch_bounds__(256) upsample2x_nhwc_bf16_kernel(const uint16_t *x, const uint16_t *skip, uint16_t *out, int B, int H, int W, int C, int rs)
+{
+    cl_upsample2x_walk(cl_up_sum_skip{x, skip, C}, out, C, B, H, W, rs);
 }
 
 // ---- stride-1 convolutions with few output channels (the decoders: 5x5, 32 / 64 / 128 columns): HALO tiles ------------------
@@ -978,59 +1012,22 @@ __global__ void __launch_bounds__(256) conv_stem_pack_kernel(const float *w, uin
 // ---- the concat skip in front of a decoder: out[B,2H,2W,C1+C2] = cat(up2(x), up2(skip)) along the channels, which IS
 // f.interpolate(cat(x, skip), scale_factor=2, mode='bilinear', align_corners=False) (skip_concat, model/model_util.py:10, at
 // model/unet.py:350): bilinear interpolation works per channel, so each source is interpolated straight into its channel slice and no
-// low-resolution cat tensor exists.  upsample2x_nhwc_bf16_kernel's work-item (same expressions in the same order: horizontal 0.25 / 0.75,
-// then vertical, fp32, one bf16 rounding; `rs` input rows walked, each loaded once) over the (C1 + C2) / 8 channel groups of the OUTPUT:
-// group c8 reads x (pixel pitch C1) when 8 c8 < C1, else skip (pitch C2) at channel 8 c8 - C1, and writes at pixel pitch C1 + C2.
+// low-resolution cat tensor exists.  cl_upsample2x_walk over the (C1 + C2) / 8 channel groups of the OUTPUT: group c8 reads x (pixel
+// pitch C1) when 8 c8 < C1, else skip (pitch C2) at channel 8 c8 - C1, and writes at pixel pitch C1 + C2.
+struct cl_up_cat {
+    const uint16_t *x, *skip;
+    int C1, C2;
+    __device__ __forceinline__ void operator()(int c8, int64_t pix, float (&v)[8]) const
+    {
+        const bool first = c8 * 8 < C1;
+        const uint16_t *const src = first ? x + c8 * 8 : skip + (c8 * 8 - C1);
+        cl_unpack8(*reinterpret_cast<const uint4 *>(src + pix * (first ? C1 : C2)), v);
+    }
+};
+
 __global__ void __launch_bounds__(256) upsample2x_cat_nhwc_bf16_kernel(const uint16_t *x, int C1, const uint16_t *skip, int C2, uint16_t *out, int B, int H, int W, int rs)
 {
-    const int C = C1 + C2;
-    const uint32_t c8n = (uint32_t)C >> 3, segs = (uint32_t)(H + rs - 1) / (uint32_t)rs;
-    const uint32_t n = (uint32_t)B * segs * (uint32_t)W * c8n;   // < 2^31: checked by the launcher (32-bit divisions below)
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    uint32_t r = i / c8n;
-    const int c8 = (int)(i - r * c8n);
-    const uint32_t r2 = r / (uint32_t)W;
-    const int ix = (int)(r - r2 * (uint32_t)W);
-    const int b = (int)(r2 / segs), seg = (int)(r2 - (uint32_t)b * segs);
-    const bool first = c8 * 8 < C1;
-    const uint16_t *const src = first ? x + c8 * 8 : skip + (c8 * 8 - C1);
-    const int cs = first ? C1 : C2;                               // the source's pixel pitch
-    const int xs[3] = {ix > 0 ? ix - 1 : 0, ix, ix < W - 1 ? ix + 1 : ix};
-    float L[3][8], R[3][8];                                       // rows iy - 1, iy, iy + 1: the left (2 ix) and right (2 ix + 1) output column
-    auto hrow = [&](int y, float (&l)[8], float (&rr)[8]) __attribute__((always_inline)) {
-        float v[3][8];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) cl_unpack8(*reinterpret_cast<const uint4 *>(src + (((int64_t)b * H + y) * W + xs[k]) * cs), v[k]);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float mid = 0.75f * v[1][e];
-            l[e] = 0.25f * v[0][e] + mid;
-            rr[e] = mid + 0.25f * v[2][e];
-        }
-    };
-    auto put = [&](int oy, int ox, const float (&top)[8], float wt, const float (&bot)[8], float wb) __attribute__((always_inline)) {
-        uint32_t w[4];
-#pragma unroll
-        for (int e = 0; e < 8; e += 2) w[e >> 1] = cl_pack_bf16(wt * top[e] + wb * bot[e], wt * top[e + 1] + wb * bot[e + 1]);
-        *reinterpret_cast<uint4 *>(out + ((((int64_t)b * 2 * H + oy) * 2 * W + ox) * C + c8 * 8)) = make_uint4(w[0], w[1], w[2], w[3]);
-    };
-    const int y0 = seg * rs, y1 = min(y0 + rs, H);
-    hrow(y0 > 0 ? y0 - 1 : 0, L[0], R[0]);
-    hrow(y0, L[1], R[1]);
-    for (int iy = y0; iy < y1; ++iy) {
-        if (iy < H - 1) hrow(iy + 1, L[2], R[2]);
-        else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { L[2][e] = L[1][e]; R[2][e] = R[1][e]; }
-        }
-        put(2 * iy, 2 * ix, L[0], 0.25f, L[1], 0.75f);
-        put(2 * iy, 2 * ix + 1, R[0], 0.25f, R[1], 0.75f);
-        put(2 * iy + 1, 2 * ix, L[1], 0.75f, L[2], 0.25f);
-        put(2 * iy + 1, 2 * ix + 1, R[1], 0.75f, R[2], 0.25f);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { L[0][e] = L[1][e]; R[0][e] = R[1][e]; L[1][e] = L[2][e]; R[1][e] = R[2][e]; }
-    }
+    cl_upsample2x_walk(cl_up_cat{x, skip, C1, C2}, out, C1 + C2, B, H, W, rs);
 }
 
 #endif  // V2V_CL_STEP_ONLY

@@ -1,32 +1,8 @@
 // v2v_convlstm_tu.hip -- translation unit of the fused ConvLSTM step: launchers.
-#include <atomic>
-
 #include "v2v_convlstm.hpp"
 #include "v2v_args.hpp"
 
 namespace v2v {
-
-namespace {
-template <int MF, int WM, int STAGES = 2, int EPI = 0, int WN = 2, int NF = 4, int TPC = 1, int KS = 1>
-hipError_t launch_step_t(const ConvLstmArgs &a, hipStream_t s)
-{
-    // 80-128 KB of dynamic LDS is above the 64 KB a kernel gets by default: raise the limit once per device (kept out of the
-    // launch path so that a step captures into a hipGraph as a bare kernel node)
-    constexpr int lds = KS * cl_lds_bytes(MF, WM, STAGES, WN * NF * 32);
-    static std::atomic<bool> raised[64];              // idempotent attribute call: a benign repeat, but no data race
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (dev < 0 || dev >= 64 || !raised[dev].load(std::memory_order_acquire)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&convlstm_step_kernel<MF, WM, STAGES, EPI, WN, NF, TPC, KS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_release);
-    }
-    // ceil: the last pixel tile may be partial (rows past B*H*W read the zero line and are not stored)
-    const int64_t tiles = (((int64_t)a.B * a.H * a.W + 32 * MF * WM - 1) / (32 * MF * WM)) * (EPI != 1 ? a.C / (WN * 32) : a.n_cols / (WN * NF * 32));
-    hipLaunchKernelGGL((convlstm_step_kernel<MF, WM, STAGES, EPI, WN, NF, TPC, KS>), dim3((unsigned)tiles), dim3(64 * WM * WN * KS), lds, s, a);
-    return hipGetLastError();
-}
-}  // namespace
 
 // tile_rows: pixels per workgroup tile (64, 128 or 256); 0 = auto: the largest tile that still gives every CU a workgroup.
 // Same box, 8 clips (ms per step; tools/ab_convlstm.sh):        64 px    128 px   256 px
@@ -35,8 +11,7 @@ hipError_t launch_step_t(const ConvLstmArgs &a, hipStream_t s)
 hipError_t launch_convlstm_step(const ConvLstmArgs &a, int tile_rows, hipStream_t s)
 {
     if (tile_rows == 0) {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        const int cus = device_cus();
         const int64_t m = (int64_t)a.B * a.H * a.W, ct = a.C / kClCh;
         tile_rows = (m / 256 * ct >= cus) ? 256 : (m / 128 * ct >= cus) ? 128 : 64;      // (a partial last tile is fine: any B*H*W)
         // when even 64-pixel tiles give a CU at most one workgroup: that workgroup as two K groups (KS = 2; same box, 8 clips:
@@ -65,8 +40,7 @@ int conv_tile_cols(int Cout) { return Cout % 256 == 0 ? 256 : (Cout == 128 || Co
 hipError_t launch_conv_nhwc(const ConvLstmArgs &a, int tile_rows, hipStream_t s, int64_t like_b)
 {
     const int64_t m = (like_b > 0 ? like_b : (int64_t)a.B) * a.H * a.W;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = device_cus();
     // halo tiles (conv_halo_kernel): the 16 x 16 patch with its halo staged once per 64-channel chunk.  One patch buffer + two
     // weight-group buffers must leave room for TWO workgroups per CU (<= 80 KB): 8 clips of 256^2, same box, 5x5: 64 -> 32
     // columns 0.117 -> 0.085 ms (3 taps per group), 128 -> 64 columns 0.079 -> 0.071 ms (1 tap); 256 -> 128 columns does not fit
@@ -81,13 +55,9 @@ hipError_t launch_conv_nhwc(const ConvLstmArgs &a, int tile_rows, hipStream_t s,
         const int tps = halo_tps < a.ks ? halo_tps : a.ks;
         const int lds = halo_a + 2 * tps * a.n_cols * 128;
         const void *fn = nf == 4 ? (const void *)&conv_halo_kernel<4> : nf == 2 ? (const void *)&conv_halo_kernel<2> : (const void *)&conv_halo_kernel<1>;
-        static std::atomic<bool> raised[3][64];                              // once per instance and device (not in a captured launch path)
-        const int inst = nf == 4 ? 2 : nf - 1;
-        if (dev < 0 || dev >= 64 || !raised[inst][dev].load(std::memory_order_acquire)) {
-            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            if (dev >= 0 && dev < 64) raised[inst][dev].store(true, std::memory_order_release);
-        }
+        static std::atomic<bool> raised[3][64];                              // once per instance and device
+        const hipError_t e = ensure_dynamic_lds(fn, 160 * 1024, raised[nf == 4 ? 2 : nf - 1]);
+        if (e != hipSuccess) return e;
         const unsigned tiles = (unsigned)(a.B * (a.H / 16) * (a.W / 16));
         if (nf == 4) hipLaunchKernelGGL(conv_halo_kernel<4>, dim3(tiles), dim3(256), lds, s, a, tps);
         else if (nf == 2) hipLaunchKernelGGL(conv_halo_kernel<2>, dim3(tiles), dim3(256), lds, s, a, tps);
@@ -213,32 +183,37 @@ hipError_t launch_conv_stem_pack(const float *w, uint16_t *wp, int Cin, hipStrea
     return hipGetLastError();
 }
 
+namespace {
+// one work-item per (image, segment of rs rows, column, 8 output channels).  8 clips, same box, us per launch (events) for
+// rs = 1 / 2 / 4 / 8: 256 ch @32^2 17.1 / 18.0 / 17.9 / 23.8, 128 ch @64^2 23.0 / 20.7 / 20.0 / 22.6, 64 ch @128^2
+// 38.1 / 30.0 / 25.6 / 30.8 -> 4 rows where that leaves >= 2048 waves, else 1 (tools/upsample_time.py).  The values do not depend
+// on rs.  rs_forced > 0 takes that segment length instead.  Returns the work-items, or -1 when they do not fit the kernel's 32-bit index.
+int64_t upsample2x_work(int B, int H, int W, int C, int rs_forced, int &rs)
+{
+    const int64_t cols = (int64_t)B * W * (C / 8);
+    rs = rs_forced > 0 ? rs_forced : cols * ((H + 3) / 4) < 2048 * 64 ? 1 : 4;
+    const int64_t n = cols * ((H + rs - 1) / rs);
+    return n < (int64_t)1 << 31 ? n : -1;
+}
+}  // namespace
+
 hipError_t launch_upsample2x_cat_nhwc(const uint16_t *x, int C1, const uint16_t *skip, int C2, uint16_t *out, int B, int H, int W, hipStream_t s)
 {
-    // launch_upsample2x_nhwc's work split over the C1 + C2 output channels (same rs rule; the values do not depend on rs)
-    const int64_t cols = (int64_t)B * W * ((C1 + C2) / 8);
-    int rs = 4;
-    if (cols * ((H + rs - 1) / rs) < 2048 * 64) rs = 1;
-    const int64_t n = cols * ((H + rs - 1) / rs);
-    if (n >= (int64_t)1 << 31) return hipErrorInvalidValue;
+    int rs;
+    const int64_t n = upsample2x_work(B, H, W, C1 + C2, 0, rs);
+    if (n < 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(upsample2x_cat_nhwc_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, C1, skip, C2, out, B, H, W, rs);
     return hipGetLastError();
 }
 
 hipError_t launch_upsample2x_nhwc(const uint16_t *x, const uint16_t *skip, uint16_t *out, int B, int H, int W, int C, hipStream_t s)
 {
-    // one work-item per (image, segment of rs rows, column, 8 channels).  8 clips, same box, us per launch (events) for
-    // rs = 1 / 2 / 4 / 8: 256 ch @32^2 17.1 / 18.0 / 17.9 / 23.8, 128 ch @64^2 23.0 / 20.7 / 20.0 / 22.6, 64 ch @128^2
-    // 38.1 / 30.0 / 25.6 / 30.8 -> 4 rows where that leaves >= 2048 waves, else 1 (tools/upsample_time.py)
-    const int64_t cols = (int64_t)B * W * (C / 8);
-    int rs = 4;
+    int rs, forced = 0;
 #ifdef V2V_TUNING_KNOBS                                                           // tuning builds only (tools/upsample_time.py): never in the product launch path
-    if (const char *e = getenv("V2V_UP_RS")) rs = atoi(e) > 0 ? atoi(e) : rs;
-    else
+    if (const char *e = getenv("V2V_UP_RS")) forced = atoi(e) > 0 ? atoi(e) : 4;
 #endif
-    if (cols * ((H + rs - 1) / rs) < 2048 * 64) rs = 1;
-    const int64_t n = cols * ((H + rs - 1) / rs);
-    if (n >= (int64_t)1 << 31) return hipErrorInvalidValue;
+    const int64_t n = upsample2x_work(B, H, W, C, forced, rs);
+    if (n < 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(upsample2x_nhwc_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, skip, out, B, H, W, C, rs);
     return hipGetLastError();
 }

@@ -1,8 +1,7 @@
 // v2v_hyper_tu.hip -- translation unit of HyperE2VID's dynamic decoder (v2v_hyper.hpp): launchers.
-#include <atomic>
-
 #define V2V_HYPER_KERNELS
 #include "v2v_hyper.hpp"
+#include "v2v_launch.hpp"
 
 namespace v2v {
 
@@ -42,16 +41,9 @@ hipError_t launch_hyper_dynconv_pack(const float *w, uint16_t *wp, hipStream_t s
 hipError_t launch_hyper_dynconv(const uint16_t *x, const float *atoms, const uint16_t *wp, const float *bias, uint16_t *out, int B, int H, int W, int relu,
                                 hipStream_t s)
 {
-    // 147 KB of dynamic LDS is above the 64 KB a kernel gets by default: raise the limit once per device (kept out of the launch path so
-    // that the layer captures into a hipGraph as a bare kernel node)
-    static std::atomic<bool> raised[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (dev < 0 || dev >= 64 || !raised[dev].load(std::memory_order_acquire)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&hyper_dynconv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kHyLdsBytes);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_release);
-    }
+    static std::atomic<bool> raised[64];                                          // 147 KB of dynamic LDS
+    const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(&hyper_dynconv_kernel), kHyLdsBytes, raised);
+    if (e != hipSuccess) return e;
     const int64_t tiles = (int64_t)B * ((H + kHyTH - 1) / kHyTH) * ((W + kHyTW - 1) / kHyTW);
     hipLaunchKernelGGL(hyper_dynconv_kernel, dim3((unsigned)tiles), dim3(512), kHyLdsBytes, s, x, atoms, wp, bias, out, B, H, W, relu);
     return hipGetLastError();

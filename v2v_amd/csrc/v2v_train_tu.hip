@@ -3,8 +3,8 @@
 // Kernels in this file:  conv_wgrad_kernel + wgrad_reduce_kernel (weight / bias gradient of every convolution: K = the pixels, split
 // into slabs, fixed-order sum) | relu_mask_stuff_kernel (ReLU backward from the saved post-ReLU output, optionally spread onto the
 // stride-2 input grid) | dgrad_flip_kernel (weights flipped and transposed: the data gradient of a convolution is a convolution that
-// runs on the forward kernels) | upsample2x_bwd_kernel (adjoint of the x2 bilinear upsampling) | conv1x1_bwd_kernel +
-// conv1x1_bwd_reduce_kernel (the prediction layer).  The ConvLSTM step's backward is an epilogue of convlstm_step_kernel (EPI = 2,
+// runs on the forward kernels) | upsample2x_cat_bwd_kernel (adjoint of the x2 bilinear upsampling, whole tensor or one channel slice) |
+// conv1x1_bwd_cout_kernel + conv1x1_bwd_cout_reduce_kernel (the prediction layer, 1..3 outputs).  The ConvLSTM step's backward is an epilogue of convlstm_step_kernel (EPI = 2,
 // v2v_convlstm.hpp).  Numerics: bf16 MFMA operands, fp32 accumulation, fp32 parameter gradients; no float atomics anywhere, so every
 // gradient is bitwise reproducible from run to run.
 #include <hip/hip_runtime.h>
@@ -193,10 +193,10 @@ hipError_t launch_dgrad_flip(const float *w, float *wt, int Cout, int Cin, int k
 }
 
 // ---- adjoint of the x2 bilinear upsampling (align_corners=False, clamped edges) -------------------------------------------------
-// Forward (upsample2x_nhwc_bf16_kernel): output row 2m reads rows (max(m-1, 0), m) with weights (0.25, 0.75), row 2m+1 reads
-// (m, min(m+1, H-1)) with (0.75, 0.25); columns alike.  Gather form: input row k receives from output rows 2k-1 .. 2k+2, each with
-// the sum of the weights under which it read k.  One work-item per input pixel and 8 channels, fp32 sums, one bf16 rounding.
-// The result is the gradient of x AND of the skip (the forward upsamples x + skip).
+// Forward (upsample2x_nhwc_bf16_kernel / upsample2x_cat_nhwc_bf16_kernel): output row 2m reads rows (max(m-1, 0), m) with weights
+// (0.25, 0.75), row 2m+1 reads (m, min(m+1, H-1)) with (0.75, 0.25); columns alike.  Gather form: input row k receives from output
+// rows 2k-1 .. 2k+2, each with the sum of the weights under which it read k.  One work-item per input pixel and 8 channels, fp32
+// sums, one bf16 rounding.
 __device__ __forceinline__ float up_w(int j, int k, int n)
 {
     const int m = j >> 1;
@@ -205,123 +205,9 @@ __device__ __forceinline__ float up_w(int j, int k, int n)
     return (lo == k ? wlo : 0.0f) + (hi == k ? whi : 0.0f);
 }
 
-__global__ void __launch_bounds__(256) upsample2x_bwd_kernel(const uint16_t *dout, uint16_t *dx, int B, int H, int W, int C)
-{
-    const int G = C / 8;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)B * H * W * G) return;
-    const int g = (int)(i % G);
-    const int64_t pix = i / G;
-    const int kx = (int)(pix % W), ky = (int)((pix / W) % H), b = (int)(pix / ((int64_t)W * H));
-    const int H2 = 2 * H, W2 = 2 * W;
-    float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    for (int jy = 2 * ky - 1; jy <= 2 * ky + 2; ++jy) {
-        if (jy < 0 || jy >= H2) continue;
-        const float wy = up_w(jy, ky, H);
-        float row[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        for (int jx = 2 * kx - 1; jx <= 2 * kx + 2; ++jx) {
-            if (jx < 0 || jx >= W2) continue;
-            const float wx = up_w(jx, kx, W);
-            const uint4 v = *reinterpret_cast<const uint4 *>(dout + (((int64_t)b * H2 + jy) * W2 + jx) * C + g * 8);
-            const uint32_t *vv = reinterpret_cast<const uint32_t *>(&v);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                row[2 * j] += wx * tr_f32((uint16_t)(vv[j] & 0xFFFFu));
-                row[2 * j + 1] += wx * tr_f32((uint16_t)(vv[j] >> 16));
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] += wy * row[j];
-    }
-    uint4 o;
-    uint32_t *oo = reinterpret_cast<uint32_t *>(&o);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) oo[j] = (uint32_t)tr_bf16(acc[2 * j]) | ((uint32_t)tr_bf16(acc[2 * j + 1]) << 16);
-    *reinterpret_cast<uint4 *>(dx + pix * C + g * 8) = o;
-}
-
-hipError_t launch_upsample2x_bwd(const uint16_t *dout, uint16_t *dx, int B, int H, int W, int C, hipStream_t s)
-{
-    const int64_t n = (int64_t)B * H * W * (C / 8);
-    hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dout, dx, B, H, W, C);
-    return hipGetLastError();
-}
-
-// ---- the prediction layer's backward (1x1, C -> 1, on bf16(x + skip)) ------------------------------------------------------------
-// dy fp32 (the loss gradient of the prediction, unrounded); dx[m][c] = bf16(dy[m] * bf16(w[c])) -- the gradient of x and of the skip; dW[c] = sum_m dy[m] * bf16(x + skip)[m][c], db = sum_m dy[m].
-// One workgroup per slab of kC1x1Slab pixels: C / 8 lanes per pixel (8 channels each), the workgroup's partial sums meet in LDS in
-// a fixed order and go to ws[slab][C + 1]; the reduce kernel adds the slabs in slab order.
-constexpr int kC1x1Slab = 2048;
-__global__ void __launch_bounds__(256) conv1x1_bwd_kernel(const float *dy, const uint16_t *x, const uint16_t *skip, const float *w, uint16_t *dx,
-                                                          float *ws, int64_t M, int C)
-{
-    __shared__ float red[256 * 9];
-    const int G = C / 8, rows = 256 / G;
-    const int g = threadIdx.x % G, pr = threadIdx.x / G;
-    float wb[8], acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, accb = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) wb[j] = tr_f32(tr_bf16(w[g * 8 + j]));
-    const int64_t p0 = (int64_t)blockIdx.x * kC1x1Slab, p1 = p0 + kC1x1Slab < M ? p0 + kC1x1Slab : M;
-    for (int64_t p = p0 + pr; p < p1; p += rows) {
-        const float d = dy[p];
-        const uint4 xv = *reinterpret_cast<const uint4 *>(x + p * C + g * 8);
-        uint4 sv = make_uint4(0u, 0u, 0u, 0u);
-        if (skip) sv = *reinterpret_cast<const uint4 *>(skip + p * C + g * 8);
-        const uint32_t *xx = reinterpret_cast<const uint32_t *>(&xv), *ss = reinterpret_cast<const uint32_t *>(&sv);
-        uint4 o;
-        uint32_t *oo = reinterpret_cast<uint32_t *>(&o);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float xs0 = tr_f32((uint16_t)(xx[j] & 0xFFFFu)), xs1 = tr_f32((uint16_t)(xx[j] >> 16));
-            if (skip) {
-                xs0 = tr_f32(tr_bf16(xs0 + tr_f32((uint16_t)(ss[j] & 0xFFFFu))));
-                xs1 = tr_f32(tr_bf16(xs1 + tr_f32((uint16_t)(ss[j] >> 16))));
-            }
-            acc[2 * j] += d * xs0;
-            acc[2 * j + 1] += d * xs1;
-            oo[j] = (uint32_t)tr_bf16(d * wb[2 * j]) | ((uint32_t)tr_bf16(d * wb[2 * j + 1]) << 16);
-        }
-        *reinterpret_cast<uint4 *>(dx + p * C + g * 8) = o;
-        accb += d;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[threadIdx.x * 9 + j] = acc[j];
-    red[threadIdx.x * 9 + 8] = accb;
-    __syncthreads();
-    if ((int)threadIdx.x <= C) {                         // thread c < C: channel c; thread C: the bias (from the lanes of channel group 0)
-        const int c = threadIdx.x, cg = c < C ? c / 8 : 0, slot = c < C ? c % 8 : 8;
-        float s = 0.0f;
-        for (int r = 0; r < rows; ++r) s += red[(r * G + cg) * 9 + slot];
-        ws[(int64_t)blockIdx.x * (C + 1) + c] = s;
-    }
-}
-
-__global__ void __launch_bounds__(256) conv1x1_bwd_reduce_kernel(const float *ws, float *dw, float *db, int S, int C)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c > C) return;
-    float s = 0.0f;
-    for (int k = 0; k < S; ++k) s += ws[(int64_t)k * (C + 1) + c];
-    if (c < C) dw[c] = s;
-    else db[0] = s;
-}
-
-int64_t conv1x1_bwd_slabs(int64_t M) { return (M + kC1x1Slab - 1) / kC1x1Slab; }
-
-hipError_t launch_conv1x1_bwd(const float *dy, const uint16_t *x, const uint16_t *skip, const float *w, uint16_t *dx, float *dw, float *db, float *ws,
-                              int64_t M, int C, hipStream_t s)
-{
-    const int64_t S = conv1x1_bwd_slabs(M);
-    hipLaunchKernelGGL(conv1x1_bwd_kernel, dim3((unsigned)S), dim3(256), 0, s, dy, x, skip, w, dx, ws, M, C);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(conv1x1_bwd_reduce_kernel, dim3((unsigned)((C + 1 + 255) / 256)), dim3(256), 0, s, ws, dw, db, (int)S, C);
-    return hipGetLastError();
-}
-
-// ---- adjoint of the concat-skip upsampling (upsample2x_cat_nhwc_bf16_kernel): one channel slice [c0, c0 + C) of dout [B,2H,2W,Ctot] ->
-// dx [B,H,W,C].  upsample2x_bwd_kernel's gather (same weights, same order of the fp32 sums, one bf16 rounding) reading at pixel pitch Ctot;
-// called once for the gradient of x (c0 = 0) and once for the skip's (c0 = C1).  c0 = 0, C = Ctot is upsample2x_bwd_kernel bit for bit.
+// One channel slice [c0, c0 + C) of dout [B,2H,2W,Ctot] -> dx [B,H,W,C], read at pixel pitch Ctot.  The sum-skip layers run it with
+// c0 = 0, C = Ctot (the result is the gradient of x AND of the skip: their forward upsamples x + skip); the concat-skip layers once for
+// the gradient of x (c0 = 0) and once for the skip's (c0 = C1).
 __global__ void __launch_bounds__(256) upsample2x_cat_bwd_kernel(const uint16_t *dout, uint16_t *dx, int B, int H, int W, int Ctot, int c0, int C)
 {
     const int G = C / 8;
@@ -364,10 +250,14 @@ hipError_t launch_upsample2x_cat_bwd(const uint16_t *dout, uint16_t *dx, int B, 
     return hipGetLastError();
 }
 
-// ---- the prediction layer's backward for COUT = 1..3 outputs (EVFlowNet's flow: 2) ----------------------------------------------------
-// dy fp32 [M][COUT]; dx[m][c] = bf16(sum_o dy[m][o] * bf16(w[o][c])) (o ascending); dW[o][c] = sum_m dy[m][o] * bf16(x + skip)[m][c],
-// db[o] = sum_m dy[m][o].  conv1x1_bwd_kernel's slabs and orders per output channel: ws[slab][o][C + 1], slabs added in slab order, no
-// float atomics.  COUT = 1 gives conv1x1_bwd_kernel's results bit for bit.
+// ---- the prediction layer's backward (1x1, C -> COUT = 1..3, on bf16(x + skip); E2VID's image: 1, EVFlowNet's flow: 2) ------------
+// dy fp32 [M][COUT] (the loss gradient of the prediction, unrounded); dx[m][c] = bf16(sum_o dy[m][o] * bf16(w[o][c])) (o ascending) --
+// the gradient of x and of the skip; dW[o][c] = sum_m dy[m][o] * bf16(x + skip)[m][c], db[o] = sum_m dy[m][o].
+// One workgroup per slab of kC1x1Slab pixels: C / 8 lanes per pixel (8 channels each), the workgroup's partial sums meet in LDS in
+// a fixed order and go to ws[slab][o][C + 1]; the reduce kernel adds the slabs in slab order.  No float atomics.
+constexpr int kC1x1Slab = 2048;
+int64_t conv1x1_bwd_slabs(int64_t M) { return (M + kC1x1Slab - 1) / kC1x1Slab; }
+
 template <int COUT>
 __global__ void __launch_bounds__(256) conv1x1_bwd_cout_kernel(const float *dy, const uint16_t *x, const uint16_t *skip, const float *w, uint16_t *dx,
                                                                float *ws, int64_t M, int C)

@@ -34,6 +34,21 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _launch(name: str, device, *args) -> None:
+    """The C entry point `name` on `device` and torch's current stream there: lib().<name>(*args, stream), status checked."""
+    with torch.cuda.device(device):
+        _lib.check(getattr(_lib.lib(), name)(*args, _lib.stream_ptr()))
+
+
+def _need(name: str, t, dtype=torch.bfloat16, dims: str = "[B,H,W,C]", shape=None, last=None, device=None, owner: str = "x") -> None:
+    """ValueError unless t is a contiguous CUDA tensor of `dtype`: 4-D, or of exactly `shape` when given; with `last` channels and on
+    `device` (the device of the operand called `owner`) when given."""
+    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (t.dim() != 4 if shape is None else tuple(t.shape) != tuple(shape)) \
+            or (last is not None and t.shape[3] != last) or (device is not None and t.device != device):
+        where = f" on {owner}'s device" if device is not None else ""
+        raise ValueError(f"{name} must be a contiguous {str(dtype)[6:]} CUDA tensor {list(shape) if shape is not None else dims}{where}")
+
+
 def packed_weights(cache: dict, slot: str, w: torch.Tensor, pack) -> torch.Tensor:
     """pack(w), kept in cache[slot] (a layer's `_packed` dict) and repacked when the weight changed: another tensor (load_state_dict into
     a new parameter), an in-place update (_version: an optimizer step, copy_) or another device."""
@@ -59,8 +74,7 @@ def nchw_to_nhwc_bf16(x: torch.Tensor, relu: bool = False) -> torch.Tensor:
     x = x.contiguous()
     b, c, h, w = x.shape
     out = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_nchw_to_nhwc_bf16_hip(_ptr(x), _DTYPES[x.dtype], b, c, h, w, int(bool(relu)), _ptr(out), _lib.stream_ptr()))
+    _launch("v2v_nchw_to_nhwc_bf16_hip", x.device, _ptr(x), _DTYPES[x.dtype], b, c, h, w, int(bool(relu)), _ptr(out))
     return out
 
 
@@ -86,8 +100,7 @@ def to_nhwc8_bf16(x, scales=None):
     if scales is not None and (scales.dtype != torch.float32 or tuple(scales.shape) != (b, 2) or not scales.is_contiguous() or scales.device != x.device):
         raise ValueError(f"scales must be a contiguous float32 [{b},2] tensor on x's device")
     out = torch.empty((b, h, w, 8), dtype=torch.bfloat16, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_to_nhwc8_bf16_scaled_hip(_ptr(x), *x.stride(), b, c, h, w, _ptr(scales), _ptr(out), _lib.stream_ptr()))
+    _launch("v2v_to_nhwc8_bf16_scaled_hip", x.device, _ptr(x), *x.stride(), b, c, h, w, _ptr(scales), _ptr(out))
     return out
 
 
@@ -102,8 +115,7 @@ def pack_gate_weights(weight: torch.Tensor) -> torch.Tensor:
     n = C.c_uint64(0)
     _lib.check(_lib.lib().v2v_convlstm_packed_bytes(c, C.byref(n)))
     packed = torch.empty((n.value // 2,), dtype=torch.bfloat16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        _lib.check(_lib.lib().v2v_convlstm_pack_weights_hip(_ptr(weight.detach().contiguous()), c, _ptr(packed), _lib.stream_ptr()))
+    _launch("v2v_convlstm_pack_weights_hip", weight.device, _ptr(weight.detach().contiguous()), c, _ptr(packed))
     return packed
 
 
@@ -112,12 +124,11 @@ def convlstm_step(x, h_prev, c_prev, packed, bias, nchw_dtype=torch.float32, til
     Returns (h_state bf16 NHWC, c_state fp32 NHWC, h as [B,C,H,W] in nchw_dtype -- float32 / bfloat16 -- or None when
     nchw_dtype is None).  c_out may be c_prev (updated in place)."""
     _lib.require_gpu()
-    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4 or not x.is_contiguous():
-        raise ValueError("x must be a contiguous bfloat16 CUDA tensor [B,H,W,C]")
+    _need("x", x)
     b, h, w, c = x.shape
     for name, t, dt in (("h_prev", h_prev, torch.bfloat16), ("c_prev", c_prev, torch.float32)):
-        if t is not None and (t.dtype != dt or tuple(t.shape) != (b, h, w, c) or not t.is_contiguous() or t.device != x.device):
-            raise ValueError(f"{name} must be a contiguous {dt} tensor [B,H,W,C] on x's device")
+        if t is not None:
+            _need(name, t, dt, shape=x.shape, device=x.device)
     if bias.dtype != torch.float32 or bias.numel() != 4 * c or packed.dtype != torch.bfloat16 or packed.numel() != 4 * c * 2 * c * 9:
         raise ValueError("bias must be float32 [4C] and packed the output of pack_gate_weights for the same C")
     h_state = torch.empty_like(x)
@@ -125,10 +136,8 @@ def convlstm_step(x, h_prev, c_prev, packed, bias, nchw_dtype=torch.float32, til
     if nchw_dtype is not None and nchw_dtype not in _DTYPES:
         raise ValueError("nchw_dtype must be torch.float32, torch.bfloat16 or None")
     h_nchw = torch.empty((b, c, h, w), dtype=nchw_dtype, device=x.device) if nchw_dtype is not None else None
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_convlstm_step_hip(_ptr(x), _ptr(h_prev), _ptr(c_prev), _ptr(packed), _ptr(bias.detach().contiguous()),
-                                                    b, h, w, c, _ptr(h_state), _ptr(c_state), _ptr(h_nchw), _DTYPES.get(nchw_dtype, _lib.F32), tile_rows,
-                                                    _lib.stream_ptr()))
+    _launch("v2v_convlstm_step_hip", x.device, _ptr(x), _ptr(h_prev), _ptr(c_prev), _ptr(packed), _ptr(bias.detach().contiguous()), b, h, w, c, _ptr(h_state),
+            _ptr(c_state), _ptr(h_nchw), _DTYPES.get(nchw_dtype, _lib.F32), tile_rows)
     return h_state, c_state, h_nchw
 
 
@@ -146,8 +155,7 @@ def pack_gru_weights(update_weight, reset_weight, out_weight):
     _lib.check(_lib.lib().v2v_convgru_packed_bytes(c, C.byref(ng), C.byref(nc)))
     pg = torch.empty((ng.value // 2,), dtype=torch.bfloat16, device=update_weight.device)
     pc = torch.empty((nc.value // 2,), dtype=torch.bfloat16, device=update_weight.device)
-    with torch.cuda.device(update_weight.device):
-        _lib.check(_lib.lib().v2v_convgru_pack_weights_hip(*(_ptr(w.detach().contiguous()) for w in ws), c, _ptr(pg), _ptr(pc), _lib.stream_ptr()))
+    _launch("v2v_convgru_pack_weights_hip", update_weight.device, *(_ptr(w.detach().contiguous()) for w in ws), c, _ptr(pg), _ptr(pc))
     return pg, pc
 
 
@@ -159,14 +167,13 @@ def convgru_step(x, h_prev, h_prev_f32, packed, gates_bias, out_bias, nchw_dtype
     rne_bf16(h_prev_f32 * reset) -- the two workspaces between the launches.  h_f32_out may be h_prev_f32 (updated in place).
     tile_gates / tile_cand: kernel instance codes 1..5 (include/v2v_hip.h), 0 = by shape."""
     _lib.require_gpu()
-    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4 or not x.is_contiguous():
-        raise ValueError("x must be a contiguous bfloat16 CUDA tensor [B,H,W,C]")
+    _need("x", x)
     b, h, w, c = x.shape
     if (h_prev is None) != (h_prev_f32 is None):
         raise ValueError("h_prev and h_prev_f32 come together (both None: the zero state)")
     for name, t, dt in (("h_prev", h_prev, torch.bfloat16), ("h_prev_f32", h_prev_f32, torch.float32)):
-        if t is not None and (t.dtype != dt or tuple(t.shape) != (b, h, w, c) or not t.is_contiguous() or t.device != x.device):
-            raise ValueError(f"{name} must be a contiguous {dt} tensor [B,H,W,C] on x's device")
+        if t is not None:
+            _need(name, t, dt, shape=x.shape, device=x.device)
     pg, pc = packed
     if gates_bias.dtype != torch.float32 or gates_bias.numel() != 2 * c or out_bias.dtype != torch.float32 or out_bias.numel() != c \
             or pg.dtype != torch.bfloat16 or pg.numel() != 2 * c * 2 * c * 9 or pc.dtype != torch.bfloat16 or pc.numel() != c * 2 * c * 9:
@@ -177,10 +184,9 @@ def convgru_step(x, h_prev, h_prev_f32, packed, gates_bias, out_bias, nchw_dtype
     u = torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
     h_f32 = h_f32_out if h_f32_out is not None else torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
     h_nchw = torch.empty((b, c, h, w), dtype=nchw_dtype, device=x.device) if nchw_dtype is not None else None
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_convgru_step_hip(_ptr(x), _ptr(h_prev), _ptr(h_prev_f32), _ptr(pg), _ptr(pc), _ptr(gates_bias.detach().contiguous()),
-                                                   _ptr(out_bias.detach().contiguous()), b, h, w, c, _ptr(u), _ptr(hr), _ptr(h_bf16), _ptr(h_f32),
-                                                   _ptr(h_nchw), _DTYPES.get(nchw_dtype, _lib.F32), tile_gates, tile_cand, _lib.stream_ptr()))
+    _launch("v2v_convgru_step_hip", x.device, _ptr(x), _ptr(h_prev), _ptr(h_prev_f32), _ptr(pg), _ptr(pc), _ptr(gates_bias.detach().contiguous()),
+            _ptr(out_bias.detach().contiguous()), b, h, w, c, _ptr(u), _ptr(hr), _ptr(h_bf16), _ptr(h_f32), _ptr(h_nchw), _DTYPES.get(nchw_dtype, _lib.F32),
+            tile_gates, tile_cand)
     return (h_bf16, h_f32, u, hr) if nchw_dtype is None else (h_bf16, h_f32, u, hr, h_nchw)
 
 
@@ -196,8 +202,7 @@ def pack_gru16_weights(update_weight, reset_weight, out_weight):
     if any(not _is_f32_weight(w, (16, 32, 3, 3)) or w.device != update_weight.device for w in ws):
         raise ValueError("the three gate weights must be float32 CUDA tensors [16, 32, 3, 3] on one device")
     packed = torch.empty((_lib.lib().v2v_convgru16_packed_elems(),), dtype=torch.bfloat16, device=update_weight.device)
-    with torch.cuda.device(packed.device):
-        _lib.check(_lib.lib().v2v_convgru16_pack_weights_hip(*(_ptr(w.detach().contiguous()) for w in ws), _ptr(packed), _lib.stream_ptr()))
+    _launch("v2v_convgru16_pack_weights_hip", packed.device, *(_ptr(w.detach().contiguous()) for w in ws), _ptr(packed))
     return packed
 
 
@@ -206,14 +211,13 @@ def convgru16_step(x, h_prev, h_prev_f32, packed, gates_bias, out_bias, nchw_dty
     h_prev_f32: the float32 master of h_prev; both None = zero state.  gates_bias float32 [32] = update | reset, out_bias float32 [16].
     Returns (h_bf16, h_f32[, h as [B,16,H,W] in nchw_dtype when that is not None]): convgru_step's precision contract."""
     _lib.require_gpu()
-    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4 or x.shape[3] != 16 or not x.is_contiguous():
-        raise ValueError("x must be a contiguous bfloat16 CUDA tensor [B,H,W,16]")
+    _need("x", x, dims="[B,H,W,16]", last=16)
     b, h, w, c = x.shape
     if (h_prev is None) != (h_prev_f32 is None):
         raise ValueError("h_prev and h_prev_f32 come together (both None: the zero state)")
     for name, t, dt in (("h_prev", h_prev, torch.bfloat16), ("h_prev_f32", h_prev_f32, torch.float32)):
-        if t is not None and (t.dtype != dt or tuple(t.shape) != (b, h, w, c) or not t.is_contiguous() or t.device != x.device):
-            raise ValueError(f"{name} must be a contiguous {dt} tensor [B,H,W,16] on x's device")
+        if t is not None:
+            _need(name, t, dt, shape=x.shape, device=x.device)
     if gates_bias.dtype != torch.float32 or gates_bias.numel() != 32 or out_bias.dtype != torch.float32 or out_bias.numel() != 16 \
             or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_convgru16_packed_elems():
         raise ValueError("gates_bias must be float32 [32], out_bias float32 [16] and packed the output of pack_gru16_weights")
@@ -222,10 +226,8 @@ def convgru16_step(x, h_prev, h_prev_f32, packed, gates_bias, out_bias, nchw_dty
     h_bf16 = torch.empty_like(x)
     h_f32 = torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
     h_nchw = torch.empty((b, c, h, w), dtype=nchw_dtype, device=x.device) if nchw_dtype is not None else None
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_convgru16_step_hip(_ptr(x), _ptr(h_prev), _ptr(h_prev_f32), _ptr(packed), _ptr(gates_bias.detach().contiguous()),
-                                                     _ptr(out_bias.detach().contiguous()), b, h, w, _ptr(h_bf16), _ptr(h_f32), _ptr(h_nchw),
-                                                     _DTYPES.get(nchw_dtype, _lib.F32), _lib.stream_ptr()))
+    _launch("v2v_convgru16_step_hip", x.device, _ptr(x), _ptr(h_prev), _ptr(h_prev_f32), _ptr(packed), _ptr(gates_bias.detach().contiguous()),
+            _ptr(out_bias.detach().contiguous()), b, h, w, _ptr(h_bf16), _ptr(h_f32), _ptr(h_nchw), _DTYPES.get(nchw_dtype, _lib.F32))
     return (h_bf16, h_f32) if nchw_dtype is None else (h_bf16, h_f32, h_nchw)
 
 
@@ -235,23 +237,20 @@ def pack_resblock16_weights(w1, w2):
     if not _is_f32_weight(w1, (16, 16, 3, 3)) or not _is_f32_weight(w2, (16, 16, 3, 3)) or w1.device != w2.device:
         raise ValueError("w1 and w2 must be float32 CUDA tensors [16, 16, 3, 3] on one device")
     packed = torch.empty((_lib.lib().v2v_resblock16_packed_elems(),), dtype=torch.bfloat16, device=w1.device)
-    with torch.cuda.device(w1.device):
-        _lib.check(_lib.lib().v2v_resblock16_pack_weights_hip(_ptr(w1.detach().contiguous()), _ptr(w2.detach().contiguous()), _ptr(packed), _lib.stream_ptr()))
+    _launch("v2v_resblock16_pack_weights_hip", w1.device, _ptr(w1.detach().contiguous()), _ptr(w2.detach().contiguous()), _ptr(packed))
     return packed
 
 
 def resblock16_nhwc(x, packed, b1, b2):
     """out = relu(conv2(relu(conv1(x) + b1)) + b2 + x) on NHWC bfloat16 [B,H,W,16] in ONE launch (ResidualBlock(16, 16), norm=None)."""
     _lib.require_gpu()
-    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4 or x.shape[3] != 16 or not x.is_contiguous():
-        raise ValueError("x must be a contiguous bfloat16 CUDA tensor [B,H,W,16]")
+    _need("x", x, dims="[B,H,W,16]", last=16)
     if b1.numel() != 16 or b2.numel() != 16 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_resblock16_packed_elems():
         raise ValueError("b1 and b2 must be [16] and packed the output of pack_resblock16_weights")
     b, h, w, _ = x.shape
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_resblock16_nhwc_hip(_ptr(x), _ptr(packed), _ptr(b1.detach().float().contiguous()), _ptr(b2.detach().float().contiguous()),
-                                                      b, h, w, _ptr(out), _lib.stream_ptr()))
+    _launch("v2v_resblock16_nhwc_hip", x.device, _ptr(x), _ptr(packed), _ptr(b1.detach().float().contiguous()), _ptr(b2.detach().float().contiguous()), b, h, w,
+            _ptr(out))
     return out
 
 
@@ -261,8 +260,7 @@ def pack_head16_weights(weight):
     if not weight.is_cuda or weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[0] != 16 or weight.shape[1] > 8 or tuple(weight.shape[2:]) != (3, 3):
         raise ValueError("weight must be a float32 CUDA tensor [16, Cin <= 8, 3, 3]")
     packed = torch.empty((_lib.lib().v2v_conv_head16_packed_elems(),), dtype=torch.bfloat16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        _lib.check(_lib.lib().v2v_conv_head16_pack_weights_hip(_ptr(weight.detach().contiguous()), weight.shape[1], _ptr(packed), _lib.stream_ptr()))
+    _launch("v2v_conv_head16_pack_weights_hip", weight.device, _ptr(weight.detach().contiguous()), weight.shape[1], _ptr(packed))
     return packed
 
 
@@ -270,15 +268,12 @@ def conv_head16_nhwc(x8, packed, bias, relu=True):
     """out = [relu](conv3x3(x, pad 1) + bias): x8 [B,H,W,8] bfloat16 (to_nhwc8_bf16) -> [B,H,W,16] bfloat16, any H and W; FireNet's head
     ConvLayer(num_bins, 16, 3, padding=1) (model/model.py:278)."""
     _lib.require_gpu()
-    if not x8.is_cuda or x8.dtype != torch.bfloat16 or x8.dim() != 4 or x8.shape[3] != 8 or not x8.is_contiguous():
-        raise ValueError("x8 must be a contiguous bfloat16 CUDA tensor [B,H,W,8]")
+    _need("x8", x8, dims="[B,H,W,8]", last=8)
     if bias.numel() != 16 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_conv_head16_packed_elems():
         raise ValueError("bias must be [16] and packed the output of pack_head16_weights")
     b, h, w, _ = x8.shape
     out = torch.empty((b, h, w, 16), dtype=torch.bfloat16, device=x8.device)
-    with torch.cuda.device(x8.device):
-        _lib.check(_lib.lib().v2v_conv_head16_nhwc_hip(_ptr(x8), _ptr(packed), _ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w,
-                                                       _ptr(out), _lib.stream_ptr()))
+    _launch("v2v_conv_head16_nhwc_hip", x8.device, _ptr(x8), _ptr(packed), _ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w, _ptr(out))
     return out
 
 
@@ -293,8 +288,7 @@ def pack_conv_weights(weight: torch.Tensor) -> torch.Tensor:
     if n < 0:
         raise ValueError(f"the convolution kernel does not take {cin} -> {cout} channels, {ks}x{ks}")
     packed = torch.empty((n,), dtype=torch.bfloat16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        _lib.check(_lib.lib().v2v_conv_pack_weights_hip(_ptr(weight.detach().contiguous()), cin, cout, ks, _ptr(packed), _lib.stream_ptr()))
+    _launch("v2v_conv_pack_weights_hip", weight.device, _ptr(weight.detach().contiguous()), cin, cout, ks, _ptr(packed))
     return packed
 
 
@@ -317,24 +311,18 @@ def tile_like_batch(n: int):
 def conv_nhwc(x, packed, bias, ks: int, stride: int = 1, residual=None, relu=False, tile_rows: int = 0):
     """out = [relu](conv_ks(x, stride, pad ks//2) + bias [+ residual]) on NHWC bfloat16: x [B,Hin,Win,Cin] -> [B,Hout,Wout,Cout]."""
     _lib.require_gpu()
-    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4 or not x.is_contiguous():
-        raise ValueError("x must be a contiguous bfloat16 CUDA tensor [B,H,W,Cin]")
+    _need("x", x, dims="[B,H,W,Cin]")
     b, hin, win, cin = x.shape
     cout = bias.numel()
     if bias.dtype != torch.float32 or packed.dtype != torch.bfloat16 or packed.numel() != _conv_packed_elems(cin, cout, ks):
         raise ValueError("bias must be float32 [Cout] and packed the output of pack_conv_weights for the same Cin, Cout, ks")
     h, w = (hin - 1) // stride + 1, (win - 1) // stride + 1
-    if residual is not None and (residual.dtype != torch.bfloat16 or tuple(residual.shape) != (b, h, w, cout) or not residual.is_contiguous()
-                                 or residual.device != x.device):
-        raise ValueError("residual must be a contiguous bfloat16 tensor [B,Hout,Wout,Cout] on x's device")
+    if residual is not None:
+        _need("residual", residual, shape=(b, h, w, cout), device=x.device)
     out = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device)
-    with torch.cuda.device(x.device):
-        if tile_rows == 0 and _tile_like_batch > 0 and _tile_like_batch != b:
-            _lib.check(_lib.lib().v2v_conv_nhwc_like_hip(_ptr(x), _ptr(packed), _ptr(bias.detach().contiguous()), _ptr(residual), int(bool(relu)),
-                                                         b, hin, win, cin, cout, ks, stride, _ptr(out), _tile_like_batch, _lib.stream_ptr()))
-        else:
-            _lib.check(_lib.lib().v2v_conv_nhwc_hip(_ptr(x), _ptr(packed), _ptr(bias.detach().contiguous()), _ptr(residual), int(bool(relu)),
-                                                    b, hin, win, cin, cout, ks, stride, _ptr(out), tile_rows, _lib.stream_ptr()))
+    like = tile_rows == 0 and _tile_like_batch > 0 and _tile_like_batch != b
+    _launch("v2v_conv_nhwc_like_hip" if like else "v2v_conv_nhwc_hip", x.device, _ptr(x), _ptr(packed), _ptr(bias.detach().contiguous()), _ptr(residual),
+            int(bool(relu)), b, hin, win, cin, cout, ks, stride, _ptr(out), _tile_like_batch if like else tile_rows)
     return out
 
 
@@ -354,15 +342,12 @@ def upsample2x_nhwc(x, skip=None):
     """out = bilinear_x2(x [+ skip]) on NHWC bfloat16 ([B,H,W,C] -> [B,2H,2W,C]): f.interpolate(scale_factor=2, mode='bilinear',
     align_corners=False) of UpsampleConvLayer.forward (model/submodules.py:86-87) behind the sum skip (model/unet.py:304)."""
     _lib.require_gpu()
-    for name, v in (("x", x), ("skip", skip)):
-        if v is not None and (not v.is_cuda or v.dtype != torch.bfloat16 or v.dim() != 4 or not v.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous bfloat16 CUDA tensor [B,H,W,C]")
-    if skip is not None and (skip.shape != x.shape or skip.device != x.device):
-        raise ValueError("skip must have x's shape and device")
+    _need("x", x)
+    if skip is not None:
+        _need("skip", skip, shape=x.shape, device=x.device)
     b, h, w, c = x.shape
     out = torch.empty((b, 2 * h, 2 * w, c), dtype=torch.bfloat16, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_upsample2x_nhwc_hip(_ptr(x), _ptr(skip), b, h, w, c, _ptr(out), _lib.stream_ptr()))
+    _launch("v2v_upsample2x_nhwc_hip", x.device, _ptr(x), _ptr(skip), b, h, w, c, _ptr(out))
     return out
 
 
@@ -370,19 +355,16 @@ def conv1x1_nhwc(x, weight, bias, skip=None, out_dtype=torch.bfloat16):
     """out[..., o] = bias[o] + sum_c weight[o, c] * (x[..., c] + skip[..., c]) on NHWC bfloat16 ([B,H,W,C] -> [B,H,W,Cout], Cout <= 3):
     the prediction layer ConvLayer(base, out, 1, activation=None) on skip_sum(x, head) (model/unet.py:58-64, :307)."""
     _lib.require_gpu()
-    for name, v in (("x", x), ("skip", skip)):
-        if v is not None and (not v.is_cuda or v.dtype != torch.bfloat16 or v.dim() != 4 or not v.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous bfloat16 CUDA tensor [B,H,W,C]")
-    if skip is not None and (skip.shape != x.shape or skip.device != x.device):
-        raise ValueError("skip must have x's shape and device")
+    _need("x", x)
+    if skip is not None:
+        _need("skip", skip, shape=x.shape, device=x.device)
     b, h, w, c = x.shape
     weight = weight.detach().reshape(weight.shape[0], -1).float().contiguous()
     if weight.shape[1] != c or bias.numel() != weight.shape[0] or out_dtype not in _DTYPES:
         raise ValueError("weight must be [Cout, C(,1,1)], bias [Cout], out_dtype float32 or bfloat16")
     out = torch.empty((b, h, w, weight.shape[0]), dtype=out_dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_conv1x1_nhwc_hip(_ptr(x), _ptr(skip), _ptr(weight), _ptr(bias.detach().float().contiguous()), b * h * w, c,
-                                                   weight.shape[0], _ptr(out), _DTYPES[out_dtype], _lib.stream_ptr()))
+    _launch("v2v_conv1x1_nhwc_hip", x.device, _ptr(x), _ptr(skip), _ptr(weight), _ptr(bias.detach().float().contiguous()), b * h * w, c, weight.shape[0],
+            _ptr(out), _DTYPES[out_dtype])
     return out
 
 
@@ -394,8 +376,7 @@ def pack_head_weights(weight):
         raise ValueError("weight must be a float32 CUDA tensor [32, Cin <= 8, ks, ks], ks 3 or 5")
     ks = weight.shape[2]
     packed = torch.empty((_lib.lib().v2v_conv_head_packed_elems(ks),), dtype=torch.bfloat16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        _lib.check(_lib.lib().v2v_conv_head_pack_weights_hip(_ptr(weight.detach().contiguous()), weight.shape[1], ks, _ptr(packed), _lib.stream_ptr()))
+    _launch("v2v_conv_head_pack_weights_hip", weight.device, _ptr(weight.detach().contiguous()), weight.shape[1], ks, _ptr(packed))
     return packed
 
 
@@ -403,15 +384,12 @@ def conv_head_nhwc(x8, packed, bias, ks: int, relu=True):
     """out = [relu](conv_ks(x, stride 1, pad ks//2) + bias): x8 [B,H,W,8] bfloat16 (to_nhwc8_bf16) -> [B,H,W,32] bfloat16; the UNet's
     head ConvLayer(num_bins, 32, 5, stride 1, padding 2) (model/unet.py:77-78).  H and W multiples of 16."""
     _lib.require_gpu()
-    if not x8.is_cuda or x8.dtype != torch.bfloat16 or x8.dim() != 4 or x8.shape[3] != 8 or not x8.is_contiguous():
-        raise ValueError("x8 must be a contiguous bfloat16 CUDA tensor [B,H,W,8]")
+    _need("x8", x8, dims="[B,H,W,8]", last=8)
     if bias.numel() != 32 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_conv_head_packed_elems(ks):
         raise ValueError("bias must be [32] and packed the output of pack_head_weights for the same ks")
     b, h, w, _ = x8.shape
     out = torch.empty((b, h, w, 32), dtype=torch.bfloat16, device=x8.device)
-    with torch.cuda.device(x8.device):
-        _lib.check(_lib.lib().v2v_conv_head_nhwc_hip(_ptr(x8), _ptr(packed), _ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w, ks,
-                                                     _ptr(out), _lib.stream_ptr()))
+    _launch("v2v_conv_head_nhwc_hip", x8.device, _ptr(x8), _ptr(packed), _ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w, ks, _ptr(out))
     return out
 
 
@@ -422,8 +400,7 @@ def pack_stem_weights(weight):
             or weight.shape[1] > 8:
         raise ValueError("weight must be a float32 CUDA tensor [64, Cin <= 8, 3, 3]")
     packed = torch.empty((_lib.lib().v2v_conv_stem_packed_elems(),), dtype=torch.bfloat16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        _lib.check(_lib.lib().v2v_conv_stem_pack_weights_hip(_ptr(weight.detach().contiguous()), weight.shape[1], _ptr(packed), _lib.stream_ptr()))
+    _launch("v2v_conv_stem_pack_weights_hip", weight.device, _ptr(weight.detach().contiguous()), weight.shape[1], _ptr(packed))
     return packed
 
 
@@ -431,15 +408,12 @@ def conv_stem_nhwc(x8, packed, bias, relu=True):
     """out = [relu](conv3x3(x, stride 2, pad 1) + bias): x8 [B,H,W,8] bfloat16 (to_nhwc8_bf16) -> [B,H/2,W/2,64] bfloat16; the plain UNet's
     first encoder ConvLayer(num_bins, 64, 3, stride 2, padding 1) (model/unet.py:320-326).  H and W multiples of 16."""
     _lib.require_gpu()
-    if not x8.is_cuda or x8.dtype != torch.bfloat16 or x8.dim() != 4 or x8.shape[3] != 8 or not x8.is_contiguous():
-        raise ValueError("x8 must be a contiguous bfloat16 CUDA tensor [B,H,W,8]")
+    _need("x8", x8, dims="[B,H,W,8]", last=8)
     if bias.numel() != 64 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_conv_stem_packed_elems():
         raise ValueError("bias must be [64] and packed the output of pack_stem_weights")
     b, h, w, _ = x8.shape
     out = torch.empty((b, h // 2, w // 2, 64), dtype=torch.bfloat16, device=x8.device)
-    with torch.cuda.device(x8.device):
-        _lib.check(_lib.lib().v2v_conv_stem_nhwc_hip(_ptr(x8), _ptr(packed), _ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w,
-                                                     _ptr(out), _lib.stream_ptr()))
+    _launch("v2v_conv_stem_nhwc_hip", x8.device, _ptr(x8), _ptr(packed), _ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w, _ptr(out))
     return out
 
 
@@ -448,16 +422,15 @@ def upsample2x_cat_nhwc(x, skip=None):
     f.interpolate(skip_concat(x, skip), scale_factor=2, mode='bilinear', align_corners=False) (model/model_util.py:10, model/unet.py:350,
     model/submodules.py:86-87) without the low-resolution cat tensor."""
     _lib.require_gpu()
-    for name, v in (("x", x), ("skip", skip)):
-        if v is not None and (not v.is_cuda or v.dtype != torch.bfloat16 or v.dim() != 4 or not v.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous bfloat16 CUDA tensor [B,H,W,C]")
-    if skip is not None and (skip.shape[:3] != x.shape[:3] or skip.device != x.device):
-        raise ValueError("skip must have x's batch and spatial size and device")
+    _need("x", x)
+    if skip is not None:
+        _need("skip", skip, device=x.device)
+        if skip.shape[:3] != x.shape[:3]:
+            raise ValueError("skip must have x's batch and spatial size")
     b, h, w, c1 = x.shape
     c2 = 0 if skip is None else skip.shape[3]
     out = torch.empty((b, 2 * h, 2 * w, c1 + c2), dtype=torch.bfloat16, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_upsample2x_cat_nhwc_hip(_ptr(x), c1, _ptr(skip), c2, b, h, w, _ptr(out), _lib.stream_ptr()))
+    _launch("v2v_upsample2x_cat_nhwc_hip", x.device, _ptr(x), c1, _ptr(skip), c2, b, h, w, _ptr(out))
     return out
 
 
@@ -480,8 +453,7 @@ def relu_bwd_nhwc(dy, y):
     """y > 0 ? dy : 0 on NHWC bfloat16 (y = the saved post-ReLU output)."""
     dy = _nhwc_bf16(dy)
     out = torch.empty_like(dy)
-    with torch.cuda.device(dy.device):
-        _lib.check(_lib.lib().v2v_relu_bwd_nhwc_hip(_ptr(dy), _ptr(y), dy.numel() // dy.shape[-1], dy.shape[-1], _ptr(out), _lib.stream_ptr()))
+    _launch("v2v_relu_bwd_nhwc_hip", dy.device, _ptr(dy), _ptr(y), dy.numel() // dy.shape[-1], dy.shape[-1], _ptr(out))
     return out
 
 
@@ -493,9 +465,7 @@ def pack_dgrad_weights(weight: torch.Tensor) -> torch.Tensor:
         raise ValueError(f"no data-gradient kernel for {cin} -> {cout} channels, {ks}x{ks}")
     packed = torch.empty((n,), dtype=torch.bfloat16, device=weight.device)
     scratch = torch.empty((weight.numel(),), dtype=torch.float32, device=weight.device)
-    with torch.cuda.device(weight.device):
-        _lib.check(_lib.lib().v2v_conv_dgrad_pack_weights_hip(_ptr(weight.detach().float().contiguous()), cin, cout, ks, _ptr(scratch), _ptr(packed),
-                                                              _lib.stream_ptr()))
+    _launch("v2v_conv_dgrad_pack_weights_hip", weight.device, _ptr(weight.detach().float().contiguous()), cin, cout, ks, _ptr(scratch), _ptr(packed))
     return packed
 
 
@@ -505,9 +475,7 @@ def conv_dgrad_nhwc(dy, packed, cin: int, ks: int, stride: int, hin: int, win: i
     b, cout = dy.shape[0], dy.shape[3]
     ws = _workspace(_lib.lib().v2v_conv_dgrad_workspace_bytes(b, hin, win, cin, cout, stride), dy.device)
     dx = torch.empty((b, hin, win, cin), dtype=torch.bfloat16, device=dy.device)
-    with torch.cuda.device(dy.device):
-        _lib.check(_lib.lib().v2v_conv_dgrad_nhwc_hip(_ptr(dy), _ptr(packed), _ptr(residual), b, hin, win, cin, cout, ks, stride, _ptr(ws), _ptr(dx),
-                                                      _lib.stream_ptr()))
+    _launch("v2v_conv_dgrad_nhwc_hip", dy.device, _ptr(dy), _ptr(packed), _ptr(residual), b, hin, win, cin, cout, ks, stride, _ptr(ws), _ptr(dx))
     return dx
 
 
@@ -520,9 +488,7 @@ def conv_wgrad_nhwc(dy, x1, x2=None, c2: int = 0, cin_out: int | None = None, ks
     ws = _workspace(_lib.lib().v2v_conv_wgrad_workspace_bytes(b, ho, wo, c1 + c2, cout, ks), dy.device)
     dw = torch.empty((cout, cin_out, ks, ks), dtype=torch.float32, device=dy.device)
     db = torch.empty((cout,), dtype=torch.float32, device=dy.device)
-    with torch.cuda.device(dy.device):
-        _lib.check(_lib.lib().v2v_conv_wgrad_nhwc_hip(_ptr(dy), _ptr(x1), c1, _ptr(x2), c2, cin_out, b, hin, win, cout, ks, stride, _ptr(ws), _ptr(dw),
-                                                      _ptr(db), _lib.stream_ptr()))
+    _launch("v2v_conv_wgrad_nhwc_hip", dy.device, _ptr(dy), _ptr(x1), c1, _ptr(x2), c2, cin_out, b, hin, win, cout, ks, stride, _ptr(ws), _ptr(dw), _ptr(db))
     return dw, db
 
 
@@ -531,8 +497,7 @@ def upsample2x_bwd_nhwc(dout):
     dout = _nhwc_bf16(dout)
     b, h2, w2, c = dout.shape
     dx = torch.empty((b, h2 // 2, w2 // 2, c), dtype=torch.bfloat16, device=dout.device)
-    with torch.cuda.device(dout.device):
-        _lib.check(_lib.lib().v2v_upsample2x_bwd_nhwc_hip(_ptr(dout), b, h2 // 2, w2 // 2, c, _ptr(dx), _lib.stream_ptr()))
+    _launch("v2v_upsample2x_bwd_nhwc_hip", dout.device, _ptr(dout), b, h2 // 2, w2 // 2, c, _ptr(dx))
     return dx
 
 
@@ -541,8 +506,7 @@ def upsample2x_cat_bwd_nhwc(dout, c0: int, c: int):
     dout = _nhwc_bf16(dout)
     b, h2, w2, ctot = dout.shape
     dx = torch.empty((b, h2 // 2, w2 // 2, c), dtype=torch.bfloat16, device=dout.device)
-    with torch.cuda.device(dout.device):
-        _lib.check(_lib.lib().v2v_upsample2x_cat_bwd_nhwc_hip(_ptr(dout), b, h2 // 2, w2 // 2, ctot, c0, c, _ptr(dx), _lib.stream_ptr()))
+    _launch("v2v_upsample2x_cat_bwd_nhwc_hip", dout.device, _ptr(dout), b, h2 // 2, w2 // 2, ctot, c0, c, _ptr(dx))
     return dx
 
 
@@ -557,15 +521,14 @@ def conv1x1_bwd_cout_nhwc(dy, x, skip, weight):
     dx = torch.empty_like(x)
     dw = torch.empty((cout, c), dtype=torch.float32, device=x.device)
     db = torch.empty((cout,), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_conv1x1_bwd_cout_nhwc_hip(_ptr(dy), _ptr(x), _ptr(skip), _ptr(weight.detach().float().reshape(cout, c).contiguous()),
-                                                            m, c, cout, _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), _lib.stream_ptr()))
+    _launch("v2v_conv1x1_bwd_cout_nhwc_hip", x.device, _ptr(dy), _ptr(x), _ptr(skip), _ptr(weight.detach().float().reshape(cout, c).contiguous()), m, c, cout,
+            _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws))
     return dx, dw.reshape(weight.shape), db
 
 
 def conv1x1_bwd_nhwc(dy, x, skip, weight):
     """Prediction layer (C -> 1 on bf16(x + skip)): dy [B,H,W,1] (read as float32) -> (dx [B,H,W,C] bf16 = the gradient of x and skip,
-    dW [1,C,1,1], db [1])."""
+    dW [1,C,1,1], db [1]).  The one-output entry point; it runs conv1x1_bwd_cout_nhwc's kernel at Cout = 1."""
     dy = dy.float().contiguous()
     b, h, w, c = x.shape
     m = b * h * w
@@ -573,9 +536,8 @@ def conv1x1_bwd_nhwc(dy, x, skip, weight):
     dx = torch.empty_like(x)
     dw = torch.empty((c,), dtype=torch.float32, device=x.device)
     db = torch.empty((1,), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_conv1x1_bwd_nhwc_hip(_ptr(dy), _ptr(x), _ptr(skip), _ptr(weight.detach().float().reshape(-1).contiguous()), m, c,
-                                                       _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), _lib.stream_ptr()))
+    _launch("v2v_conv1x1_bwd_nhwc_hip", x.device, _ptr(dy), _ptr(x), _ptr(skip), _ptr(weight.detach().float().reshape(-1).contiguous()), m, c, _ptr(dx),
+            _ptr(dw), _ptr(db), _ptr(ws))
     return dx, dw.reshape(weight.shape), db
 
 
@@ -586,9 +548,8 @@ def convlstm_step_bwd(x, h_prev, c_prev, packed, bias, dh, dc):
     dc = dc.float().contiguous() if dc is not None else None
     dgates = torch.empty((b, h, w, 4 * c), dtype=torch.bfloat16, device=x.device)
     dc_prev = torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_convlstm_step_bwd_hip(_ptr(x), _ptr(h_prev), _ptr(c_prev), _ptr(packed), _ptr(bias), _ptr(dh), _ptr(dc), b, h, w, c,
-                                                        _ptr(dgates), _ptr(dc_prev), _lib.stream_ptr()))
+    _launch("v2v_convlstm_step_bwd_hip", x.device, _ptr(x), _ptr(h_prev), _ptr(c_prev), _ptr(packed), _ptr(bias), _ptr(dh), _ptr(dc), b, h, w, c, _ptr(dgates),
+            _ptr(dc_prev))
     return dgates, dc_prev
 
 
@@ -601,13 +562,11 @@ def hyper_context_nhwc8(events, prev):
     if not events.is_cuda or events.dtype != torch.float32 or events.dim() != 4 or events.shape[1] > 7:
         raise ValueError("events must be a float32 CUDA tensor [B, C <= 7, H, W]")
     b, c, h, w = events.shape
-    if prev.dtype != torch.float32 or tuple(prev.shape) != (b, 1, h, w) or not prev.is_contiguous() or prev.device != events.device:
-        raise ValueError(f"prev must be a contiguous float32 [{b},1,{h},{w}] tensor on events' device")
+    _need("prev", prev, torch.float32, shape=(b, 1, h, w), device=events.device, owner="events")
     if h % 4 != 0 or w % 4 != 0:
         raise ValueError("H and W must be multiples of 4")
     out = torch.empty((b, h // 4, w // 4, 8), dtype=torch.bfloat16, device=events.device)
-    with torch.cuda.device(events.device):
-        _lib.check(_lib.lib().v2v_hyper_context_hip(_ptr(events), *events.stride(), _ptr(prev), b, c, h, w, _ptr(out), _lib.stream_ptr()))
+    _launch("v2v_hyper_context_hip", events.device, _ptr(events), *events.stride(), _ptr(prev), b, c, h, w, _ptr(out))
     return out
 
 
@@ -615,16 +574,14 @@ def context_conv_nhwc(x8, weight, bias):
     """out = conv3x3(x8, pad 1) + bias: x8 [B,h,w,8] bfloat16 (hyper_context_nhwc8) -> [B,h,w,32] bfloat16, any h and w;
     ConvolutionalContextFusion.conv (model/hyper/hyper_dynamic.py:22).  weight float32 [32, Cin <= 8, 3, 3], read as it is (no packing)."""
     _lib.require_gpu()
-    if not x8.is_cuda or x8.dtype != torch.bfloat16 or x8.dim() != 4 or x8.shape[3] != 8 or not x8.is_contiguous():
-        raise ValueError("x8 must be a contiguous bfloat16 CUDA tensor [B,h,w,8]")
+    _need("x8", x8, dims="[B,h,w,8]", last=8)
     if weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[0] != 32 or weight.shape[1] > 8 or tuple(weight.shape[2:]) != (3, 3) \
             or bias.numel() != 32 or weight.device != x8.device:
         raise ValueError("weight must be float32 [32, Cin <= 8, 3, 3] on x8's device, bias [32]")
     b, h, w, _ = x8.shape
     out = torch.empty((b, h, w, 32), dtype=torch.bfloat16, device=x8.device)
-    with torch.cuda.device(x8.device):
-        _lib.check(_lib.lib().v2v_hyper_context_conv_hip(_ptr(x8), _ptr(weight.detach().contiguous()), _ptr(bias.detach().float().contiguous()), b, h, w,
-                                                         weight.shape[1], _ptr(out), _lib.stream_ptr()))
+    _launch("v2v_hyper_context_conv_hip", x8.device, _ptr(x8), _ptr(weight.detach().contiguous()), _ptr(bias.detach().float().contiguous()), b, h, w,
+            weight.shape[1], _ptr(out))
     return out
 
 
@@ -633,8 +590,7 @@ def tanh_bf16_(x):
     _lib.require_gpu()
     if not x.is_cuda or x.dtype != torch.bfloat16 or not x.is_contiguous() or x.numel() % 8 != 0:
         raise ValueError("x must be a contiguous bfloat16 CUDA tensor with a multiple of 8 elements")
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_tanh_bf16_hip(_ptr(x), x.numel(), _ptr(x), _lib.stream_ptr()))
+    _launch("v2v_tanh_bf16_hip", x.device, _ptr(x), x.numel(), _ptr(x))
     return x
 
 
@@ -643,14 +599,11 @@ def hyper_atoms(coeff, bases):
     zero-padded to the convolution kernel's 128 columns), bases float32 [12,25] -> atoms float32 [B,h,w,25,6]:
     atoms[..., l, m] = sum_k tanh(coeff[..., m * 12 + k]) * bases[k, l] (DynamicAtomGeneration.forward, model/hyper/hyper_dynamic.py:54-56)."""
     _lib.require_gpu()
-    if not coeff.is_cuda or coeff.dtype != torch.bfloat16 or coeff.dim() != 4 or coeff.shape[3] != 128 or not coeff.is_contiguous():
-        raise ValueError("coeff must be a contiguous bfloat16 CUDA tensor [B,h,w,128]")
-    if bases.dtype != torch.float32 or tuple(bases.shape) != (12, 25) or not bases.is_contiguous() or bases.device != coeff.device:
-        raise ValueError("bases must be a contiguous float32 [12,25] tensor on coeff's device")
+    _need("coeff", coeff, dims="[B,h,w,128]", last=128)
+    _need("bases", bases, torch.float32, shape=(12, 25), device=coeff.device, owner="coeff")
     b, h, w, _ = coeff.shape
     atoms = torch.empty((b, h, w, 25, 6), dtype=torch.float32, device=coeff.device)
-    with torch.cuda.device(coeff.device):
-        _lib.check(_lib.lib().v2v_hyper_atoms_hip(_ptr(coeff), _ptr(bases), b * h * w, _ptr(atoms), _lib.stream_ptr()))
+    _launch("v2v_hyper_atoms_hip", coeff.device, _ptr(coeff), _ptr(bases), b * h * w, _ptr(atoms))
     return atoms
 
 
@@ -665,8 +618,7 @@ def pack_dynconv_weights(weight):
     if n < 0:
         raise ValueError(f"the dynamic convolution takes 256 -> 128 channels with 6 atoms (got weight {tuple(weight.shape)})")
     packed = torch.empty((n,), dtype=torch.bfloat16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        _lib.check(_lib.lib().v2v_hyper_dynconv_pack_weights_hip(_ptr(weight.detach().contiguous()), k // 6, cout, 6, _ptr(packed), _lib.stream_ptr()))
+    _launch("v2v_hyper_dynconv_pack_weights_hip", weight.device, _ptr(weight.detach().contiguous()), k // 6, cout, 6, _ptr(packed))
     return packed
 
 
@@ -674,16 +626,13 @@ def dynconv_nhwc(x, atoms, packed, bias, relu=True):
     """out = [relu](DynamicConv(x, atoms) + bias) on NHWC bfloat16: x [B,H,W,256], atoms float32 [B,H,W,25,6] (hyper_atoms) -> [B,H,W,128];
     neither the unfolded input nor the intermediate features of model/hyper/hyper_dynamic.py:87-91 are written anywhere."""
     _lib.require_gpu()
-    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4 or not x.is_contiguous():
-        raise ValueError("x must be a contiguous bfloat16 CUDA tensor [B,H,W,Cin]")
+    _need("x", x, dims="[B,H,W,Cin]")
     b, h, w, cin = x.shape
     cout = bias.numel()
-    if atoms.dtype != torch.float32 or tuple(atoms.shape) != (b, h, w, 25, 6) or not atoms.is_contiguous() or atoms.device != x.device:
-        raise ValueError(f"atoms must be a contiguous float32 [{b},{h},{w},25,6] tensor on x's device")
+    _need("atoms", atoms, torch.float32, shape=(b, h, w, 25, 6), device=x.device)
     if bias.dtype != torch.float32 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_hyper_dynconv_packed_elems(cin, cout, 6, 5):
         raise ValueError("bias must be float32 [128] and packed the output of pack_dynconv_weights (256 -> 128 channels, 6 atoms)")
     out = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().v2v_hyper_dynconv_nhwc_hip(_ptr(x), _ptr(atoms), _ptr(packed), _ptr(bias.detach().contiguous()), int(bool(relu)), b, h, w,
-                                                         cin, cout, 6, 5, _ptr(out), _lib.stream_ptr()))
+    _launch("v2v_hyper_dynconv_nhwc_hip", x.device, _ptr(x), _ptr(atoms), _ptr(packed), _ptr(bias.detach().contiguous()), int(bool(relu)), b, h, w, cin, cout,
+            6, 5, _ptr(out))
     return out

@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import torch
 
-from .nhwc_ops import (conv1x1_bwd_cout_nhwc, conv1x1_bwd_nhwc, conv1x1_nhwc, conv_dgrad_nhwc, conv_head_nhwc, conv_nhwc, conv_stem_nhwc,
+from .nhwc_ops import (conv1x1_bwd_cout_nhwc, conv1x1_nhwc, conv_dgrad_nhwc, conv_head_nhwc, conv_nhwc, conv_stem_nhwc,
                        conv_wgrad_nhwc, convlstm_step, convlstm_step_bwd, pack_dgrad_weights, packed_weights, relu_bwd_nhwc,
                        upsample2x_bwd_nhwc, upsample2x_cat_bwd_nhwc, upsample2x_cat_nhwc, upsample2x_nhwc)
 
@@ -181,7 +181,7 @@ class PredFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, skip, weight = ctx.saved_tensors
-        dx, dw, db = (conv1x1_bwd_nhwc if weight.shape[0] == 1 else conv1x1_bwd_cout_nhwc)(dout, x, skip, weight)
+        dx, dw, db = conv1x1_bwd_cout_nhwc(dout, x, skip, weight)
         return dx, dx if ctx.has_skip else None, dw, db, None, None
 
 

@@ -229,3 +229,20 @@ def test_module_is_a_drop_in_over_a_sequence():
         CL.ConvGRU(64, 64, 5)
     with pytest.raises(ValueError, match="backward"):
         CL.ConvGRU(64, 64, 3, trainable=True)
+
+
+@pytest.mark.gpu
+def test_wide_cache_serves_no_stale_weights():
+    """ConvGRU(64, 64, 3): its packed streams AND its concatenated float32 biases sit in one cache entry keyed on all six parameters.
+    1 x 64 x 4 x 4 channels-last bfloat16 input, a non-zero previous state (tests/stale_weights.py)."""
+    import torch
+    from seeded_weights import seeded_input
+    from stale_weights import check_no_stale_weights
+    from v2v_amd import convlstm as CL
+    x = torch.from_numpy(seeded_input(2701, 1, 64, 4, 4)).cuda().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+    state = torch.tanh(torch.from_numpy(seeded_input(2702, 1, 64, 4, 4))).cuda()
+
+    def make():
+        torch.manual_seed(27)
+        return CL.ConvGRU(64, 64, 3).cuda().eval()
+    check_no_stale_weights(make, x, state)

@@ -1,5 +1,5 @@
-"""Training EVFlowNet on the device kernels (trainable=True): gradients of the three new autograd Functions (StemFn, UpCatConvFn, PredFn with
-2 outputs) and of all 26 parameters of the network against stock PyTorch's float32 autograd on the GPU, and 20 Adam steps.
+"""Training EVFlowNet on the device kernels (trainable=True): gradients of its three autograd Functions (VoxelConvFn as the stem, UpConvFn
+behind a concat skip, PredFn with 2 outputs) and of all 26 parameters of the network against stock PyTorch's float32 autograd on the GPU, and 20 Adam steps.
 
 The tolerance is tests/test_train_grad.py's, measured in each test rather than chosen: for every gradient tensor g of the package
     rel(g) = |g - g_fp32| / |g_fp32|  <=  2 x rel(g_bf16) + 1e-3      and      cos(g, g_fp32) >= 0.99,      g finite,
@@ -93,7 +93,7 @@ def test_stem_gradients():
 @gpu
 @pytest.mark.parametrize("c,cout,size", [(512, 256, 8), (256, 128, 16), (128, 64, 16), (64, 32, 32)])
 def test_concat_decoder_gradients(c, cout, size):
-    """UpCatConvFn incl. the input gradients of x and skip; (64 + 64 -> 32) is the transposed 32 -> 128 convolution on the two-taps-per-chunk
+    """UpConvFn behind a concat skip incl. the input gradients of x and skip; (64 + 64 -> 32) is the transposed 32 -> 128 convolution on the two-taps-per-chunk
     packing at kernel size 3."""
     import torch
     import torch.nn.functional as F

@@ -487,3 +487,20 @@ def test_batch_one_at_unpadded_real_data_sizes(size):
             bar = S.err(auto.float().cpu().numpy(), want.cpu().numpy())
             assert bar[0] > 0
             _within(f"{size} step {t} image", out.cpu().numpy(), want.cpu().numpy(), bar)
+
+
+@gpu
+@pytest.mark.parametrize("kind", ["convgru16", "resblock16"])
+def test_narrow_caches_serve_no_stale_weights(kind):
+    """ConvGRU(16, 16, 3) (one cache entry keyed on six parameters) and ResidualBlock(16, 16) (one stream packed from both weights) on a
+    1 x 16 x 8 x 8 channels-last bfloat16 input, the ConvGRU from a non-zero previous state (tests/stale_weights.py)."""
+    import torch
+    from stale_weights import check_no_stale_weights
+    from v2v_amd import convlstm as CL
+    x = torch.from_numpy(seeded_input(2860, 1, 16, 8, 8)).cuda().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+    state = torch.tanh(torch.from_numpy(seeded_input(2861, 1, 16, 8, 8))).cuda()
+
+    def make():
+        torch.manual_seed(28)
+        return (CL.ConvGRU(16, 16, 3) if kind == "convgru16" else CL.ResidualBlock(16, 16)).cuda().eval()
+    check_no_stale_weights(make, *((x, state) if kind == "convgru16" else (x,)))

@@ -24,6 +24,13 @@ The 3x3 gate convolution runs as an implicit GEMM on the bf16 matrix cores with 
 update fused on the accumulators (v2v_amd/csrc/v2v_convlstm.hpp).  Inference only by default (a call that would need a gradient
 raises); trainable=True on a layer records its backward kernels under grad (v2v_amd/train.py).  No fallback: shapes the kernel does not take (hidden_size % 64, H*W % 4, kernel_size
 != 3, input_size != hidden_size) raise ValueError.
+
+How the layers are put together: every layer has `_packed` (the cache of nhwc_ops.packed_weights, the one place that decides when a packed
+copy is stale) and `_weights()` (everything its forward needs packed, made or found current on the current stream; a network calls it on
+every submodule that has one before it forks streams).  ConvLayer is six layers -- `role`: pred, head, head16, stem, conv, upconv -- told
+apart once, in its constructor; ConvLayer._ROLES gives each role its weight packing, its autograd Function and the method forward hands
+over to after the argument checks.  _fold_sum_skip (the sum skip in front of a kernel that can add it) and _out_dtype (the dtype a network
+hands its prediction out in) are shared with v2v_amd/unet.py and v2v_amd/hyper.py.
 """
 from __future__ import annotations
 
@@ -34,7 +41,7 @@ from .nhwc_ops import (_to_nhwc_bf16, conv1x1_nhwc, conv3x3_nhwc, conv_head16_nh
                        convlstm_step, nchw_to_nhwc_bf16, pack_conv3x3_weights, pack_conv_weights, pack_gate_weights, pack_gru16_weights, pack_gru_weights,
                        pack_head16_weights, pack_head_weights, pack_resblock16_weights, pack_stem_weights, packed_weights, resblock16_nhwc,
                        to_nhwc8_bf16, upsample2x_cat_nhwc, upsample2x_nhwc)
-from .train import ConvFn, ConvLSTMFn, HeadFn, PredFn, ResidualBlockFn, StemFn, UpCatConvFn, UpConvFn
+from .train import ConvFn, ConvLSTMFn, PredFn, ResidualBlockFn, UpConvFn, VoxelConvFn
 
 
 def _training(layer, x) -> bool:
@@ -70,6 +77,21 @@ def _nhwc_in(x: torch.Tensor, nhwc: bool, train: bool, relu: bool = False) -> to
     else:
         x = x.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()
     return torch.relu(x) if relu else x
+
+
+def _fold_sum_skip(x, skip):
+    """The sum skip in front of a layer whose kernel can add it while it reads: -> (x, skip, nhwc).  Both operands NHWC bfloat16: they go
+    in as they are.  Anything else: added here first, skip = None.  nhwc = _is_nhwc_bf16 of the x that comes back."""
+    nhwc = _is_nhwc_bf16(x)
+    if skip is not None and not (nhwc and _is_nhwc_bf16(skip)):
+        x, skip = x + skip, None
+        nhwc = _is_nhwc_bf16(x)
+    return x, skip, nhwc
+
+
+def _out_dtype(x: torch.Tensor) -> torch.dtype:
+    """What a network hands its prediction out in: the input's dtype, bfloat16 under autocast."""
+    return torch.bfloat16 if (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()) else x.dtype
 
 
 def _nchw_out(out: torch.Tensor, like: torch.Tensor, nhwc_io: bool) -> torch.Tensor:
@@ -194,14 +216,12 @@ class ConvGRU(nn.Module):
     def _weights(self):
         """Everything forward needs packed, now (on the current stream): ((gates stream, candidate stream), gates bias [2C], out bias [C]),
         repacked when any of the six parameters changed (another tensor, an in-place update, another device)."""
-        ps = (self.update_gate.weight, self.reset_gate.weight, self.out_gate.weight, self.update_gate.bias, self.reset_gate.bias, self.out_gate.bias)
-        key = tuple((p.data_ptr(), p._version, p.device) for p in ps)
-        hit = self._packed.get("gru")
-        if hit is None or hit[0] != key:
-            w_u, w_r, w_o, b_u, b_r, b_o = (p.detach() for p in ps)
-            pack = pack_gru16_weights if self.narrow else pack_gru_weights
-            hit = self._packed["gru"] = (key, (pack(w_u, w_r, w_o), torch.cat([b_u, b_r]).float().contiguous(), b_o.float().contiguous()))
-        return hit[1]
+        u, r, o = self.update_gate, self.reset_gate, self.out_gate
+        return packed_weights(self._packed, "gru", (u.weight, r.weight, o.weight, u.bias, r.bias, o.bias), self._pack)
+
+    def _pack(self, w_u, w_r, w_o, b_u, b_r, b_o):
+        pack = pack_gru16_weights if self.narrow else pack_gru_weights
+        return pack(w_u, w_r, w_o), torch.cat([b_u, b_r]).float().contiguous(), b_o.float().contiguous()
 
     def forward(self, input_, prev_state=None, input_relu: bool = False):
         """input_relu=True takes the PRE-activation output of the convolution in front and applies its ReLU on the way in (as ConvLSTM)."""
@@ -217,13 +237,12 @@ class ConvGRU(nn.Module):
                 h_prev32 = prev_state.detach().permute(0, 2, 3, 1).float().contiguous()
                 h_prev = h_prev32.to(torch.bfloat16)
         packed, b_gates, b_out = self._weights()
+        nchw_dtype = None if nhwc_io else input_.dtype
         if self.narrow:
-            outs = convgru16_step(x.contiguous(), h_prev, h_prev32, packed, b_gates, b_out, nchw_dtype=None if nhwc_io else input_.dtype)
-            state = outs[0].permute(0, 3, 1, 2) if nhwc_io else outs[2]
-            state._v2v_gru = (outs[1], outs[0], state._version)
-            return state
-        outs = convgru_step(x, h_prev, h_prev32, packed, b_gates, b_out, nchw_dtype=None if nhwc_io else input_.dtype)
-        state = outs[0].permute(0, 3, 1, 2) if nhwc_io else outs[4]
+            outs = convgru16_step(x.contiguous(), h_prev, h_prev32, packed, b_gates, b_out, nchw_dtype=nchw_dtype)
+        else:
+            outs = convgru_step(x, h_prev, h_prev32, packed, b_gates, b_out, nchw_dtype=nchw_dtype)
+        state = outs[0].permute(0, 3, 1, 2) if nhwc_io else outs[-1]             # (h bf16, h float32, .., h as NCHW when nchw_dtype is given)
         state._v2v_gru = (outs[1], outs[0], state._version)
         return state
 
@@ -254,12 +273,7 @@ class ResidualBlock(nn.Module):
     def _weights(self):
         """Everything forward needs packed, now (on the current stream): (conv1's, conv2's) packed streams (16 channels: one stream of both)."""
         if self.narrow:
-            ws = (self.conv1.weight, self.conv2.weight)
-            key = tuple((p.data_ptr(), p._version, p.device) for p in ws)
-            hit = self._packed.get("both")
-            if hit is None or hit[0] != key:
-                hit = self._packed["both"] = (key, pack_resblock16_weights(*(p.detach() for p in ws)))
-            return hit[1]
+            return packed_weights(self._packed, "both", (self.conv1.weight, self.conv2.weight), pack_resblock16_weights)
         return (packed_weights(self._packed, "conv1", self.conv1.weight, pack_conv_weights),
                 packed_weights(self._packed, "conv2", self.conv2.weight, pack_conv_weights))
 
@@ -305,76 +319,88 @@ class ConvLayer(nn.Module):
                              "plain UNet's stem (64 output channels, kernel_size 3, stride 2)")
         if self.head16 and trainable:
             raise ValueError("ConvLayer(<= 8, 16, 3) is inference-only: the 16-channel head has no backward kernel")
+        # which of the six layers this is, decided here once: _ROLES (below the methods) gives its weight packing, its Function and its method
+        self.role = ("pred" if kernel_size == 1 else "stem" if self.stem else "head16" if self.head16 else "head" if self.head
+                     else "upconv" if upsample else "conv")
         self.force_channels_last = False          # head / stem only: hand out the kernel's NHWC buffer as a channels-last view whatever came in
         self._packed = {}                         # nhwc_ops.packed_weights' cache
-        self.trainable = trainable                # True: under grad, forward records a v2v_amd.train Function (ConvFn / UpConvFn / HeadFn / PredFn)
+        self.trainable = trainable                # True: under grad, forward records the role's v2v_amd.train Function
 
     def _weights(self):
         """Everything forward needs packed, now (on the current stream): the convolution's packed stream (None for the 1x1 prediction
         layer: its kernel reads the float32 weight)."""
-        w = self.conv2d.weight
-        if self.head16:
-            return packed_weights(self._packed, "conv2d", w, pack_head16_weights)
-        if self.head or self.stem:
-            return packed_weights(self._packed, "conv2d", w, pack_head_weights if self.head else pack_stem_weights)
-        return packed_weights(self._packed, "conv2d", w, pack_conv_weights) if w.shape[2] != 1 else None
+        pack = self._ROLES[self.role][0]
+        return packed_weights(self._packed, "conv2d", self.conv2d.weight, pack) if pack is not None else None
 
     def forward(self, x, skip=None, scales=None, skip_type="sum"):
         """skip (upsample=True only): the sum skip connection model/unet.py:304 adds in front of the decoder, folded into the
         upsampling kernel -- layer(x, skip) == layer(x + skip).  Under training the fusions are differentiated as fused (the skip into
         the upsampling, pred(x + head)).  skip_type "concat" (upsample=True only): layer(x, skip) == layer(cat(x, skip)), the plain UNet's
-        concat skip (model/unet.py:350) -- each source is upsampled into its channel slice, the low-resolution cat is never written."""
+        concat skip (model/unet.py:350) -- each source is upsampled into its channel slice, the low-resolution cat is never written.
+        Every argument check stands here; the role's own method below it only runs kernels."""
         train = _training(self, x)
-        conv = self.conv2d
-        if skip_type not in ("sum", "concat") or (skip_type == "concat" and (not self.upsample or skip is None)):
+        role, cat = self.role, skip_type == "concat"
+        if skip_type not in ("sum", "concat") or (cat and (not self.upsample or skip is None)):
             raise ValueError("skip_type is 'sum' or 'concat'; 'concat' is the decoder's (upsample=True) skip and needs one")
         if scales is not None and not (self.head or self.stem):
             # only the head kernel (<= 8 input channels, 3x3 / 5x5) divides by normalize_batch_voxel's scales while it reads; anything else
             # would silently run on raw, un-normalised events (RingLoader(normalize='scales') hands out raw voxels)
             raise ValueError("`scales` is applied by the head kernel only (in_channels <= 8, kernel 3 or 5): normalise the events first "
                              "(v2v_amd.postops.apply_scales / RingLoader(normalize=True)) for this layer")
-        if conv.kernel_size[0] == 1:                                                   # prediction layer: pred(skip_sum(x, head)), model/unet.py:307
-            nhwc = all(v is None or _is_nhwc_bf16(v) for v in (x, skip))
-            if not nhwc:
-                x, skip = (x if skip is None else x + skip), None
-            xn, sn = _nhwc_in(x, nhwc, train), None if skip is None else skip.permute(0, 2, 3, 1)
-            out_dtype = torch.bfloat16 if nhwc else x.dtype
-            # training: float32 out (the bf16 kernel values widened exactly; with a float32 input the inference path's dtype too): the loss
-            # gradient then reaches the backward kernel unrounded -- UNetRecurrent.forward's .to(out_dtype) gives the inference bits
-            out = PredFn.apply(xn, sn, conv.weight, conv.bias, self, out_dtype) if train else PredFn.kernels(xn, sn, self, out_dtype)
-            return _nchw_out(out, x, nhwc)
-        if skip is not None and not self.upsample:
+        if skip is not None and not self.upsample and role != "pred":
             raise ValueError("skip is the decoder's (upsample=True) sum skip connection")
-        if self.head or self.stem:                                                     # model/unet.py:77-78 / :320-326: any float layout in, bf16 out
-            if train and x.requires_grad:
-                raise ValueError("the trainable head / stem computes no gradient for its input (the voxel grid)")
-            low = x.dtype == torch.bfloat16 or (x.is_cuda and torch.is_autocast_enabled())
-            # channels-last out when the input or (as torch's own convolution decides) the weight is channels-last
-            cl = self.force_channels_last or _is_channels_last(x) or _is_channels_last(conv.weight)
-            x8 = to_nhwc8_bf16(x.detach().float(), scales)
-            fn = HeadFn if self.head else StemFn
-            if self.head16:
-                out = conv_head16_nhwc(x8, self._weights(), conv.bias, relu=self.relu).permute(0, 3, 1, 2)
-            else:
-                out = (fn.apply(x8, conv.weight, conv.bias, self) if train else fn.kernels(x8, self)).permute(0, 3, 1, 2)
-            out = out if cl else out.contiguous()
-            return out if low else out.to(x.dtype)
-        if skip_type == "concat":
-            if conv.in_channels != x.shape[1] + skip.shape[1]:
-                raise ValueError(f"concat skip: conv2d.in_channels {conv.in_channels} != {x.shape[1]} + {skip.shape[1]}")
-            nhwc_io = _is_nhwc_bf16(x) and _is_nhwc_bf16(skip)
-            xn, sn = _nhwc_in(x, _is_nhwc_bf16(x), train), _nhwc_in(skip, _is_nhwc_bf16(skip), train)
-            out = UpCatConvFn.apply(xn, sn, conv.weight, conv.bias, self) if train else UpCatConvFn.kernels(xn, sn, self)[0]
-            return _nchw_out(out, x, nhwc_io)
+        if train and x.requires_grad and (self.head or self.stem):
+            raise ValueError("the trainable head / stem computes no gradient for its input (the voxel grid)")
+        if cat and self.conv2d.in_channels != x.shape[1] + skip.shape[1]:
+            raise ValueError(f"concat skip: conv2d.in_channels {self.conv2d.in_channels} != {x.shape[1]} + {skip.shape[1]}")
+        _, fn, run = self._ROLES[role]
+        return run(self, fn, x, skip, scales, train, cat)
+
+    def _run_pred(self, fn, x, skip, scales, train, cat):
+        """pred(skip_sum(x, head)), model/unet.py:307.  Training: float32 out (the bf16 kernel values widened exactly; with a float32 input
+        the inference path's dtype too): the loss gradient then reaches the backward kernel unrounded -- UNetRecurrent.forward's
+        .to(out_dtype) gives the inference bits."""
+        conv, x_in = self.conv2d, x
+        x, skip, nhwc = _fold_sum_skip(x, skip)
+        nhwc = nhwc and x is x_in                                   # a sum made here goes through the layout kernel, whatever its layout
+        xn, sn = _nhwc_in(x, nhwc, train), None if skip is None else skip.permute(0, 2, 3, 1)
+        out_dtype = torch.bfloat16 if nhwc else x.dtype
+        out = fn.apply(xn, sn, conv.weight, conv.bias, self, out_dtype) if train else fn.kernels(xn, sn, self, out_dtype)
+        return _nchw_out(out, x, nhwc)
+
+    def _run_voxel(self, fn, x, skip, scales, train, cat):
+        """head / head16 / stem (model/unet.py:77-78 / :320-326): any float layout in, bf16 out; channels-last out when the input or (as
+        torch's own convolution decides) the weight is channels-last."""
+        conv = self.conv2d
+        low = x.dtype == torch.bfloat16 or (x.is_cuda and torch.is_autocast_enabled())
+        cl = self.force_channels_last or _is_channels_last(x) or _is_channels_last(conv.weight)
+        x8 = to_nhwc8_bf16(x.detach().float(), scales)
+        out = (fn.apply(x8, conv.weight, conv.bias, self) if train else fn.kernels(x8, self)).permute(0, 3, 1, 2)
+        out = out if cl else out.contiguous()
+        return out if low else out.to(x.dtype)
+
+    def _run_conv(self, fn, x, skip, scales, train, cat):
         nhwc_io = _is_nhwc_bf16(x)
-        if skip is not None and not (nhwc_io and _is_nhwc_bf16(skip)):
-            x, skip = x + skip, None
-            nhwc_io = _is_nhwc_bf16(x)
-        xn, sn = _nhwc_in(x, nhwc_io, train), None if skip is None else skip.permute(0, 2, 3, 1)
-        if not self.upsample:
-            out = ConvFn.apply(xn, conv.weight, conv.bias, self) if train else ConvFn.kernels(xn, self)
-        elif train:
-            out = UpConvFn.apply(xn, sn, conv.weight, conv.bias, self)
-        else:
-            out = UpConvFn.kernels(xn, sn, self)[0]
+        xn = _nhwc_in(x, nhwc_io, train)
+        out = fn.apply(xn, self.conv2d.weight, self.conv2d.bias, self) if train else fn.kernels(xn, self)
         return _nchw_out(out, x, nhwc_io)
+
+    def _run_upconv(self, fn, x, skip, scales, train, cat):
+        conv = self.conv2d
+        if cat:
+            nhwc_x, nhwc_skip = _is_nhwc_bf16(x), _is_nhwc_bf16(skip)
+            nhwc_io = nhwc_x and nhwc_skip
+            xn, sn = _nhwc_in(x, nhwc_x, train), _nhwc_in(skip, nhwc_skip, train)
+        else:
+            x, skip, nhwc_io = _fold_sum_skip(x, skip)
+            xn, sn = _nhwc_in(x, nhwc_io, train), None if skip is None else skip.permute(0, 2, 3, 1)
+        out = fn.apply(xn, sn, conv.weight, conv.bias, self, cat) if train else fn.kernels(xn, sn, self, cat)[0]
+        return _nchw_out(out, x, nhwc_io)
+
+    # role -> (weight packing | None, autograd Function whose `kernels` is the forward, the method that runs it)
+    _ROLES = {"pred": (None, PredFn, _run_pred),
+              "head": (pack_head_weights, VoxelConvFn, _run_voxel),
+              "head16": (pack_head16_weights, VoxelConvFn, _run_voxel),
+              "stem": (pack_stem_weights, VoxelConvFn, _run_voxel),
+              "conv": (pack_conv_weights, ConvFn, _run_conv),
+              "upconv": (pack_conv_weights, UpConvFn, _run_upconv)}

@@ -17,6 +17,10 @@ What runs per time step for the dynamic layer (raw operators in v2v_amd/nhwc_ops
     hyper_context_nhwc8 -> context_conv_nhwc (context_fusion.conv) -> conv_nhwc (bases_net.0 + folded BatchNorm) -> tanh_bf16_ ->
     conv_nhwc (bases_net.3 + folded BatchNorm, 72 outputs zero-padded to 128) -> hyper_atoms (tanh + the Fourier-Bessel einsum, float32) ->
     upsample2x_nhwc (sum skip folded in) -> dynconv_nhwc (features in registers -> matrix cores, bias, ReLU).
+
+The layers follow v2v_amd/convlstm.py's protocol: `_packed` + `_weights()` on nhwc_ops.packed_weights (the BatchNorm fold is keyed on all six
+tensors it reads), convlstm._fold_sum_skip for the sum skip.  HyperE2VID keeps its own states / reset_states (it also clears prev_recs and
+has no graphed sequence: sharing unet._Stateful would need as many lines as it saves).
 """
 from __future__ import annotations
 
@@ -24,9 +28,9 @@ import torch
 import torch.nn as nn
 
 from . import unet as _unet
-from .convlstm import _is_nhwc_bf16, _nchw_out, _nhwc_in
+from .convlstm import _fold_sum_skip, _nchw_out, _nhwc_in, _out_dtype
 from .nhwc_ops import (context_conv_nhwc, conv_nhwc, dynconv_nhwc, hyper_atoms, hyper_context_nhwc8, pack_conv_weights, pack_dynconv_weights,
-                       tanh_bf16_, upsample2x_nhwc)
+                       packed_weights, tanh_bf16_, upsample2x_nhwc)
 
 
 def fourier_bessel_bases(kernel_size: int, num_bases: int) -> torch.Tensor:
@@ -76,16 +80,6 @@ def fold_batchnorm(conv: nn.Conv2d, bn: nn.BatchNorm2d):
     scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
     b = conv.bias.detach().float() if conv.bias is not None else torch.zeros_like(scale)
     return conv.weight.detach().float() * scale[:, None, None, None], (b - bn.running_mean.detach().float()) * scale + bn.bias.detach().float()
-
-
-def _packed_group(cache: dict, slot: str, tensors, make):
-    """nhwc_ops.packed_weights for a pack that reads SEVERAL tensors (a convolution and its BatchNorm): rebuilt when any of them is another
-    tensor, was updated in place (_version: load_state_dict, an optimizer step) or moved to another device."""
-    key = tuple((t.data_ptr(), t._version, t.device) for t in tensors)
-    hit = cache.get(slot)
-    if hit is None or hit[0] != key:
-        hit = cache[slot] = (key, make())
-    return hit[1]
 
 
 class ConvolutionalContextFusion(nn.Module):
@@ -145,14 +139,18 @@ class DynamicAtomGeneration(nn.Module):
         out = []
         for i, pad_to in ((0, 64), (3, 128)):
             conv, bn = self.bases_net[i], self.bases_net[i + 1]
-            out.append(_packed_group(self._packed, f"bases_net.{i}", (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var),
-                                     lambda i=i, pad_to=pad_to: self._fold(i, pad_to)))
+            out.append(packed_weights(self._packed, f"bases_net.{i}", (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var),
+                                      lambda *_, i=i, pad_to=pad_to: self._fold(i, pad_to)))   # _fold reads the same six tensors from the modules
         return out
 
     def forward(self, context):
         (p0, b0), (p1, b1) = self._weights()
         hid = tanh_bf16_(conv_nhwc(context, p0, b0, 3))
         return hyper_atoms(conv_nhwc(hid, p1, b1, 3), self.bases.float().contiguous())
+
+
+def _pack_coefficients(w):
+    return pack_dynconv_weights(w.float().contiguous())
 
 
 class DynamicConv(nn.Module):
@@ -175,8 +173,7 @@ class DynamicConv(nn.Module):
         nn.init.zeros_(self.bias)
 
     def _weights(self):
-        w = self.compositional_coefficients
-        return _packed_group(self._packed, "compositional_coefficients", (w,), lambda: pack_dynconv_weights(w.detach().float().contiguous()))
+        return packed_weights(self._packed, "compositional_coefficients", self.compositional_coefficients, _pack_coefficients)
 
     def forward(self, x, atoms, relu=False):
         return dynconv_nhwc(x, atoms, self._weights(), self.bias.detach().float(), relu=relu)
@@ -225,10 +222,7 @@ class DynamicUpsampleLayer(nn.Module):
         if tuple(ev_tensor.shape[-2:]) != (8 * x.shape[-2], 8 * x.shape[-1]) or tuple(prev_recs.shape[-2:]) != tuple(ev_tensor.shape[-2:]):
             raise ValueError(f"the 1/4-scale context must meet the x2-upsampled input: events / prev_recs must be 8x the size of x "
                              f"(x {tuple(x.shape[-2:])}, events {tuple(ev_tensor.shape[-2:])}, prev_recs {tuple(prev_recs.shape[-2:])})")
-        nhwc_io = _is_nhwc_bf16(x)
-        if skip is not None and not (nhwc_io and _is_nhwc_bf16(skip)):
-            x, skip = x + skip, None
-            nhwc_io = _is_nhwc_bf16(x)
+        x, skip, nhwc_io = _fold_sum_skip(x, skip)
         xn, sn = _nhwc_in(x, nhwc_io, False), None if skip is None else skip.permute(0, 2, 3, 1)
         atoms = self.atoms(ev_tensor, prev_recs)
         out = self.dynamic_conv(upsample2x_nhwc(xn, sn), atoms, relu=self.relu)
@@ -255,11 +249,6 @@ class UNetRecurrent(_unet.UNetRecurrent):
             self.decoders[0] = DynamicUpsampleLayer(self.encoder_output_sizes[-1], self.encoder_input_sizes[-1], kernel_size=k, padding=k // 2,
                                                     in_fuse_channels=1 + self.num_bins)
 
-    def _pack_weights(self):
-        super()._pack_weights()
-        if self.use_dynamic_decoder:
-            self.decoders[0]._weights()
-
     def _decode(self, head, blocks, ev_tensor=None, prev_recs=None):
         x = blocks[-1]
         for resblock in self.resblocks:
@@ -283,7 +272,7 @@ class UNetRecurrent(_unet.UNetRecurrent):
 
     def forward(self, x, prev_recs=None):
         self.check_input(x)
-        out_dtype = torch.bfloat16 if (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()) else x.dtype
+        out_dtype = _out_dtype(x)
         if prev_recs is None:
             prev_recs = torch.zeros((x.shape[0], 1) + tuple(x.shape[-2:]), dtype=torch.float32, device=x.device)
         head, blocks = self._encode(x, None)
@@ -333,13 +322,10 @@ class HyperE2VID(nn.Module):
     def forward_sequence(self, events, out=None):
         """events [N,T,num_bins,H,W] -> images [N,T,1,H,W]: the plain step loop on the caller's stream (step t + 1's decoder needs step t's
         image, so the decoder halves cannot run beside one another as E2VIDRecurrent's do); bit-identical to T calls of forward()."""
-        if events.dim() != 5:
-            raise ValueError("events must be [N, T, num_bins, H, W]")
-        n, t_steps = events.shape[:2]
+        n, t_steps = _unet._sequence_shape(events)
         self.unetrecurrent.check_input(events[:, 0])
-        out_dtype = torch.bfloat16 if (events.dtype == torch.bfloat16 or torch.is_autocast_enabled()) else events.dtype
         if out is None:
-            out = torch.empty((n, t_steps, 1) + tuple(events.shape[-2:]), dtype=out_dtype, device=events.device)
+            out = torch.empty((n, t_steps, 1) + tuple(events.shape[-2:]), dtype=_out_dtype(events), device=events.device)
         for t in range(t_steps):
             out[:, t] = self.forward(events[:, t])["image"]
         return out

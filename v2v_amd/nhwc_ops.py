@@ -1,6 +1,7 @@
 """The raw NHWC bfloat16 operators of the recurrent UNet, forward and backward: one Python function per C entry point of the layer kernels
-(v2v_amd/csrc/v2v_convlstm.hpp, v2v_train_tu.hip), plus the packed-weight cache every layer shares.  No nn.Module and no autograd here:
-v2v_amd/train.py builds the torch.autograd.Functions on these, v2v_amd/convlstm.py the layers.
+(v2v_amd/csrc/v2v_convlstm.hpp, v2v_train_tu.hip), plus the packed-weight cache every layer shares (packed_weights: one tensor or a
+tuple of tensors as the key, the only implementation).  No nn.Module and no autograd here: v2v_amd/train.py builds the
+torch.autograd.Functions on these, v2v_amd/convlstm.py the layers.
 
     convlstm_step / conv_nhwc / conv3x3_nhwc / upsample2x_nhwc     the forward operators
     convgru_step / pack_gru_weights                        the ConvGRU step (gates launch + candidate launch) and its packing
@@ -49,13 +50,18 @@ def _need(name: str, t, dtype=torch.bfloat16, dims: str = "[B,H,W,C]", shape=Non
         raise ValueError(f"{name} must be a contiguous {str(dtype)[6:]} CUDA tensor {list(shape) if shape is not None else dims}{where}")
 
 
-def packed_weights(cache: dict, slot: str, w: torch.Tensor, pack) -> torch.Tensor:
-    """pack(w), kept in cache[slot] (a layer's `_packed` dict) and repacked when the weight changed: another tensor (load_state_dict into
-    a new parameter), an in-place update (_version: an optimizer step, copy_) or another device."""
-    key = (w.data_ptr(), w._version, w.device)
+def packed_weights(cache: dict, slot: str, tensors, make):
+    """The one packed-weight cache: make(*detached tensors), kept in cache[slot] (a layer's `_packed` dict) and made again when ANY source
+    tensor changed -- another tensor (load_state_dict into a new parameter), an in-place update (_version: an optimizer step, copy_) or
+    another device.  tensors: one tensor, or a tuple of everything the cached value was computed from (a key that leaves one out serves
+    stale weights silently)."""
+    if type(tensors) is tuple:
+        key = tuple([(t.data_ptr(), t._version, t.device) for t in tensors])
+    else:
+        key = (tensors.data_ptr(), tensors._version, tensors.device)
     hit = cache.get(slot)
     if hit is None or hit[0] != key:
-        hit = cache[slot] = (key, pack(w.detach()))
+        hit = cache[slot] = (key, make(*[t.detach() for t in tensors]) if type(tensors) is tuple else make(tensors.detach()))
     return hit[1]
 
 

@@ -9,12 +9,15 @@ only HIP kernels; no float atomics: bitwise reproducible.
 
 `kernels` reads the parameters from the layer it is given.  The weight / bias arguments of every `forward` are there for autograd alone (it
 routes their gradients): they must be that layer's own parameters, as the layers of v2v_amd.convlstm pass them.
+
+    ConvFn / UpConvFn (sum or concat skip) / VoxelConvFn (head, stem, 16-channel head)     ConvLayer's roles; one backward: conv_backward
+    PredFn / ResidualBlockFn / ConvLSTMFn                                                 the prediction layer, ResidualBlock, ConvLSTM
 """
 from __future__ import annotations
 
 import torch
 
-from .nhwc_ops import (conv1x1_bwd_cout_nhwc, conv1x1_nhwc, conv_dgrad_nhwc, conv_head_nhwc, conv_nhwc, conv_stem_nhwc,
+from .nhwc_ops import (conv1x1_bwd_cout_nhwc, conv1x1_nhwc, conv_dgrad_nhwc, conv_head16_nhwc, conv_head_nhwc, conv_nhwc, conv_stem_nhwc,
                        conv_wgrad_nhwc, convlstm_step, convlstm_step_bwd, pack_dgrad_weights, packed_weights, relu_bwd_nhwc,
                        upsample2x_bwd_nhwc, upsample2x_cat_bwd_nhwc, upsample2x_cat_nhwc, upsample2x_nhwc)
 
@@ -22,6 +25,22 @@ from .nhwc_ops import (conv1x1_bwd_cout_nhwc, conv1x1_nhwc, conv_dgrad_nhwc, con
 def dgrad_weights(layer, name: str) -> torch.Tensor:
     """The transposed convolution's packed weights of getattr(layer, name) (an nn.Conv2d), through the layer's packed-weight cache."""
     return packed_weights(layer._packed, name + ".dgrad", getattr(layer, name).weight, pack_dgrad_weights)
+
+
+def conv_backward(layer, dout, out, x, need_dx: bool, cin_out=None, adjoint=None):
+    """The backward every convolution layer shares, from the layer's input x and its post-ReLU output `out`: ReLU mask -> data gradient
+    (when need_dx; handed through `adjoint`, the backward of what stood in front of the convolution, before the next launch) -> weight /
+    bias gradient.  -> (dx | None, dw, db).  cin_out: the weight's input channels when x carries more (the voxel layers' 8-channel pad)."""
+    conv = layer.conv2d
+    ks, stride = conv.kernel_size[0], conv.stride[0]
+    dz = relu_bwd_nhwc(dout, out if layer.relu else None)
+    dx = None
+    if need_dx:
+        dx = conv_dgrad_nhwc(dz, dgrad_weights(layer, "conv2d"), x.shape[3], ks, stride, x.shape[1], x.shape[2])
+        if adjoint is not None:
+            dx = adjoint(dx)
+    dw, db = conv_wgrad_nhwc(dz, x, cin_out=cin_out, ks=ks, stride=stride)
+    return dx, dw, db
 
 
 class ConvFn(torch.autograd.Function):
@@ -42,112 +61,60 @@ class ConvFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, out, _ = ctx.saved_tensors
-        layer = ctx.layer
-        conv = layer.conv2d
-        ks, stride = conv.kernel_size[0], conv.stride[0]
-        dz = relu_bwd_nhwc(dout, out if layer.relu else None)
-        dx = conv_dgrad_nhwc(dz, dgrad_weights(layer, "conv2d"), x.shape[3], ks, stride, x.shape[1], x.shape[2]) if ctx.needs_input_grad[0] else None
-        dw, db = conv_wgrad_nhwc(dz, x, ks=ks, stride=stride)
-        return dx, dw, db, None
+        return conv_backward(ctx.layer, dout, out, x, ctx.needs_input_grad[0]) + (None,)
 
 
 class UpConvFn(torch.autograd.Function):
-    """[relu](conv_ks(up2(x [+ skip])) + bias) (UpsampleConvLayer with the decoder's sum skip folded into the upsampling)."""
+    """[relu](conv_ks(up2(x [+ skip])) + bias), or with cat=True [relu](conv_ks(up2(cat(x, skip))) + bias): UpsampleConvLayer with the
+    decoder's sum skip folded into the upsampling, or behind the plain UNet's concat skip (model/unet.py:350).  The two differ in the
+    upsampling call and in its adjoint."""
 
     @staticmethod
-    def kernels(x, skip, layer):
-        """-> (out, u = the upsampled sum the convolution read)."""
+    def kernels(x, skip, layer, cat=False):
+        """-> (out, u = the upsampled sum / concat buffer the convolution read)."""
         conv = layer.conv2d
-        u = upsample2x_nhwc(x, skip)
+        u = upsample2x_cat_nhwc(x, skip) if cat else upsample2x_nhwc(x, skip)
         return conv_nhwc(u, layer._weights(), conv.bias.detach().float(), conv.kernel_size[0], conv.stride[0], relu=layer.relu), u
 
     @staticmethod
-    def forward(ctx, x, skip, weight, bias, layer):
-        out, u = UpConvFn.kernels(x, skip, layer)
-        ctx.layer, ctx.has_skip = layer, skip is not None
+    def forward(ctx, x, skip, weight, bias, layer, cat=False):
+        out, u = UpConvFn.kernels(x, skip, layer, cat)
+        ctx.layer, ctx.cat, ctx.has_skip, ctx.c1 = layer, cat, skip is not None, x.shape[3]
         ctx.save_for_backward(u, out, weight)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         u, out, _ = ctx.saved_tensors
-        layer = ctx.layer
-        ks, stride = layer.conv2d.kernel_size[0], layer.conv2d.stride[0]
-        dz = relu_bwd_nhwc(dout, out if layer.relu else None)
-        dsum = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            du = conv_dgrad_nhwc(dz, dgrad_weights(layer, "conv2d"), u.shape[3], ks, stride, u.shape[1], u.shape[2])
-            dsum = upsample2x_bwd_nhwc(du)
-        dw, db = conv_wgrad_nhwc(dz, u, ks=ks, stride=stride)
-        return dsum, dsum if ctx.has_skip else None, dw, db, None
+        need_x, need_skip = ctx.needs_input_grad[:2]
+
+        def adjoint(du):
+            if not ctx.cat:
+                dsum = upsample2x_bwd_nhwc(du)
+                return dsum, dsum if ctx.has_skip else None
+            return (upsample2x_cat_bwd_nhwc(du, 0, ctx.c1) if need_x else None,
+                    upsample2x_cat_bwd_nhwc(du, ctx.c1, u.shape[3] - ctx.c1) if need_skip else None)
+        dxs, dw, db = conv_backward(ctx.layer, dout, out, u, need_x or need_skip, adjoint=adjoint)
+        return (dxs or (None, None)) + (dw, db, None, None)
 
 
-class UpCatConvFn(torch.autograd.Function):
-    """[relu](conv_ks(up2(cat(x, skip))) + bias) (UpsampleConvLayer behind the plain UNet's concat skip, model/unet.py:350)."""
-
-    @staticmethod
-    def kernels(x, skip, layer):
-        """-> (out, u = the upsampled concat buffer the convolution read)."""
-        conv = layer.conv2d
-        u = upsample2x_cat_nhwc(x, skip)
-        return conv_nhwc(u, layer._weights(), conv.bias.detach().float(), conv.kernel_size[0], conv.stride[0], relu=layer.relu), u
-
-    @staticmethod
-    def forward(ctx, x, skip, weight, bias, layer):
-        out, u = UpCatConvFn.kernels(x, skip, layer)
-        ctx.layer, ctx.c1 = layer, x.shape[3]
-        ctx.save_for_backward(u, out, weight)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        u, out, _ = ctx.saved_tensors
-        layer, c1 = ctx.layer, ctx.c1
-        ks, stride = layer.conv2d.kernel_size[0], layer.conv2d.stride[0]
-        dz = relu_bwd_nhwc(dout, out if layer.relu else None)
-        dx = dskip = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            du = conv_dgrad_nhwc(dz, dgrad_weights(layer, "conv2d"), u.shape[3], ks, stride, u.shape[1], u.shape[2])
-            dx = upsample2x_cat_bwd_nhwc(du, 0, c1) if ctx.needs_input_grad[0] else None
-            dskip = upsample2x_cat_bwd_nhwc(du, c1, u.shape[3] - c1) if ctx.needs_input_grad[1] else None
-        dw, db = conv_wgrad_nhwc(dz, u, ks=ks, stride=stride)
-        return dx, dskip, dw, db, None
-
-
-class StemFn(torch.autograd.Function):
-    """The plain UNet's stem (voxel bins -> 64 channels, 3x3, stride 2): x8 = the input as bf16 NHWC padded to 8 channels; no input gradient."""
-
-    @staticmethod
-    def kernels(x8, layer):
-        return conv_stem_nhwc(x8, layer._weights(), layer.conv2d.bias, relu=layer.relu)
-
-    @staticmethod
-    def forward(ctx, x8, weight, bias, layer):
-        out = StemFn.kernels(x8, layer)
-        ctx.layer = layer
-        ctx.save_for_backward(x8, out, weight)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        x8, out, weight = ctx.saved_tensors
-        layer = ctx.layer
-        dz = relu_bwd_nhwc(dout, out if layer.relu else None)
-        dw, db = conv_wgrad_nhwc(dz, x8, cin_out=weight.shape[1], ks=3, stride=2)
-        return None, dw, db, None
-
-
-class HeadFn(torch.autograd.Function):
-    """The head (voxel bins -> 32 channels): x8 = the input as bf16 NHWC padded to 8 channels; no input gradient (the voxel grid is data)."""
+class VoxelConvFn(torch.autograd.Function):
+    """The layers that read the voxel grid, by the layer's role: the head (voxel bins -> 32 channels, stride 1), the plain UNet's stem
+    (-> 64 channels, 3x3, stride 2) and FireNet's 16-channel head (inference only: ConvLayer refuses trainable=True).  x8 = the input as
+    bf16 NHWC padded to 8 channels; no input gradient (the voxel grid is data)."""
 
     @staticmethod
     def kernels(x8, layer):
         conv = layer.conv2d
+        if layer.role == "stem":
+            return conv_stem_nhwc(x8, layer._weights(), conv.bias, relu=layer.relu)
+        if layer.role == "head16":
+            return conv_head16_nhwc(x8, layer._weights(), conv.bias, relu=layer.relu)
         return conv_head_nhwc(x8, layer._weights(), conv.bias, conv.kernel_size[0], relu=layer.relu)
 
     @staticmethod
     def forward(ctx, x8, weight, bias, layer):
-        out = HeadFn.kernels(x8, layer)
+        out = VoxelConvFn.kernels(x8, layer)
         ctx.layer = layer
         ctx.save_for_backward(x8, out, weight)
         return out
@@ -155,10 +122,7 @@ class HeadFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x8, out, weight = ctx.saved_tensors
-        layer = ctx.layer
-        dz = relu_bwd_nhwc(dout, out if layer.relu else None)
-        dw, db = conv_wgrad_nhwc(dz, x8, cin_out=weight.shape[1], ks=layer.conv2d.kernel_size[0], stride=1)
-        return None, dw, db, None
+        return conv_backward(ctx.layer, dout, out, x8, False, cin_out=weight.shape[1]) + (None,)
 
 
 class PredFn(torch.autograd.Function):

@@ -27,14 +27,33 @@ Inside forward() everything runs in bfloat16 NHWC (torch.channels_last views of 
 the float voxel grid in any layout, every later layer consumes and produces NHWC in place, the cell states stay float32, and
 the prediction comes back in the input's dtype.  Parity: golden G18 = the reference's modules run in float32 on seeded
 weights (tests/test_unet_golden.py; tolerance stated there).
+
+Shared by the sequence calls: _sequence_shape (the [N,T,bins,H,W] check), _t_major (one launch of a state-free layer for all T steps),
+_Stateful (states / reset_states / the hipGraph capture of a sequence: E2VIDRecurrent, FlowNet and FireNet) and _graphed_sequence behind it.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from .convlstm import ConvGRU, ConvLayer, ConvLSTM, ResidualBlock, clone_state
+from .convlstm import ConvGRU, ConvLayer, ConvLSTM, ResidualBlock, _out_dtype, clone_state
 from .nhwc_ops import tile_like_batch
+
+
+def _sequence_shape(events):
+    """(N, T) of an [N, T, num_bins, H, W] sequence; anything else raises."""
+    if events.dim() != 5:
+        raise ValueError("events must be [N, T, num_bins, H, W]")
+    return events.shape[0], events.shape[1]
+
+
+def _t_major(events, event_scales):
+    """What a layer that does not touch the states needs to run for all T steps in ONE launch: (events as [T*N, num_bins, H, W], the scales
+    repeated to match | None, step) with step(batched, t) = the rows of time step t (t*N .. (t+1)*N) of anything computed from them."""
+    n, t_steps = events.shape[:2]
+    ev_t = events.transpose(0, 1).reshape((t_steps * n,) + tuple(events.shape[2:]))
+    sc_t = event_scales.repeat(t_steps, 1) if event_scales is not None else None
+    return ev_t, sc_t, lambda batched, t: batched[t * n:(t + 1) * n]
 
 
 class UpsampleConvLayer(ConvLayer):
@@ -159,7 +178,7 @@ class UNetRecurrent(nn.Module):
         pack kernels have written them (and the packed tensors would live in one side stream's allocator pool while every stream reads
         them).  Packed here, they are ordered before every side stream by the wait_stream() that follows."""
         for m in self.modules():
-            if isinstance(m, (ConvLayer, ConvLSTM, ConvGRU, ResidualBlock)):
+            if hasattr(type(m), "_weights"):                    # the layers' protocol: everything forward needs packed, now
                 m._weights()
 
     def forward_sequence(self, events, event_scales=None, out=None, overlap=True):
@@ -178,12 +197,9 @@ class UNetRecurrent(nn.Module):
         block can never be handed out again while the side stream still reads it.  Captures into a hipGraph (fork / join through
         events) like the single-stream loop.  (A three-STAGE form -- the decoder half itself split over two chained side streams -- ran
         eagerly but crashed hipGraph's capture_end on ROCm 7.2; whole decoder halves on alternating streams capture fine.)"""
-        if events.dim() != 5:
-            raise ValueError("events must be [N, T, num_bins, H, W]")
-        n, t_steps = events.shape[:2]
-        out_dtype = torch.bfloat16 if (events.dtype == torch.bfloat16 or torch.is_autocast_enabled()) else events.dtype
+        n, t_steps = _sequence_shape(events)
         if out is None:
-            out = torch.empty((n, t_steps, self.num_output_channels) + tuple(events.shape[-2:]), dtype=out_dtype, device=events.device)
+            out = torch.empty((n, t_steps, self.num_output_channels) + tuple(events.shape[-2:]), dtype=_out_dtype(events), device=events.device)
         if self.trainable and torch.is_grad_enabled():
             overlap = False                                     # training: the plain step loop (autograd records every step on this stream)
         if not overlap:
@@ -198,8 +214,7 @@ class UNetRecurrent(nn.Module):
         heads = conv0s = None
         c_head = self.base_num_channels
         if t_steps > 1 and n * t_steps * events.shape[-2] * events.shape[-1] * c_head * 3 <= (2 << 30):
-            ev_t = events.transpose(0, 1).reshape((t_steps * n,) + tuple(events.shape[2:]))          # t-major copy: step t = rows t*N .. (t+1)*N
-            sc_t = event_scales.repeat(t_steps, 1) if event_scales is not None else None
+            ev_t, sc_t, step = _t_major(events, event_scales)
             with torch.autocast("cuda", dtype=torch.bfloat16):
                 heads = self.head(ev_t, scales=sc_t)
                 if n * events.shape[-2] * events.shape[-1] <= 16 * 128 * 128:   # larger steps fill the chip themselves (8 x 256^2: batching the
@@ -220,8 +235,8 @@ class UNetRecurrent(nn.Module):
             if len(held) == n_side + 1:                         # the oldest step's operands may go once cur is ordered after their last reader
                 cur.wait_event(held[0][1])
                 held.pop(0)
-            head, blocks = self._encode(events[:, t], event_scales, head=None if heads is None else heads[t * n:(t + 1) * n],
-                                        conv0=None if conv0s is None else conv0s[t * n:(t + 1) * n])
+            head, blocks = self._encode(events[:, t], event_scales, head=None if heads is None else step(heads, t),
+                                        conv0=None if conv0s is None else step(conv0s, t))
             ready = torch.cuda.Event()
             ready.record(cur)
             side = sides[t % n_side]
@@ -240,7 +255,7 @@ class UNetRecurrent(nn.Module):
         event_scales (this implementation only): float32 [N,2] = (neg_max, pos_max) per sample, e.g. RingLoader(normalize='scales')'s
         batch['event_scales'] -- normalize_batch_voxel (model/train_utils.py:147-166) is then applied by the head while it reads the
         RAW voxel grid; None = x is used as it is."""
-        out_dtype = torch.bfloat16 if (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()) else x.dtype
+        out_dtype = _out_dtype(x)
         head, blocks = self._encode(x, event_scales)
         return {"image": self._decode(head, blocks).to(out_dtype)}
 
@@ -311,9 +326,33 @@ def _graphed_sequence(owner, events, event_scales, extra_key, run, get_states, s
     return res
 
 
-class _RecurrentModel(nn.Module):
+class _Stateful(nn.Module):
+    """What every model class with recurrent states shares: the `states` property (copies out, assigns in) / reset_states the reference's
+    training loop uses, and the hipGraph capture of a whole sequence.  `_states` is the live list of `num_recurrent_units` states: an
+    attribute of the model itself (FireNet) or a property forwarding to its network's (_RecurrentModel)."""
+
+    @property
+    def states(self):
+        return copy_states(self._states)
+
+    @states.setter
+    def states(self, states):
+        self._states = states
+
+    def reset_states(self):
+        self._states = [None] * self.num_recurrent_units
+
+    def _graphed(self, events, event_scales, extra_key, sequence):
+        """forward_sequence(graph=True): reset_states(), then sequence(ev, sc), captured once and replayed (_graphed_sequence)."""
+        def run(ev, sc):
+            self.reset_states()
+            return sequence(ev, sc)
+        return _graphed_sequence(self, events, event_scales, extra_key, run, lambda: self._states, lambda st: setattr(self, "_states", st))
+
+
+class _RecurrentModel(_Stateful):
     """What the reference's recurrent model classes share (model/model.py:194-223, :111-139): the network under its own attribute name
-    (`NET`), the states property / reset_states the training loop uses, the sequence call and its hipGraph capture."""
+    (`NET`), which owns the states, the sequence call and its hipGraph capture."""
 
     NET = None                                             # attribute (and state_dict prefix) of the network
     NET_CLASS = None
@@ -321,7 +360,7 @@ class _RecurrentModel(nn.Module):
     def __init__(self, unet_kwargs, trainable: bool = False):
         super().__init__()
         self.num_bins = unet_kwargs["num_bins"]
-        self.num_encoders = unet_kwargs["num_encoders"]
+        self.num_encoders = self.num_recurrent_units = unet_kwargs["num_encoders"]
         self.trainable = bool(trainable)           # the YAML switch: model: {target: .., params: {unet_kwargs: .., trainable: true}}
         setattr(self, self.NET, self.NET_CLASS(unet_kwargs, trainable=trainable, convgru=True))
 
@@ -330,15 +369,12 @@ class _RecurrentModel(nn.Module):
         return getattr(self, self.NET)
 
     @property
-    def states(self):
-        return copy_states(self.net.states)
+    def _states(self):
+        return self.net.states
 
-    @states.setter
-    def states(self, states):
+    @_states.setter
+    def _states(self, states):
         self.net.states = states
-
-    def reset_states(self):
-        self.net.states = [None] * self.net.num_encoders
 
     def forward(self, event_tensor, event_scales=None):
         return self.net.forward(event_tensor, event_scales)
@@ -359,10 +395,7 @@ class _RecurrentModel(nn.Module):
             raise ValueError("graph=True captures inference only: run training steps with graph=False (or under torch.no_grad())")
         if out is not None:
             raise ValueError("graph=True returns the captured graph's own output buffer; `out` is not supported")
-        def run(ev, sc):
-            self.reset_states()
-            return self.net.forward_sequence(ev, sc, overlap=overlap)
-        return _graphed_sequence(self, events, event_scales, overlap, run, lambda: self.net.states, lambda st: setattr(self.net, "states", st))
+        return self._graphed(events, event_scales, overlap, lambda ev, sc: self.net.forward_sequence(ev, sc, overlap=overlap))
 
 
 class E2VIDRecurrent(_RecurrentModel):
@@ -383,7 +416,7 @@ class FlowNet(_RecurrentModel):
         return UNetFlow.split(super().forward_sequence(events, event_scales, out=out, overlap=overlap, graph=graph))
 
 
-class FireNet(nn.Module):
+class FireNet(_Stateful):
     """model/model.py:264-311: the reference's light reconstruction network, head ConvLayer(num_bins -> 16, 3x3, relu), G1 = ConvGRU(16, 16, 3),
     R1 = ResidualBlock(16, 16), G2, R2, pred = ConvLayer(16 -> 1, 1x1), every layer at full resolution -- on the 16-channel kernels of
     v2v_amd/csrc/v2v_narrow.hpp (each ConvGRU step and each residual block is ONE launch).  Same constructor (the legacy `unet_kwargs`
@@ -416,17 +449,6 @@ class FireNet(nn.Module):
         self.num_recurrent_units = 2
         self.reset_states()
 
-    @property
-    def states(self):
-        return copy_states(self._states)
-
-    @states.setter
-    def states(self, states):
-        self._states = states
-
-    def reset_states(self):
-        self._states = [None] * self.num_recurrent_units
-
     def _head(self, x, event_scales):
         with torch.autocast("cuda", dtype=torch.bfloat16):      # the head hands out bfloat16 NHWC; every later layer keeps it
             return self.head(x, scales=event_scales)
@@ -442,8 +464,7 @@ class FireNet(nn.Module):
     def forward(self, x, event_scales=None):
         """x: [N, num_bins, H, W] float voxel grid (any layout, any H and W) -> {'image': [N,1,H,W]} in x's dtype (bfloat16 under autocast).
         event_scales as in UNetRecurrent.forward: normalize_batch_voxel applied by the input staging kernel on the RAW voxel grid."""
-        out_dtype = torch.bfloat16 if (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()) else x.dtype
-        return {"image": self._body(self._head(x, event_scales)).to(out_dtype)}
+        return {"image": self._body(self._head(x, event_scales)).to(_out_dtype(x))}
 
     def forward_sequence(self, events, event_scales=None, graph=False):
         """The reference's time loop (`for t in range(T): pred = model(events[:, t])`) as one call: events [N,T,num_bins,H,W] -> images
@@ -452,21 +473,14 @@ class FireNet(nn.Module):
         on the one before it through the recurrent states, so there is nothing to overlap.
         graph=True: reset_states(), then the T steps, captured once per (shape, dtype, device, weights) into a hipGraph and replayed from
         then on (as E2VIDRecurrent.forward_sequence): the returned tensor is the graph's static output (clone it to keep it)."""
-        if events.dim() != 5:
-            raise ValueError("events must be [N, T, num_bins, H, W]")
+        n, t_steps = _sequence_shape(events)
         if graph:
-            def run(ev, sc):
-                self.reset_states()
-                return self.forward_sequence(ev, sc)
-            return _graphed_sequence(self, events, event_scales, None, run, lambda: self._states, lambda st: setattr(self, "_states", st))
-        n, t_steps = events.shape[:2]
-        out_dtype = torch.bfloat16 if (events.dtype == torch.bfloat16 or torch.is_autocast_enabled()) else events.dtype
-        out = torch.empty((n, t_steps, 1) + tuple(events.shape[-2:]), dtype=out_dtype, device=events.device)
-        ev_t = events.transpose(0, 1).reshape((t_steps * n,) + tuple(events.shape[2:]))              # t-major: step t = rows t*N .. (t+1)*N
-        sc_t = event_scales.repeat(t_steps, 1) if event_scales is not None else None
+            return self._graphed(events, event_scales, None, self.forward_sequence)
+        out = torch.empty((n, t_steps, 1) + tuple(events.shape[-2:]), dtype=_out_dtype(events), device=events.device)
+        ev_t, sc_t, step = _t_major(events, event_scales)
         heads = self._head(ev_t, sc_t)
         for t in range(t_steps):
-            out[:, t] = self._body(heads[t * n:(t + 1) * n])
+            out[:, t] = self._body(step(heads, t))
         return out
 
 
@@ -526,7 +540,7 @@ class UNet(nn.Module):
         """x: [N, num_bins, H, W] float voxel grid (any layout) -> [N, num_output_channels, H, W] (contiguous, x's dtype; bfloat16 under
         autocast; float32 under training: the values of the bfloat16 kernel output widened exactly).  event_scales as in UNetRecurrent."""
         self.check_size(x.shape[-2], x.shape[-1])
-        out_dtype = torch.bfloat16 if (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()) else x.dtype
+        out_dtype = _out_dtype(x)
         with torch.autocast("cuda", dtype=torch.bfloat16):      # the stem hands out bfloat16; every later layer keeps it
             x = self.encoders[0](x, scales=event_scales)
         blocks = [x]
@@ -576,11 +590,9 @@ class EVFlowNet(nn.Module):
         network has no state, so the loop is the same network on N*T images: time is folded into the batch, `chunk` images per launch
         (default: default_chunk, from the kernels' 2^31-element limit).  Every convolution runs the kernel instance the per-step batch of
         N images gets (nhwc_ops.tile_like_batch), so the result equals the per-step loop bit for bit.  Inference only."""
-        if events.dim() != 5:
-            raise ValueError("events must be [N, T, num_bins, H, W]")
+        n, t_steps = _sequence_shape(events)
         if self.trainable and torch.is_grad_enabled():
             raise ValueError("forward_sequence is inference only: train with the per-step loop or forward() on a folded batch")
-        n, t_steps = events.shape[:2]
         self.unet.check_size(events.shape[-2], events.shape[-1])
         chunk = self.default_chunk(events.shape[-2], events.shape[-1]) if chunk is None else max(1, int(chunk))
         ev = events.reshape((n * t_steps,) + tuple(events.shape[2:]))                  # n-major: image i = (i // T, i % T); a view when contiguous

@@ -600,6 +600,32 @@ int v2v_tc_loss_bwd_hip(const float *image0, const float *image1, const float *p
 int v2v_warp_bilinear_hip(const float *img, const float *flow, int64_t n, int64_t c, int64_t h, int64_t w, float *out, void *stream);
 int v2v_warp_bilinear_adjoint_hip(const float *dout, const float *flow, int64_t n, int64_t c, int64_t h, int64_t w, float *din, void *workspace, void *stream);
 
+/* ---- the LPIPS-VGG perceptual loss (PerceptualSimilarity PNetLin, model/loss.py:95-119): what is not a 64..512-channel convolution --------
+ * Activations and their gradients are bf16 NHWC (16-byte aligned), everything else float32.  Every reduction has a fixed order and there
+ * are no float atomics; a sample's result does not depend on what else is in the launch.
+ * Stem: x [B,Cin,H,W] (Cin 1 or 3; one channel stands for three equal ones; x_dtype V2V_F32 or V2V_BF16), weight [64,3,3,3], bias [64],
+ * shift / scale [3] -> out [B,H,W,64] = relu(conv3x3(s) + bias), s = ((normalize ? 2x - 1 : x) - shift_c) / scale_c inside the image and 0
+ * outside (the zero padding comes AFTER the scaling layer).  Any H, W >= 1.
+ * Stem backward: dz [B,H,W,64] (ReLU-masked) -> dpred float32 [B,Cin,H,W] = (normalize ? 2 : 1) / scale_c * the transposed convolution
+ * 64 -> 3 in float32, the three channels summed when Cin is 1. */
+int v2v_lpips_stem_hip(const void *x, int x_dtype, int64_t B, int64_t Cin, int64_t H, int64_t W, const float *weight, const float *bias, const float *shift,
+                       const float *scale, int normalize, void *out, void *stream);
+int v2v_lpips_stem_bwd_hip(const void *dz, int64_t B, int64_t Cin, int64_t H, int64_t W, const float *weight, const float *scale, int normalize,
+                           float *dpred, void *stream);
+/* 2x2 max-pool x [B,H,W,C] -> out [B,H/2,W/2,C] (H, W even, C a multiple of 8) and its backward: dx [B,H,W,C] gets dy at the FIRST maximum of
+ * each window in row-major order (autograd's rule), plus dtap [B,H,W,C] when that is not NULL -- added in float32, rounded to bf16 once --
+ * and is zeroed where x <= 0 when relu_mask is set (x is then the post-ReLU tensor that was pooled). */
+int v2v_lpips_pool_hip(const void *x, int64_t B, int64_t H, int64_t W, int64_t C, void *out, void *stream);
+int v2v_lpips_pool_bwd_hip(const void *dy, const void *x, const void *dtap, int relu_mask, int64_t B, int64_t H, int64_t W, int64_t C, void *dx, void *stream);
+/* Compare: f0, f1 [n_img,HW,Cc] (Cc 64, 128, 256 or 512), w float32 [Cc]; n = f / (sqrt(sum_c f^2) + 1e-10) per pixel.
+ * Forward: dist[b] += mean_pixels sum_c w_c (n0_c - n1_c)^2 (dist float32 [n_img] is ACCUMULATED into: zero it before the first tap);
+ * workspace: v2v_lpips_compare_workspace_bytes(n_img, HW) bytes, 16-byte aligned.
+ * Backward: df0 [n_img,HW,Cc] bf16 from ddist float32 [n_img]: g_c = 2 w_c (n0_c - n1_c) ddist / HW, df0_c = g_c / (r + eps) -
+ * f0_c (sum_k g_k f0_k) / (r (r + eps)^2), r = |f0|; at r == 0 the second term is defined as 0 (autograd returns NaN there). */
+int64_t v2v_lpips_compare_workspace_bytes(int64_t n_img, int64_t HW);
+int v2v_lpips_compare_fwd_hip(const void *f0, const void *f1, const float *w, int64_t n_img, int64_t HW, int64_t Cc, float *dist, void *workspace, void *stream);
+int v2v_lpips_compare_bwd_hip(const void *f0, const void *f1, const float *w, const float *ddist, int64_t n_img, int64_t HW, int64_t Cc, void *df0, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

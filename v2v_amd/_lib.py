@@ -38,7 +38,9 @@ EXPORTS = ("v2v_version", "v2v_last_error", "v2v_device_count", "v2v_lut_get", "
            "v2v_convgru_packed_bytes", "v2v_convgru_pack_weights_hip", "v2v_convgru_step_hip",
            "v2v_convgru16_packed_elems", "v2v_convgru16_pack_weights_hip", "v2v_convgru16_step_hip", "v2v_resblock16_packed_elems", "v2v_resblock16_pack_weights_hip",
            "v2v_resblock16_nhwc_hip", "v2v_conv_head16_packed_elems", "v2v_conv_head16_pack_weights_hip", "v2v_conv_head16_nhwc_hip",
-           "v2v_tc_loss_workspace_bytes", "v2v_tc_loss_fwd_hip", "v2v_tc_loss_bwd_hip", "v2v_warp_bilinear_hip", "v2v_warp_bilinear_adjoint_hip")
+           "v2v_tc_loss_workspace_bytes", "v2v_tc_loss_fwd_hip", "v2v_tc_loss_bwd_hip", "v2v_warp_bilinear_hip", "v2v_warp_bilinear_adjoint_hip",
+           "v2v_lpips_stem_hip", "v2v_lpips_stem_bwd_hip", "v2v_lpips_pool_hip", "v2v_lpips_pool_bwd_hip", "v2v_lpips_compare_workspace_bytes",
+           "v2v_lpips_compare_fwd_hip", "v2v_lpips_compare_bwd_hip")
 EV_MAKE_VOXEL_DISCRETE, EV_MAKE_VOXEL_INTERP, EV_BILINEAR = 0, 1, 2
 NORM_NONE, NORM_RADIX, NORM_COUNT = 0, 1, 2
 VOXEL_STATS_WORDS = 516
@@ -250,7 +252,15 @@ def lib():
             ("v2v_tc_loss_fwd_hip", C.c_int, [P] * 5 + [I64] * 10 + [C.c_float] * 5 + [P] * 7),
             ("v2v_tc_loss_bwd_hip", C.c_int, [P] * 5 + [I64] * 10 + [C.c_float] * 5 + [P, C.c_int] + [P] * 4),
             ("v2v_warp_bilinear_hip", C.c_int, [P, P] + [I64] * 4 + [P, P]),
-            ("v2v_warp_bilinear_adjoint_hip", C.c_int, [P, P] + [I64] * 4 + [P, P, P])):
+            ("v2v_warp_bilinear_adjoint_hip", C.c_int, [P, P] + [I64] * 4 + [P, P, P]),
+            # the LPIPS-VGG perceptual loss (v2v_amd/lpips.py): stem, max-pool, compare, each forward and backward
+            ("v2v_lpips_stem_hip", C.c_int, [P, C.c_int] + [I64] * 4 + [P] * 4 + [C.c_int, P, P]),
+            ("v2v_lpips_stem_bwd_hip", C.c_int, [P] + [I64] * 4 + [P, P, C.c_int, P, P]),
+            ("v2v_lpips_pool_hip", C.c_int, [P] + [I64] * 4 + [P, P]),
+            ("v2v_lpips_pool_bwd_hip", C.c_int, [P, P, P, C.c_int] + [I64] * 4 + [P, P]),
+            ("v2v_lpips_compare_workspace_bytes", I64, [I64, I64]),
+            ("v2v_lpips_compare_fwd_hip", C.c_int, [P, P, P] + [I64] * 3 + [P, P, P]),
+            ("v2v_lpips_compare_bwd_hip", C.c_int, [P, P, P, P] + [I64] * 3 + [P, P])):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     if L.v2v_version() != ABI_VERSION:

@@ -7,8 +7,10 @@ Functions on them, and the functional drop-in for utils/loss.py's temporal_consi
     seq_loss_fwd / seq_loss_bwd                     the same for all T steps of [B,T,C,H,W] tensors in a fixed number of launches
     temporal_consistency_loss(...)                  utils/loss.py:6-69, same signature and return values
     sequence_losses(...)                            {class name: [B,T]} of v2v_amd/losses.py's classes called step by step, in one Function
+    lpips_stem / lpips_pool / lpips_compare_fwd     the LPIPS-VGG kernels around the backbone's convolutions (v2v_lpips.hpp), each with its
+    (+ _bwd), lpips_vgg(model, pred, target)        backward; lpips_vgg = the distance of a v2v_amd.lpips.LPIPSVGG, mean or per sample
 
-Everything is float32 (other dtypes are widened), on the GPU; gradients go to the processed images only, frames and flow are data.  Rows of a
+Everything but LPIPS' bf16 activations is float32 (other dtypes are widened), on the GPU; gradients go to the processed images only, frames and flow are data.  Rows of a
 [3, N] loss tensor are temporal consistency, l1, l2; a zero weight skips that loss.
 """
 from __future__ import annotations
@@ -235,3 +237,129 @@ def sequence_losses(pred, frame, flow, l1_weight, l2_weight, temporal_consistenc
     out = SeqLossFn.apply(pred, frame, flow, int(L0), float(alpha), _weights(weights))
     names = ("temporal_consistency_loss", "l1_loss", "l2_loss")
     return {names[k]: out[k] for k in (L1, L2, TC) if weights[k] is not None}
+
+
+# ---- LPIPS-VGG: the raw operators around the backbone's convolutions (v2v_amd/csrc/v2v_lpips.hpp; the network is v2v_amd/lpips.py) -----------
+_LP_DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _lp_launch(name, device, *args):
+    with torch.cuda.device(device):
+        _lib.check(getattr(_lib.lib(), name)(*args, _lib.stream_ptr()))
+
+
+def _lp_act(name, t, shape=None):
+    """t must be a contiguous bfloat16 CUDA tensor [B,H,W,C] (of exactly `shape` when given)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 4 or not t.is_contiguous() \
+            or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{name} must be a contiguous bfloat16 CUDA tensor {list(shape) if shape is not None else '[B,H,W,C]'}")
+    return t
+
+
+def _lp_vec(name, t, n, device):
+    """t as a contiguous float32 vector of n elements on `device` (a [1,3,1,1] buffer or a [1,C,1,1] weight is fine)."""
+    if not isinstance(t, torch.Tensor) or t.numel() != n or t.device != device:
+        raise ValueError(f"{name} must hold {n} values on {device}")
+    return t.detach().to(torch.float32).reshape(-1).contiguous()
+
+
+def lpips_stem(x, weight, bias, shift, scale, normalize=False, out=None):
+    """x float32 / bfloat16 [B,1|3,H,W] -> bfloat16 [B,H,W,64] = relu(conv3x3(((2x - 1 if normalize else x) - shift_c) / scale_c) + bias), zero
+    padding AFTER the scaling; weight float32 [64,3,3,3] (a one-channel x stands for three equal channels).  out: write into this tensor."""
+    _lib.require_gpu()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in _LP_DTYPES or x.dim() != 4 or x.shape[1] not in (1, 3):
+        raise ValueError("x must be a float32 or bfloat16 CUDA tensor [B,1|3,H,W]")
+    x = x.detach().contiguous()
+    b, cin, h, w = x.shape
+    if weight.dtype != torch.float32 or tuple(weight.shape) != (64, 3, 3, 3) or weight.device != x.device:
+        raise ValueError("weight must be float32 [64,3,3,3] on x's device")
+    out = torch.empty((b, h, w, 64), dtype=torch.bfloat16, device=x.device) if out is None else _lp_act("out", out, (b, h, w, 64))
+    _lp_launch("v2v_lpips_stem_hip", x.device, _p(x), _LP_DTYPES[x.dtype], b, cin, h, w, _p(weight.detach().contiguous()), _p(_lp_vec("bias", bias, 64, x.device)),
+               _p(_lp_vec("shift", shift, 3, x.device)), _p(_lp_vec("scale", scale, 3, x.device)), int(bool(normalize)), _p(out))
+    return out
+
+
+def lpips_stem_bwd(dz, weight, scale, cin, normalize=False):
+    """dz bfloat16 [B,H,W,64] (ReLU-masked) -> float32 [B,cin,H,W]: the gradient of lpips_stem's x (the three channels summed for cin = 1)."""
+    _lib.require_gpu()
+    _lp_act("dz", dz)
+    b, h, w, c = dz.shape
+    if c != 64 or cin not in (1, 3) or weight.dtype != torch.float32 or tuple(weight.shape) != (64, 3, 3, 3) or weight.device != dz.device:
+        raise ValueError("dz must be [B,H,W,64], cin 1 or 3, weight float32 [64,3,3,3] on dz's device")
+    dpred = torch.empty((b, cin, h, w), dtype=torch.float32, device=dz.device)
+    _lp_launch("v2v_lpips_stem_bwd_hip", dz.device, _p(dz), b, cin, h, w, _p(weight.detach().contiguous()), _p(_lp_vec("scale", scale, 3, dz.device)),
+               int(bool(normalize)), _p(dpred))
+    return dpred
+
+
+def _lp_pool_shape(x):
+    b, h, w, c = x.shape
+    if h % 2 or w % 2 or c % 8:
+        raise ValueError(f"the 2x2 max-pool needs even H and W and C % 8 == 0 (got {tuple(x.shape)})")
+    return b, h, w, c
+
+
+def lpips_pool(x):
+    """2x2 max-pool on NHWC bfloat16: [B,H,W,C] -> [B,H/2,W/2,C]."""
+    _lib.require_gpu()
+    b, h, w, c = _lp_pool_shape(_lp_act("x", x))
+    out = torch.empty((b, h // 2, w // 2, c), dtype=torch.bfloat16, device=x.device)
+    _lp_launch("v2v_lpips_pool_hip", x.device, _p(x), b, h, w, c, _p(out))
+    return out
+
+
+def lpips_pool_bwd(dy, x, dtap=None, relu_mask=False):
+    """Backward of lpips_pool: dy [B,H/2,W/2,C] goes to the first maximum (row-major) of each window of x [B,H,W,C]; + dtap [B,H,W,C] in
+    float32 with ONE rounding to bfloat16; relu_mask: zero where x <= 0 (x is the post-ReLU tensor that was pooled)."""
+    _lib.require_gpu()
+    b, h, w, c = _lp_pool_shape(_lp_act("x", x))
+    _lp_act("dy", dy, (b, h // 2, w // 2, c))
+    if dtap is not None:
+        _lp_act("dtap", dtap, x.shape)
+    dx = torch.empty_like(x)
+    _lp_launch("v2v_lpips_pool_bwd_hip", x.device, _p(dy), _p(x), _p(dtap), int(bool(relu_mask)), b, h, w, c, _p(dx))
+    return dx
+
+
+def _lp_compare_args(f0, f1, w):
+    _lp_act("f0", f0)
+    _lp_act("f1", f1, f0.shape)
+    n, cc = f0.shape[0], f0.shape[3]
+    if cc not in (64, 128, 256, 512) or f1.device != f0.device:
+        raise ValueError("f0 / f1 must have 64, 128, 256 or 512 channels and share a device")
+    return n, f0.shape[1] * f0.shape[2], cc, _lp_vec("w", w, cc, f0.device)
+
+
+def lpips_compare_fwd(f0, f1, w, dist):
+    """dist[b] += mean_pixels sum_c w_c (n0_c - n1_c)^2, n = f / (|f| + 1e-10) per pixel; f0 / f1 bfloat16 [B,H,W,Cc] (the two halves of one
+    tap), w [Cc] (any shape), dist float32 [B], accumulated in place (zeros before the first tap) and returned."""
+    _lib.require_gpu()
+    n, hw, cc, w = _lp_compare_args(f0, f1, w)
+    if not isinstance(dist, torch.Tensor) or dist.dtype != torch.float32 or tuple(dist.shape) != (n,) or not dist.is_contiguous() or dist.device != f0.device:
+        raise ValueError(f"dist must be a contiguous float32 [{n}] tensor on f0's device")
+    ws = torch.empty((_lib.lib().v2v_lpips_compare_workspace_bytes(n, hw),), dtype=torch.uint8, device=f0.device)
+    _lp_launch("v2v_lpips_compare_fwd_hip", f0.device, _p(f0), _p(f1), _p(w), n, hw, cc, _p(dist), _p(ws))
+    return dist
+
+
+def lpips_compare_bwd(f0, f1, w, ddist):
+    """df0 bfloat16 [B,H,W,Cc]: the gradient of sum_b ddist[b] * (lpips_compare_fwd's term of sample b) to f0.  At a pixel with f0 == 0
+    everywhere the norm's own derivative (NaN in autograd) is taken as 0: df0 = g / eps there."""
+    _lib.require_gpu()
+    n, hw, cc, w = _lp_compare_args(f0, f1, w)
+    ddist = _f32("ddist", ddist, (n,))
+    df0 = torch.empty_like(f0)
+    _lp_launch("v2v_lpips_compare_bwd_hip", f0.device, _p(f0), _p(f1), _p(w), _p(ddist), n, hw, cc, _p(df0))
+    return df0
+
+
+def lpips_vgg(model, pred, target, normalize=True, reduce_batch=True):
+    """The LPIPS-VGG distance of model (a v2v_amd.lpips.LPIPSVGG) between pred and target [B,1|3,H,W]: the mean over the batch, or float32 [B]
+    with reduce_batch=False; the gradient goes to pred only.  Time has no state in this loss: a sequence [N,T,...] is evaluated as the
+    batch [N*T,...] (reshape before the call), there is no step loop to fold."""
+    dist = model(pred, target, normalize=normalize)
+    return dist.mean() if reduce_batch else dist

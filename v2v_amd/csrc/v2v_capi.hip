@@ -270,6 +270,9 @@ static int esim_launch_impl(const void *frames, int in_dtype, int64_t B, int64_t
     const size_t in_sz = in_dtype == V2V_U8 ? 1 : 4, out_sz = out_dtype == V2V_F32 ? 4 : 8;
     if (!aligned(frames, in_sz) || !aligned(out_voxel, out_sz) || !aligned(params, 8) || (out_counts && !aligned(out_counts, 8)))
         return fail(V2V_ERR_ALIGN, "buffer not aligned to its element size");
+    // the float32 4-pixel device-noise instances address a lane's pixels inside a frame / a plane with a 32-bit byte offset on a
+    // scalar base (H*W <= 2^30 above covers the frames)
+    if ((uint64_t)out_plane_size * out_sz > ((uint64_t)1 << 32)) return fail(V2V_ERR_SHAPE, "out_plane_size above 4 GiB per plane");
     if (B == 0) return V2V_OK;
 
     // 4 (or 2) pixels per work-item when every row segment a lane touches is 16-byte (8-byte) fp32 / 4-byte (2-byte) u8 aligned

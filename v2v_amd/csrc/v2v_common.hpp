@@ -25,7 +25,10 @@ namespace v2v {
 #define V2V_V2E_MIN_WAVES 3  // __launch_bounds__ occupancy target of the v2e kernel (waves per SIMD): 2 -> 3 waves is worth 12 % (2.27 -> 2.06 ms, config 3) despite ~25 spilled dwords; 4 spills the loop (3.3 ms)
 #endif
 #ifndef V2V_ESIM_ASYM4
-#define V2V_ESIM_ASYM4 1   // general device-noise ESIM instances: by-polarity loop only, 2-frame ring, 4 waves per SIMD
+#define V2V_ESIM_ASYM4 1   // general device-noise ESIM instances: by-polarity loop only, 4 waves per SIMD
+#endif
+#ifndef V2V_ESIM_F32_RING
+#define V2V_ESIM_F32_RING 4  // frames in flight per work-item of the float32 4-pixel device-noise ESIM instances (even; 4 waves per SIMD)
 #endif
 #ifndef V2V_MIN_WAVES
 #define V2V_MIN_WAVES 1
@@ -79,6 +82,19 @@ __device__ __forceinline__ Raw<IN, VEC> load_raw(const void *base, int64_t elem_
     return r;
 }
 
+// The same load with the address split into a WAVE-UNIFORM element offset (clip and frame: scalar registers) and the lane's own byte
+// offset (its pixels: one 32-bit vector register, computed once): the load takes the scalar base + 32-bit offset form and no 64-bit
+// lane address has to live in vector registers.
+template <int IN, int VEC, bool NT = (V2V_NT_LOADS != 0)>
+__device__ __forceinline__ Raw<IN, VEC> load_raw_at(const void *base, int64_t uniform_elem_off, uint32_t &lane_byte_off)
+{
+    const unsigned char *ub = static_cast<const unsigned char *>(base) + uniform_elem_off * (int64_t)(IN == kInF32 ? 4 : 1);
+    // (the lane offset is made opaque IN PLACE -- hence the reference: the compiler would otherwise hoist base + lane offset out of the
+    // time loop as a 64-bit vector pair and add the uniform part per lane)
+    asm volatile("" : "+v"(lane_byte_off));
+    return load_raw<IN, VEC, NT>(ub + lane_byte_off, 0);
+}
+
 template <int IN> struct LutT { using type = double; };
 template <> struct LutT<kInF32> { using type = float; };
 
@@ -125,6 +141,15 @@ __device__ __forceinline__ void store_vec(void *out, int64_t off, const T (&v)[V
         o[0] = v[0];
     }
 #endif
+}
+
+// store_vec with the address split like load_raw_at: wave-uniform element offset (clip, plane) + the lane's byte offset inside a plane
+template <int VEC, typename T>
+__device__ __forceinline__ void store_vec_at(void *out, int64_t uniform_elem_off, uint32_t &lane_byte_off, const T (&v)[VEC])
+{
+    unsigned char *ub = reinterpret_cast<unsigned char *>(static_cast<T *>(out) + uniform_elem_off);
+    asm volatile("" : "+v"(lane_byte_off));
+    store_vec<VEC, T>(ub + lane_byte_off, 0, v);
 }
 
 }  // namespace v2v

@@ -117,7 +117,7 @@ __device__ __forceinline__ void pix_logs(const Raw<IN, VEC> &r, const typename L
 //          converts (~28 of 213 VALU instructions per 4-pixel step of the noise-on launch, SQ_INSTS_VALU).
 // The GENERAL device-noise instances (4 pixels per work-item, float32 grid, thresholds unknown to the host -- per-clip device
 // parameters as the dataset draws them, data/v2v_datasets.py:368-386) carry ONE time loop, the by-polarity one: it is exact for
-// C+ == C- too, and without the second (symmetric) loop and with a 2-frame ring the kernel fits 128 VGPRs = 4 waves per SIMD.
+// C+ == C- too, and without the second (symmetric) loop the kernel fits 128 VGPRs = 4 waves per SIMD.
 template <int VEC, int RNG, bool NOISE, bool OUT64, bool EXT, bool SYMONLY>
 constexpr bool esim_asym4() { return V2V_ESIM_ASYM4 && NOISE && RNG == kRngPhilox && VEC == 4 && !OUT64 && !EXT && !SYMONLY; }
 
@@ -128,13 +128,17 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
 {
     static_assert(!FIDX || BIN == kBinSum, "the frame index row uses the dynamic LDS region the bilinear tables live in");
     constexpr bool ASYM4 = esim_asym4<VEC, RNG, NOISE, OUT64, EXT, SYMONLY>();
-    // SYMONLY (V2V_FLAG_SYMMETRIC: the caller guarantees C+ == C- for every clip): compiled without the asymmetric loop and with a
-    // 2-frame ring, which fits 128 VGPRs = 4 waves per SIMD (-4.6 % on the headline, same box); a clip that breaks the
-    // guarantee gets NaN planes (loud, never a wrong count)
+    // SYMONLY (V2V_FLAG_SYMMETRIC: the caller guarantees C+ == C- for every clip): compiled without the asymmetric loop, which fits
+    // 128 VGPRs = 4 waves per SIMD (-4.6 % on the headline, same box); a clip that breaks the guarantee gets NaN planes (loud, never
+    // a wrong count)
+    // F32W4 (the float32 instances at 4 waves per SIMD): 4 frames in flight like everyone else.  They ran a 2-frame ring as long as the
+    // 4-frame one cost 128 VGPRs + 32..48 bytes of scratch; with the lane addresses below as 32-bit offsets on a scalar base it fits
+    // (112..125 VGPRs, no scratch) and is worth 2 % on the headline (profiles/esim_ring4/)
     // (uint8 frames are 4 bytes per lane and frame: their ring stays kDepth deep -- with 2 in flight config 4's shape lost 20 %)
     // (1 pixel per work-item: 8 frames in flight -- at 3 waves per SIMD a step is short and 4 frames of look-ahead do not cover the
     // memory latency; -2 % at the training shape, same box)
-    constexpr int kRing = ((SYMONLY || ASYM4) && IN == kInF32) ? 2 : VEC == 1 ? 8 : kDepth;
+    constexpr bool F32W4 = (SYMONLY || ASYM4) && IN == kInF32;
+    constexpr int kRing = F32W4 ? V2V_ESIM_F32_RING : VEC == 1 ? 8 : kDepth;
     static_assert(NOISE || !EXT, "external noise needs the noise path");
     using lut_t = typename LutT<IN>::type;
     using acc_t = typename std::conditional<OUT64, double, float>::type;
@@ -267,7 +271,19 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
     }
     const uint64_t seed_ = a.clip_keys ? a.clip_keys[2 * clip] : a.seed;
     const uint32_t clip_id = a.clip_keys ? (uint32_t)a.clip_keys[2 * clip + 1] : (uint32_t)(a.clip_id0 + (uint64_t)clip);
-    const int64_t in_base = (FIDX ? a.clip_offsets[clip] : (int64_t)clip * a.clip_stride) + p0;
+    // F32W4: addresses = a wave-uniform part (clip, frame / plane: scalar registers) + the lane's own 32-bit byte offset (the C entry
+    // bounds H*W and the plane size), so that no 64-bit lane address lives across the time loop (docs/experiments, "scalar-base
+    // addresses": timing-neutral by itself; here it is wanted for its registers -- 4 to 6 per instance, what the 4-frame ring was short of)
+    uint32_t lane_in = p0 * (uint32_t)(IN == kInF32 ? 4 : 1), lane_out = (uint32_t)pix_off * (uint32_t)sizeof(acc_t);
+    const int64_t in_base = (FIDX ? a.clip_offsets[clip] : (int64_t)clip * a.clip_stride) + (F32W4 ? 0 : p0);
+    auto load_frame = [&](int f) {
+        if constexpr (F32W4) return load_raw_at<IN, VEC>(a.frames, in_base + foff(f), lane_in);
+        else return load_raw<IN, VEC>(a.frames, in_base + foff(f));
+    };
+    auto store_plane = [&](int64_t uniform_off, const acc_t (&v)[VEC]) {       // uniform_off: element offset of the plane (clip, bin)
+        if constexpr (F32W4) store_vec_at<VEC, acc_t>(a.out, uniform_off, lane_out, v);
+        else store_vec<VEC, acc_t>(a.out, uniform_off + pix_off, v);
+    };
 
     // ---- per-pixel state
     double pot[VEC];
@@ -319,7 +335,7 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
 
     lut_t lprev[VEC];
     {
-        const Raw<IN, VEC> r0 = load_raw<IN, VEC>(a.frames, in_base + foff(0));
+        const Raw<IN, VEC> r0 = load_frame(0);
         pix_logs<IN, VEC>(r0, s_lut, lprev);
     }
 
@@ -329,7 +345,7 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
     for (int j = 0; j < VEC; ++j) { acc_lo[j] = 0; acc_hi[j] = 0; }
     // plane of the lower bin leaves the accumulators, the upper bin becomes the lower one
     auto flush_lower = [&](int seg) {
-        store_vec<VEC, acc_t>(a.out, ((int64_t)clip * a.Tb + seg) * a.out_plane + pix_off, acc_lo);
+        store_plane(((int64_t)clip * a.Tb + seg) * a.out_plane, acc_lo);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) { acc_lo[j] = acc_hi[j]; acc_hi[j] = 0; }
     };
@@ -340,7 +356,7 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
     }
     int sub = 0, plane = 0;   // SUM: pairs accumulated into the current plane, plane index
     const int64_t planes_per_clip = (BIN == kBinSum) ? (a.K / a.fpb) : a.Tb;
-    const int64_t out_base = (int64_t)clip * planes_per_clip * a.out_plane + pix_off;
+    const int64_t out_base = (int64_t)clip * planes_per_clip * a.out_plane;        // wave-uniform
     uint32_t n_all = 0, n_off = 0;
     const bool want_counts = a.counts != nullptr;
 
@@ -540,7 +556,7 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
         }
         if constexpr (BIN == kBinSum) {
             if (++sub == a.fpb) {                                      // wave-uniform
-                store_vec<VEC, acc_t>(a.out, out_base + (int64_t)plane * a.out_plane, acc_lo);
+                store_plane(out_base + (int64_t)plane * a.out_plane, acc_lo);
                 if constexpr (STATS) {
                     if (want_stats) {                                  // wave-uniform
 #pragma unroll
@@ -580,7 +596,7 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
 #pragma unroll
         for (int u = 0; u < kRing; ++u) {
             const int f = (1 + u <= a.K) ? 1 + u : a.K;
-            ring[u] = load_raw<IN, VEC>(a.frames, in_base + foff(f));
+            ring[u] = load_frame(f);
         }
         if constexpr (VEC == 1) pix_logs<IN, VEC>(ring[0], s_lut, ln_pre);
         int k0 = 0;
@@ -590,7 +606,7 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
                 const int k = k0 + u;
                 step(sym_tag, hot_tag, std::integral_constant<int, (u & 1)>{}, k, ring[u], ring[(u + 1) % kRing]);
                 const int fn = k + 1 + kRing;
-                ring[u] = load_raw<IN, VEC>(a.frames, in_base + foff(fn <= a.K ? fn : a.K));
+                ring[u] = load_frame(fn <= a.K ? fn : a.K);
             });
         }
         tail(sym_tag, hot_tag, k0, ring);

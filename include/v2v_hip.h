@@ -568,6 +568,37 @@ int v2v_hyper_dynconv_pack_weights_hip(const float *weight, int64_t Cin, int64_t
 int v2v_hyper_dynconv_nhwc_hip(const void *x, const float *atoms, const void *packed, const float *bias, int relu, int64_t B, int64_t H, int64_t W,
                                int64_t Cin, int64_t Cout, int n_atoms, int ks, void *out, void *stream);
 
+/* ---- the dynamic decoder's backward (training; v2v_amd/train.py DynamicUpsampleFn).  No atomics: two runs give equal bits.  These entry
+ * points keep their error text apart from v2v_last_error(): v2v_hyper_train_last_error() (thread-local). ---------------------------------
+ * With dz = relu'(dout) bf16 [M = B*H*W][128], x = the upsampled input bf16 [B,H,W,256], atoms float32 [B,H,W,25,6]:
+ *   pack_t   compositional_coefficients float32 [128,1536] -> the transposed bf16 stream of df (128 * 1536 elements)
+ *   df       dF[p][c][m] = sum_o dz[p][o] W[o][c*6+m], stored bf16 as [M][c / 64][m][c % 64] (1536 per pixel), one rounding
+ *   datoms   dAtoms[p][l][m] = sum_c x[p + offset_l][c] dF[p][c][m], float32 [M,25,6], zero padding as the forward
+ *   dx       dX[q][c] = sum_l sum_m atoms[q - offset_l][l][m] dF[q - offset_l][c][m], bf16 [B,H,W,256], one rounding
+ *   wgrad    dW[o][c*6+m] = sum_p dz[p][o] bf16(F[p][c][m]) with F recomputed as the forward computes it, db[o] = sum_p dz[p][o]; float32;
+ *            workspace of v2v_hyper_dynconv_wgrad_workspace_bytes (16-byte aligned; -1: shape not taken)
+ * Any B, H, W >= 1 with B*H*W*1536 below 2^33. */
+const char *v2v_hyper_train_last_error(void);
+int v2v_hyper_dynconv_pack_t_hip(const float *weight, void *packed_t, void *stream);
+int v2v_hyper_dynconv_df_hip(const void *dz, const void *packed_t, int64_t M, void *dF, void *stream);
+int v2v_hyper_dynconv_datoms_hip(const void *x, const void *dF, int64_t B, int64_t H, int64_t W, float *datoms, void *stream);
+int v2v_hyper_dynconv_dx_hip(const float *atoms, const void *dF, int64_t B, int64_t H, int64_t W, void *dx, void *stream);
+int64_t v2v_hyper_dynconv_wgrad_workspace_bytes(int64_t B, int64_t H, int64_t W);
+int v2v_hyper_dynconv_wgrad_hip(const void *dz, const void *x, const float *atoms, int64_t B, int64_t H, int64_t W, void *workspace, float *dw, float *db,
+                                void *stream);
+/* BatchNorm on batch statistics over the M rows of z bf16 [M][Cs] (Cs % 8 == 0; columns >= Cv are padding: outputs and gradients zero).
+ *   stats   mean, biased variance and rstd = 1 / sqrt(var + eps) per column (float32 [Cs] each; two passes, sums carried in float64)
+ *   apply   out = gamma (z - mean) rstd + beta [-> tanh], bf16 [M][Cs]
+ *   bwd     dy (bf16, or float32 with dy_is_f32) -> sums float32 [4][Cs] = (dbeta, dgamma, sum over the rows of dz before its rounding, unused)
+ *           and dz bf16 [M][Cs] = gamma rstd (dpre - dbeta / M - xhat dgamma / M), dpre = dy [(1 - tanh(gamma xhat + beta)^2) with tanh_out]
+ * atoms_bwd: dpre[p][m*12+k] = (1 - tanh(pre[p][m*12+k])^2) sum_l datoms[p][l][m] bases[k][l], float32 [M][128], columns 72..127 zero. */
+int v2v_hyper_bn_stats_hip(const void *z, int64_t M, int64_t Cs, float eps, float *mean, float *var, float *rstd, void *stream);
+int v2v_hyper_bn_apply_hip(const void *z, const float *mean, const float *rstd, const float *gamma, const float *beta, int64_t M, int64_t Cs, int64_t Cv,
+                           int tanh_out, void *out, void *stream);
+int v2v_hyper_bn_bwd_hip(const void *dy, int dy_is_f32, const void *z, const float *mean, const float *rstd, const float *gamma, const float *beta, int64_t M,
+                         int64_t Cs, int64_t Cv, int tanh_out, float *sums, void *dz, void *stream);
+int v2v_hyper_atoms_bwd_hip(const float *datoms, const void *pre, const float *bases, int64_t M, float *dpre, void *stream);
+
 /* ---- the image losses of training (utils/loss.py:6-69 temporal consistency; model/loss.py l1_loss, l2_loss), float32 ----------------------
  * One call serves a list of images (a, b), a < outer, b < inner: image1 / processed1 of image (a, b) start at element a * img_stride_outer +
  * b * img_stride_inner and are contiguous [c,h,w]; the temporal term exists for b >= tc_first, and image0 / processed0 / flow ([2,h,w],

@@ -35,6 +35,9 @@ EXPORTS = ("v2v_version", "v2v_last_error", "v2v_device_count", "v2v_lut_get", "
            "v2v_upsample2x_cat_bwd_nhwc_hip", "v2v_conv1x1_bwd_cout_workspace_bytes", "v2v_conv1x1_bwd_cout_nhwc_hip", "v2v_conv_nhwc_like_hip",
            "v2v_hyper_context_hip", "v2v_hyper_context_conv_hip", "v2v_tanh_bf16_hip", "v2v_hyper_atoms_hip", "v2v_hyper_dynconv_packed_elems", "v2v_hyper_dynconv_pack_weights_hip",
            "v2v_hyper_dynconv_nhwc_hip",
+           "v2v_hyper_train_last_error", "v2v_hyper_dynconv_pack_t_hip", "v2v_hyper_dynconv_df_hip", "v2v_hyper_dynconv_datoms_hip", "v2v_hyper_dynconv_dx_hip",
+           "v2v_hyper_dynconv_wgrad_workspace_bytes", "v2v_hyper_dynconv_wgrad_hip", "v2v_hyper_bn_stats_hip", "v2v_hyper_bn_apply_hip", "v2v_hyper_bn_bwd_hip",
+           "v2v_hyper_atoms_bwd_hip",
            "v2v_convgru_packed_bytes", "v2v_convgru_pack_weights_hip", "v2v_convgru_step_hip",
            "v2v_convgru16_packed_elems", "v2v_convgru16_pack_weights_hip", "v2v_convgru16_step_hip", "v2v_resblock16_packed_elems", "v2v_resblock16_pack_weights_hip",
            "v2v_resblock16_nhwc_hip", "v2v_conv_head16_packed_elems", "v2v_conv_head16_pack_weights_hip", "v2v_conv_head16_nhwc_hip",
@@ -233,6 +236,18 @@ def lib():
             ("v2v_hyper_dynconv_packed_elems", I64, [I64, I64, C.c_int, C.c_int]),
             ("v2v_hyper_dynconv_pack_weights_hip", C.c_int, [P, I64, I64, C.c_int, P, P]),
             ("v2v_hyper_dynconv_nhwc_hip", C.c_int, [P, P, P, P, C.c_int] + [I64] * 5 + [C.c_int, C.c_int, P, P]),
+            # the dynamic decoder's backward and BatchNorm on batch statistics (v2v_amd/train.py DynamicUpsampleFn)
+            ("v2v_hyper_train_last_error", C.c_char_p, []),
+            ("v2v_hyper_dynconv_pack_t_hip", C.c_int, [P, P, P]),
+            ("v2v_hyper_dynconv_df_hip", C.c_int, [P, P, I64, P, P]),
+            ("v2v_hyper_dynconv_datoms_hip", C.c_int, [P, P, I64, I64, I64, P, P]),
+            ("v2v_hyper_dynconv_dx_hip", C.c_int, [P, P, I64, I64, I64, P, P]),
+            ("v2v_hyper_dynconv_wgrad_workspace_bytes", I64, [I64, I64, I64]),
+            ("v2v_hyper_dynconv_wgrad_hip", C.c_int, [P, P, P, I64, I64, I64, P, P, P, P]),
+            ("v2v_hyper_bn_stats_hip", C.c_int, [P, I64, I64, C.c_float, P, P, P, P]),
+            ("v2v_hyper_bn_apply_hip", C.c_int, [P] * 5 + [I64] * 3 + [C.c_int, P, P]),
+            ("v2v_hyper_bn_bwd_hip", C.c_int, [P, C.c_int] + [P] * 5 + [I64] * 3 + [C.c_int, P, P, P]),
+            ("v2v_hyper_atoms_bwd_hip", C.c_int, [P, P, P, I64, P, P]),
             # the ConvGRU step (two launches behind one call)
             ("v2v_convgru_packed_bytes", C.c_int, [I64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
             ("v2v_convgru_pack_weights_hip", C.c_int, [P, P, P, I64, P, P, P]),
@@ -269,11 +284,12 @@ def lib():
     return L
 
 
-def check(rc: int):
-    """Map a v2v_status to the exception the reference would raise at the same spot."""
+def check(rc: int, last_error: str = "v2v_last_error"):
+    """Map a v2v_status to the exception the reference would raise at the same spot.  last_error: the entry point that holds the text
+    (the dynamic decoder's training entry points keep theirs in v2v_hyper_train_last_error)."""
     if rc == OK:
         return
-    msg = lib().v2v_last_error().decode()
+    msg = getattr(lib(), last_error)().decode()
     if rc == ERR_BINS:
         raise AssertionError(msg)            # reference: `assert (N-1) % (num_bins*frames_per_bin) == 0`
     if rc in (ERR_SHAPE, ERR_DTYPE, ERR_MODE, ERR_PARAM, ERR_NULL, ERR_ALIGN):

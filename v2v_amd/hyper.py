@@ -11,7 +11,10 @@ reference checkpoint loads with strict=True:
 
 Configuration covered = config/train_v2v_hyper_10k.yaml / config/test_hypere2vid_original.yaml: skip 'sum', 'convlstm', kernel_size 5, base 32,
 multiplier 2, norm none, use_upsample_conv, 3 encoders, one output channel; anything else raises ValueError (no stock fallback).  Inference
-only: eval mode (BatchNorm runs on its running statistics, folded into the convolutions' packed weights) under torch.no_grad().
+by default: eval mode (BatchNorm runs on its running statistics, folded into the convolutions' packed weights) under torch.no_grad().
+trainable=True (HyperE2VID / UNetRecurrent / DynamicUpsampleLayer) adds training: in .train() mode the dynamic layer runs BatchNorm on the
+batch's statistics (and updates the running ones), and under grad it records v2v_amd.train.DynamicUpsampleFn like every other layer
+records its Function; .eval() stays the inference path.
 
 What runs per time step for the dynamic layer (raw operators in v2v_amd/nhwc_ops.py, kernels in v2v_amd/csrc/v2v_hyper.hpp):
     hyper_context_nhwc8 -> context_conv_nhwc (context_fusion.conv) -> conv_nhwc (bases_net.0 + folded BatchNorm) -> tanh_bf16_ ->
@@ -29,8 +32,9 @@ import torch.nn as nn
 
 from . import unet as _unet
 from .convlstm import _fold_sum_skip, _nchw_out, _nhwc_in, _out_dtype
-from .nhwc_ops import (context_conv_nhwc, conv_nhwc, dynconv_nhwc, hyper_atoms, hyper_context_nhwc8, pack_conv_weights, pack_dynconv_weights,
-                       packed_weights, tanh_bf16_, upsample2x_nhwc)
+from .nhwc_ops import (context_conv_nhwc, conv_nhwc, dynconv_nhwc, hyper_atoms, hyper_context_nhwc8, pack_conv_weights, pack_dgrad_weights,
+                       pack_dynconv_weights, pack_dynconv_weights_t, packed_weights, tanh_bf16_, upsample2x_nhwc)
+from .train import DynamicUpsampleFn
 
 
 def fourier_bessel_bases(kernel_size: int, num_bases: int) -> torch.Tensor:
@@ -96,11 +100,14 @@ class ConvolutionalContextFusion(nn.Module):
     def _weights(self):
         return None                                                  # context_conv_nhwc reads the float32 weight itself
 
-    def forward(self, ev_tensor, prev_recs):
+    def stage(self, ev_tensor, prev_recs):
+        """cat(events, prev_recs) at 1/4 scale as bfloat16 NHWC8: the convolution's input (what its weight gradient reads in training)."""
         if ev_tensor.shape[1] + 1 != self.conv.in_channels:
             raise ValueError(f"context fusion was built for {self.conv.in_channels - 1} event bins + 1 image, got {ev_tensor.shape[1]} bins")
-        x8 = hyper_context_nhwc8(ev_tensor.detach().float(), prev_recs.detach().float().contiguous())
-        return context_conv_nhwc(x8, self.conv.weight.detach().float(), self.conv.bias)
+        return hyper_context_nhwc8(ev_tensor.detach().float(), prev_recs.detach().float().contiguous())
+
+    def forward(self, ev_tensor, prev_recs):
+        return context_conv_nhwc(self.stage(ev_tensor, prev_recs), self.conv.weight.detach().float(), self.conv.bias)
 
 
 class DynamicAtomGeneration(nn.Module):
@@ -143,6 +150,28 @@ class DynamicAtomGeneration(nn.Module):
                                       lambda *_, i=i, pad_to=pad_to: self._fold(i, pad_to)))   # _fold reads the same six tensors from the modules
         return out
 
+    @staticmethod
+    def _pad_rows(t, pad_to: int):
+        return t if pad_to <= t.shape[0] else torch.cat([t, t.new_zeros((pad_to - t.shape[0],) + tuple(t.shape[1:]))])
+
+    def _train_weights(self):
+        """Training mode: ((packed, bias) of bases_net.0, (packed, bias) of bases_net.3) WITHOUT the BatchNorm fold (the statistics are
+        the batch's), each pack keyed on its convolution weight alone, beside the folded entries; 72 outputs still padded to 128."""
+        out = []
+        for i, pad_to in ((0, 64), (3, 128)):
+            conv = self.bases_net[i]
+            packed = packed_weights(self._packed, f"bases_net.{i}.train", conv.weight,
+                                    lambda w, pad_to=pad_to: pack_conv_weights(self._pad_rows(w.float(), pad_to).contiguous()))
+            bias = conv.bias.detach().float() if conv.bias is not None else conv.weight.new_zeros(conv.out_channels, dtype=torch.float32)
+            out.append((packed, self._pad_rows(bias, pad_to).contiguous()))
+        return out
+
+    def _dgrad_weights(self, i: int):
+        """The transposed convolution's packed weights of bases_net.i (i = 0 or 3; the 72 outputs padded to 128 as the forward pads them)."""
+        pad_to = 64 if i == 0 else 128
+        return packed_weights(self._packed, f"bases_net.{i}.dgrad", self.bases_net[i].weight,
+                              lambda w: pack_dgrad_weights(self._pad_rows(w.float(), pad_to).contiguous()))
+
     def forward(self, context):
         (p0, b0), (p1, b1) = self._weights()
         hid = tanh_bf16_(conv_nhwc(context, p0, b0, 3))
@@ -175,6 +204,11 @@ class DynamicConv(nn.Module):
     def _weights(self):
         return packed_weights(self._packed, "compositional_coefficients", self.compositional_coefficients, _pack_coefficients)
 
+    def _weights_t(self):
+        """The transposed stream the backward's dF kernel reads."""
+        return packed_weights(self._packed, "compositional_coefficients.t", self.compositional_coefficients,
+                              lambda w: pack_dynconv_weights_t(w.float().contiguous()))
+
     def forward(self, x, atoms, relu=False):
         return dynconv_nhwc(x, atoms, self._weights(), self.bias.detach().float(), relu=relu)
 
@@ -184,10 +218,12 @@ class DynamicUpsampleLayer(nn.Module):
     previous reconstruction, then ReLU.  forward(x, ev_tensor, prev_recs, skip=None): skip = the decoder's sum skip, folded into the
     upsampling kernel (layer(x, ev, prev, skip) == layer(x + skip, ev, prev)).  x [B,256,h,w]: channels-last bfloat16 is consumed and produced
     in place, anything else goes through the layout kernel and comes back NCHW in x's dtype.  ev_tensor [B,bins,8h,8w] float of any layout,
-    prev_recs [B,1,8h,8w].  Inference only: eval mode and no grad, else RuntimeError."""
+    prev_recs [B,1,8h,8w].  trainable=False: eval mode and no grad, else RuntimeError.  trainable=True: .train() runs BatchNorm on the
+    batch's statistics and updates the running ones (under grad it records v2v_amd.train.DynamicUpsampleFn; events and prev_recs get no
+    gradient); .eval() is the inference path, without a backward."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, activation="relu", in_fuse_channels=6, out_fuse_channels=32,
-                 num_atoms=6):
+                 num_atoms=6, trainable: bool = False):
         super().__init__()
         if activation not in ("relu", None):
             raise ValueError("the dynamic layer's epilogue covers activation 'relu' or None")
@@ -196,13 +232,18 @@ class DynamicUpsampleLayer(nn.Module):
                                                              in_context_channels=out_fuse_channels, hid_channels=64, stride=stride)
         self.dynamic_conv = DynamicConv(in_channels, out_channels, kernel_size=kernel_size, stride=stride, padding=padding, num_atoms=num_atoms)
         self.relu = activation == "relu"
-        self.trainable = False
+        self.trainable = bool(trainable)
 
     def _weights(self):
         """Everything forward needs packed, now (on the current stream)."""
         return self.context_fusion._weights(), self.dynamic_atom_generation._weights(), self.dynamic_conv._weights()
 
     def _check_mode(self, x):
+        if self.trainable:
+            if not self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+                raise RuntimeError("v2v_amd.hyper.DynamicUpsampleLayer has no backward in eval mode (BatchNorm folded into the convolutions): "
+                                   "call .train() to train it, or run it under torch.no_grad()")
+            return
         if self.training:
             raise RuntimeError("v2v_amd.hyper.DynamicUpsampleLayer runs BatchNorm on its running statistics only: call .eval() first "
                                "(batch-statistics BatchNorm is not implemented, and using running statistics in training mode would differ "
@@ -223,6 +264,18 @@ class DynamicUpsampleLayer(nn.Module):
             raise ValueError(f"the 1/4-scale context must meet the x2-upsampled input: events / prev_recs must be 8x the size of x "
                              f"(x {tuple(x.shape[-2:])}, events {tuple(ev_tensor.shape[-2:])}, prev_recs {tuple(prev_recs.shape[-2:])})")
         x, skip, nhwc_io = _fold_sum_skip(x, skip)
+        if self.training:                                                # trainable (else _check_mode raised): BatchNorm on batch statistics
+            train = torch.is_grad_enabled()
+            xn, sn = _nhwc_in(x, nhwc_io, train), None if skip is None else skip.permute(0, 2, 3, 1)
+            if train:
+                fus, gen, dyn = self.context_fusion, self.dynamic_atom_generation, self.dynamic_conv
+                net = gen.bases_net
+                out = DynamicUpsampleFn.apply(xn, sn, ev_tensor, prev_recs, fus.conv.weight, fus.conv.bias, net[0].weight, net[0].bias, net[1].weight,
+                                              net[1].bias, net[3].weight, net[3].bias, net[4].weight, net[4].bias, dyn.compositional_coefficients,
+                                              dyn.bias, self)
+            else:
+                out = DynamicUpsampleFn.kernels(xn, sn, ev_tensor, prev_recs, self)[0]
+            return _nchw_out(out, x, nhwc_io)
         xn, sn = _nhwc_in(x, nhwc_io, False), None if skip is None else skip.permute(0, 2, 3, 1)
         atoms = self.atoms(ev_tensor, prev_recs)
         out = self.dynamic_conv(upsample2x_nhwc(xn, sn), atoms, relu=self.relu)
@@ -231,9 +284,9 @@ class DynamicUpsampleLayer(nn.Module):
 
 class UNetRecurrent(_unet.UNetRecurrent):
     """model/hyper_model.py:138-196: v2v_amd.unet.UNetRecurrent whose decoders[0] is the DynamicUpsampleLayer when use_dynamic_decoder is
-    true.  forward(x, prev_recs=None) -> {'image'}; prev_recs None = zeros.  Inference only."""
+    true.  forward(x, prev_recs=None) -> {'image'}; prev_recs None = zeros.  trainable: as the base class, and for the dynamic decoder."""
 
-    def __init__(self, unet_kwargs):
+    def __init__(self, unet_kwargs, trainable: bool = False):
         kw = dict(unet_kwargs)
         self_dynamic = bool(kw.pop("use_dynamic_decoder", False))
         if kw.get("num_output_channels", 1) != 1:
@@ -242,12 +295,12 @@ class UNetRecurrent(_unet.UNetRecurrent):
             raise ValueError("the device kernels cover kernel_size 5, base_num_channels 32, channel_multiplier 2 (config/train_v2v_hyper_10k.yaml)")
         if self_dynamic and kw.get("num_encoders") != 3:
             raise ValueError("the dynamic decoder needs num_encoders 3: its 1/4-scale context meets decoders[0]'s output only at three levels")
-        super().__init__(kw, trainable=False)
+        super().__init__(kw, trainable=trainable)
         self.use_dynamic_decoder = self_dynamic
         if self_dynamic:
             k = self.kernel_size
             self.decoders[0] = DynamicUpsampleLayer(self.encoder_output_sizes[-1], self.encoder_input_sizes[-1], kernel_size=k, padding=k // 2,
-                                                    in_fuse_channels=1 + self.num_bins)
+                                                    in_fuse_channels=1 + self.num_bins, trainable=trainable)
 
     def _decode(self, head, blocks, ev_tensor=None, prev_recs=None):
         x = blocks[-1]
@@ -265,7 +318,7 @@ class UNetRecurrent(_unet.UNetRecurrent):
         return img
 
     def check_input(self, x):
-        if self.training:
+        if self.training and not self.trainable:
             raise RuntimeError("v2v_amd.hyper.UNetRecurrent is inference-only and runs BatchNorm on its running statistics: call .eval() first")
         if x.dim() != 4 or x.shape[-2] % 16 != 0 or x.shape[-1] % 16 != 0 or x.shape[-2] < 16 or x.shape[-1] < 16:
             raise ValueError(f"H and W must be multiples of 16 (got {tuple(x.shape)}): pad the events first")
@@ -284,13 +337,16 @@ class UNetRecurrent(_unet.UNetRecurrent):
 
 class HyperE2VID(nn.Module):
     """model/hyper_model.py:198-237: `unetrecurrent` + states / reset_states + the previous reconstruction fed back into the dynamic
-    decoder.  YAML target v2v_amd.hyper.HyperE2VID; call .eval() and run under torch.no_grad()."""
+    decoder.  YAML target v2v_amd.hyper.HyperE2VID (params: {unet_kwargs: .., trainable: true} to train it, as for E2VIDRecurrent).
+    trainable=False: call .eval() and run under torch.no_grad().  trainable=True: .train() under grad records every layer's backward;
+    prev_recs is detached and mixed with gt_image in plain torch, so nothing flows back through the context's inputs."""
 
-    def __init__(self, unet_kwargs):
+    def __init__(self, unet_kwargs, trainable: bool = False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.num_bins = unet_kwargs["num_bins"]
         self.num_encoders = unet_kwargs["num_encoders"]
-        self.unetrecurrent = UNetRecurrent(unet_kwargs)
+        self.unetrecurrent = UNetRecurrent(unet_kwargs, trainable=trainable)
         self.prev_recs = None
 
     @property
@@ -312,7 +368,7 @@ class HyperE2VID(nn.Module):
         if self.prev_recs is None:
             self.prev_recs = torch.zeros((event_tensor.shape[0], 1) + tuple(event_tensor.shape[-2:]), device=event_tensor.device)
         if gt_image is not None and beta > 0:
-            prev_recs = self.prev_recs * (1 - beta) + gt_image * beta
+            prev_recs = self.prev_recs * (1 - beta) + gt_image.detach() * beta
         else:
             prev_recs = self.prev_recs
         output_dict = self.unetrecurrent.forward(event_tensor, prev_recs)

@@ -642,3 +642,122 @@ def dynconv_nhwc(x, atoms, packed, bias, relu=True):
     _launch("v2v_hyper_dynconv_nhwc_hip", x.device, _ptr(x), _ptr(atoms), _ptr(packed), _ptr(bias.detach().contiguous()), int(bool(relu)), b, h, w, cin, cout,
             6, 5, _ptr(out))
     return out
+
+
+# ---- the dynamic decoder's backward and BatchNorm on batch statistics (kernels: the training section of v2v_amd/csrc/v2v_hyper.hpp) ---------
+def _launch_train(name: str, device, *args) -> None:
+    """_launch for the entry points of v2v_hyper_train_tu.hip, which keep their error text in v2v_hyper_train_last_error."""
+    with torch.cuda.device(device):
+        _lib.check(getattr(_lib.lib(), name)(*args, _lib.stream_ptr()), "v2v_hyper_train_last_error")
+
+
+def pack_dynconv_weights_t(weight):
+    """compositional_coefficients float32 [128, 1536, 1, 1] -> the transposed bfloat16 stream dynconv_df_nhwc reads ([1536 feature columns in
+    dF's order][128])."""
+    _lib.require_gpu()
+    if not weight.is_cuda or weight.dtype != torch.float32 or tuple(weight.shape) != (128, 1536, 1, 1):
+        raise ValueError("weight must be a float32 CUDA tensor [128, 1536, 1, 1]")
+    packed = torch.empty((128 * 1536,), dtype=torch.bfloat16, device=weight.device)
+    _launch_train("v2v_hyper_dynconv_pack_t_hip", weight.device, _ptr(weight.detach().contiguous()), _ptr(packed))
+    return packed
+
+
+def dynconv_df_nhwc(dz, packed_t):
+    """dz bf16 [B,H,W,128] (the ReLU backward applied) -> dF bf16 [B,H,W,4,6,64]: dF[p][cb][m][k] = sum_o dz[p][o] * W[o][(cb*64+k)*6+m],
+    float32 accumulation on the matrix cores, one rounding."""
+    _need("dz", dz, dims="[B,H,W,128]", last=128)
+    if packed_t.dtype != torch.bfloat16 or packed_t.numel() != 128 * 1536 or packed_t.device != dz.device:
+        raise ValueError("packed_t must be the output of pack_dynconv_weights_t on dz's device")
+    b, h, w, _ = dz.shape
+    df = torch.empty((b, h, w, 4, 6, 64), dtype=torch.bfloat16, device=dz.device)
+    _launch_train("v2v_hyper_dynconv_df_hip", dz.device, _ptr(dz), _ptr(packed_t), b * h * w, _ptr(df))
+    return df
+
+
+def dynconv_datoms_nhwc(x, df):
+    """x bf16 [B,H,W,256] (the dynamic convolution's input), dF (dynconv_df_nhwc) -> dAtoms float32 [B,H,W,25,6]:
+    dAtoms[p][l][m] = sum_c x[p + offset_l][c] * dF[p][c][m] over the zero-padded 5 x 5 window."""
+    _need("x", x, dims="[B,H,W,256]", last=256)
+    b, h, w, _ = x.shape
+    _need("df", df, shape=(b, h, w, 4, 6, 64), device=x.device)
+    out = torch.empty((b, h, w, 25, 6), dtype=torch.float32, device=x.device)
+    _launch_train("v2v_hyper_dynconv_datoms_hip", x.device, _ptr(x), _ptr(df), b, h, w, _ptr(out))
+    return out
+
+
+def dynconv_dx_nhwc(atoms, df):
+    """atoms float32 [B,H,W,25,6], dF -> dX bf16 [B,H,W,256]: dX[q][c] = sum_l sum_m atoms[q - offset_l][l][m] * dF[q - offset_l][c][m]."""
+    if atoms.dim() != 5:
+        raise ValueError("atoms must be float32 [B,H,W,25,6]")
+    b, h, w = atoms.shape[:3]
+    _need("atoms", atoms, torch.float32, shape=(b, h, w, 25, 6))
+    _need("df", df, shape=(b, h, w, 4, 6, 64), device=atoms.device, owner="atoms")
+    out = torch.empty((b, h, w, 256), dtype=torch.bfloat16, device=atoms.device)
+    _launch_train("v2v_hyper_dynconv_dx_hip", atoms.device, _ptr(atoms), _ptr(df), b, h, w, _ptr(out))
+    return out
+
+
+def dynconv_wgrad_nhwc(dz, x, atoms):
+    """(dW float32 [128, 1536, 1, 1], db float32 [128]) of the dynamic convolution: dW[o][c*6+m] = sum_p dz[p][o] * bf16(F[p][c][m]) with the
+    features F recomputed from x and atoms exactly as dynconv_nhwc computes and rounds them (they are never stored)."""
+    _need("dz", dz, dims="[B,H,W,128]", last=128)
+    b, h, w, _ = dz.shape
+    _need("x", x, shape=(b, h, w, 256), device=dz.device, owner="dz")
+    _need("atoms", atoms, torch.float32, shape=(b, h, w, 25, 6), device=dz.device, owner="dz")
+    ws = _workspace(_lib.lib().v2v_hyper_dynconv_wgrad_workspace_bytes(b, h, w), dz.device)
+    dw = torch.empty((128, 1536, 1, 1), dtype=torch.float32, device=dz.device)
+    db = torch.empty((128,), dtype=torch.float32, device=dz.device)
+    _launch_train("v2v_hyper_dynconv_wgrad_hip", dz.device, _ptr(dz), _ptr(x), _ptr(atoms), b, h, w, _ptr(ws), _ptr(dw), _ptr(db))
+    return dw, db
+
+
+def hyper_bn_stats(z, eps: float = 1e-5):
+    """z bf16 [B,h,w,Cs] -> (mean, biased variance, rstd = 1 / sqrt(var + eps)), float32 [Cs] each, over the B*h*w rows."""
+    _need("z", z, dims="[B,h,w,Cs]")
+    cs = z.shape[3]
+    mean, var, rstd = (torch.empty((cs,), dtype=torch.float32, device=z.device) for _ in range(3))
+    _launch_train("v2v_hyper_bn_stats_hip", z.device, _ptr(z), z.numel() // cs, cs, C.c_float(eps), _ptr(mean), _ptr(var), _ptr(rstd))
+    return mean, var, rstd
+
+
+def _bn_affine(z, gamma, beta):
+    cs, cv = z.shape[3], gamma.numel()
+    if cv > cs or beta.numel() != cv or gamma.device != z.device:
+        raise ValueError("gamma / beta must hold Cv <= Cs values on z's device")
+    return cs, cv, gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+
+
+def hyper_bn_apply(z, mean, rstd, gamma, beta, tanh: bool):
+    """gamma * (z - mean) * rstd + beta [-> tanh] -> bf16 [B,h,w,Cs]; gamma / beta hold the Cv valid columns, the rest come out zero."""
+    _need("z", z, dims="[B,h,w,Cs]")
+    cs, cv, g, b = _bn_affine(z, gamma, beta)
+    out = torch.empty_like(z)
+    _launch_train("v2v_hyper_bn_apply_hip", z.device, _ptr(z), _ptr(mean), _ptr(rstd), _ptr(g), _ptr(b), z.numel() // cs, cs, cv, int(bool(tanh)), _ptr(out))
+    return out
+
+
+def hyper_bn_bwd(dy, z, mean, rstd, gamma, beta, tanh: bool):
+    """Backward of hyper_bn_apply on batch statistics: dy bf16 or float32 [B,h,w,Cs] -> (dz bf16 [B,h,w,Cs], dgamma [Cv], dbeta [Cv],
+    dz_sum [Cv] = the row sum of dz before its bf16 rounding: the bias gradient of the convolution in front, zero in exact arithmetic)."""
+    _need("z", z, dims="[B,h,w,Cs]")
+    cs, cv, g, b = _bn_affine(z, gamma, beta)
+    if dy.dtype not in _DTYPES:
+        raise ValueError("dy must be float32 or bfloat16")
+    _need("dy", dy, dy.dtype, shape=z.shape, device=z.device, owner="z")
+    sums = torch.empty((4, cs), dtype=torch.float32, device=z.device)
+    dz = torch.empty_like(z)
+    _launch_train("v2v_hyper_bn_bwd_hip", z.device, _ptr(dy), int(dy.dtype == torch.float32), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(g), _ptr(b), z.numel() // cs,
+                  cs, cv, int(bool(tanh)), _ptr(sums), _ptr(dz))
+    return dz, sums[1, :cv], sums[0, :cv], sums[2, :cv]
+
+
+def hyper_atoms_bwd(datoms, pre, bases):
+    """Adjoint of hyper_atoms: datoms float32 [B,h,w,25,6], pre bf16 [B,h,w,128] (what hyper_atoms read) -> dpre float32 [B,h,w,128],
+    dpre[..., m*12+k] = (1 - tanh(pre)^2) * sum_l datoms[..., l, m] * bases[k, l]; columns 72..127 zero."""
+    _need("pre", pre, dims="[B,h,w,128]", last=128)
+    b, h, w, _ = pre.shape
+    _need("datoms", datoms, torch.float32, shape=(b, h, w, 25, 6), device=pre.device, owner="pre")
+    _need("bases", bases, torch.float32, shape=(12, 25), device=pre.device, owner="pre")
+    out = torch.empty((b, h, w, 128), dtype=torch.float32, device=pre.device)
+    _launch_train("v2v_hyper_atoms_bwd_hip", pre.device, _ptr(datoms), _ptr(pre), _ptr(bases), b * h * w, _ptr(out))
+    return out

@@ -11,7 +11,8 @@
  *   - Every call is asynchronous on the caller's HIP stream (`stream` is a hipStream_t passed as void*;
  *     NULL = the default stream) and never synchronises.
  *   - Return value: 0 (V2V_OK) or a negative v2v_status.  No exceptions, no aborts.  A human-readable
- *     message for the last failure on the calling thread is available from v2v_last_error().
+ *     message for the last failure on the calling thread is available from v2v_last_error(): one slot per
+ *     thread for every entry point of the library, whichever family it belongs to.
  *   - No global mutable state except the log-intensity tables (v2v_lut_set) and the per-thread error slot.
  *   - There is NO CPU implementation behind this ABI.  Without a GPU every compute entry point
  *     returns V2V_ERR_HIP.
@@ -568,8 +569,9 @@ int v2v_hyper_dynconv_pack_weights_hip(const float *weight, int64_t Cin, int64_t
 int v2v_hyper_dynconv_nhwc_hip(const void *x, const float *atoms, const void *packed, const float *bias, int relu, int64_t B, int64_t H, int64_t W,
                                int64_t Cin, int64_t Cout, int n_atoms, int ks, void *out, void *stream);
 
-/* ---- the dynamic decoder's backward (training; v2v_amd/train.py DynamicUpsampleFn).  No atomics: two runs give equal bits.  These entry
- * points keep their error text apart from v2v_last_error(): v2v_hyper_train_last_error() (thread-local). ---------------------------------
+/* ---- the dynamic decoder's backward (training; v2v_amd/train.py DynamicUpsampleFn).  No atomics: two runs give equal bits.  Errors go to
+ * v2v_last_error() like everyone's; v2v_hyper_train_last_error() is a DEPRECATED ALIAS that returns v2v_last_error() (ABI 6 first shipped
+ * these entry points with a slot of their own; the symbol stays so that a client linked against that build keeps working). -----------
  * With dz = relu'(dout) bf16 [M = B*H*W][128], x = the upsampled input bf16 [B,H,W,256], atoms float32 [B,H,W,25,6]:
  *   pack_t   compositional_coefficients float32 [128,1536] -> the transposed bf16 stream of df (128 * 1536 elements)
  *   df       dF[p][c][m] = sum_o dz[p][o] W[o][c*6+m], stored bf16 as [M][c / 64][m][c % 64] (1536 per pixel), one rounding
@@ -578,7 +580,7 @@ int v2v_hyper_dynconv_nhwc_hip(const void *x, const float *atoms, const void *pa
  *   wgrad    dW[o][c*6+m] = sum_p dz[p][o] bf16(F[p][c][m]) with F recomputed as the forward computes it, db[o] = sum_p dz[p][o]; float32;
  *            workspace of v2v_hyper_dynconv_wgrad_workspace_bytes (16-byte aligned; -1: shape not taken)
  * Any B, H, W >= 1 with B*H*W*1536 below 2^33. */
-const char *v2v_hyper_train_last_error(void);
+const char *v2v_hyper_train_last_error(void);        /* deprecated: the same text as v2v_last_error() */
 int v2v_hyper_dynconv_pack_t_hip(const float *weight, void *packed_t, void *stream);
 int v2v_hyper_dynconv_df_hip(const void *dz, const void *packed_t, int64_t M, void *dF, void *stream);
 int v2v_hyper_dynconv_datoms_hip(const void *x, const void *dF, int64_t B, int64_t H, int64_t W, float *datoms, void *stream);

@@ -20,7 +20,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "v2v_amd", "csrc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-S", "--cuda-device-only"]
-TUS = ["v2v_v2e_tu", "v2v_v2e_spec_f32_tu", "v2v_v2e_spec_u8_tu", "v2v_esim_u8_tu", "v2v_esim_f32_tu", "v2v_convlstm_tu", "v2v_convgru_tu", "v2v_narrow_tu", "v2v_train_tu", "v2v_hyper_tu", "v2v_loss_tu", "v2v_lpips_tu", "v2v_capi"]
+TUS = re.search(r"^TUS\s*:=\s*(.+)$", open(os.path.join(CSRC, "Makefile")).read(), re.M).group(1).split()      # the Makefile's own list
 FIELDS = {".vgpr_count": "vgpr", ".vgpr_spill_count": "vgpr_spill", ".sgpr_count": "sgpr", ".sgpr_spill_count": "sgpr_spill",
           ".group_segment_fixed_size": "lds_static_bytes", ".private_segment_fixed_size": "scratch_bytes", ".agpr_count": "agpr"}
 

@@ -20,30 +20,6 @@ FLAG_MAP_4PX, FLAG_MAP_1PX, FLAG_MAP_2PX = 0x8, 0x10, 0x20
 OK, ERR_NULL, ERR_SHAPE, ERR_BINS, ERR_DTYPE, ERR_MODE, ERR_ALIGN, ERR_HIP, ERR_PARAM = 0, -1, -2, -3, -4, -5, -6, -7, -8
 ABI_VERSION = 6
 
-EXPORTS = ("v2v_version", "v2v_last_error", "v2v_device_count", "v2v_lut_get", "v2v_lut_set",
-           "v2v_esim_voxel_hip", "v2v_esim_voxel_keyed_hip", "v2v_esim_voxel_bytes", "v2v_synth_clips_hip", "v2v_events_to_voxel_hip", "v2v_events_to_voxel_segmented_hip",
-           "v2v_v2e_voxel_hip", "v2v_v2e_workspace_bytes", "v2v_events_to_voxel_f32_hip", "v2v_events_to_voxel_f32_segmented_hip", "v2v_esim_voxel_padded_hip", "v2v_normalize_pad_ex_hip", "v2v_frontend_hip", "v2v_frontend_batch_hip",
-           "v2v_normalize_pad_hip", "v2v_postops_workspace_bytes",
-           "v2v_convlstm_packed_bytes", "v2v_convlstm_pack_weights_hip", "v2v_convlstm_step_hip", "v2v_nchw_to_nhwc_bf16_hip",
-           "v2v_conv3x3_pack_weights_hip", "v2v_conv3x3_nhwc_hip", "v2v_conv_pack_weights_hip", "v2v_conv_nhwc_hip", "v2v_upsample2x_nhwc_hip", "v2v_conv1x1_nhwc_hip", "v2v_conv_packed_elems", "v2v_conv_head_packed_elems", "v2v_conv_head_pack_weights_hip",
-           "v2v_to_nhwc8_bf16_hip", "v2v_conv_head_nhwc_hip", "v2v_clip_frames_f32_hip",
-           "v2v_esim_voxel_stats_hip", "v2v_voxel_scales_hip", "v2v_voxel_apply_scales_hip", "v2v_voxel_scales_select_hip", "v2v_to_nhwc8_bf16_scaled_hip", "v2v_esim_voxel_ex_hip", "v2v_clip_frames_f32_ex_hip", "v2v_clip_frames_f32_bounded_hip",
-           "v2v_convlstm_step_bwd_hip", "v2v_relu_bwd_nhwc_hip", "v2v_conv_dgrad_packed_elems", "v2v_conv_dgrad_pack_weights_hip",
-           "v2v_conv_dgrad_workspace_bytes", "v2v_conv_dgrad_nhwc_hip", "v2v_conv_wgrad_workspace_bytes", "v2v_conv_wgrad_nhwc_hip",
-           "v2v_upsample2x_bwd_nhwc_hip", "v2v_conv1x1_bwd_workspace_bytes", "v2v_conv1x1_bwd_nhwc_hip",
-           "v2v_conv_stem_packed_elems", "v2v_conv_stem_pack_weights_hip", "v2v_conv_stem_nhwc_hip", "v2v_upsample2x_cat_nhwc_hip",
-           "v2v_upsample2x_cat_bwd_nhwc_hip", "v2v_conv1x1_bwd_cout_workspace_bytes", "v2v_conv1x1_bwd_cout_nhwc_hip", "v2v_conv_nhwc_like_hip",
-           "v2v_hyper_context_hip", "v2v_hyper_context_conv_hip", "v2v_tanh_bf16_hip", "v2v_hyper_atoms_hip", "v2v_hyper_dynconv_packed_elems", "v2v_hyper_dynconv_pack_weights_hip",
-           "v2v_hyper_dynconv_nhwc_hip",
-           "v2v_hyper_train_last_error", "v2v_hyper_dynconv_pack_t_hip", "v2v_hyper_dynconv_df_hip", "v2v_hyper_dynconv_datoms_hip", "v2v_hyper_dynconv_dx_hip",
-           "v2v_hyper_dynconv_wgrad_workspace_bytes", "v2v_hyper_dynconv_wgrad_hip", "v2v_hyper_bn_stats_hip", "v2v_hyper_bn_apply_hip", "v2v_hyper_bn_bwd_hip",
-           "v2v_hyper_atoms_bwd_hip",
-           "v2v_convgru_packed_bytes", "v2v_convgru_pack_weights_hip", "v2v_convgru_step_hip",
-           "v2v_convgru16_packed_elems", "v2v_convgru16_pack_weights_hip", "v2v_convgru16_step_hip", "v2v_resblock16_packed_elems", "v2v_resblock16_pack_weights_hip",
-           "v2v_resblock16_nhwc_hip", "v2v_conv_head16_packed_elems", "v2v_conv_head16_pack_weights_hip", "v2v_conv_head16_nhwc_hip",
-           "v2v_tc_loss_workspace_bytes", "v2v_tc_loss_fwd_hip", "v2v_tc_loss_bwd_hip", "v2v_warp_bilinear_hip", "v2v_warp_bilinear_adjoint_hip",
-           "v2v_lpips_stem_hip", "v2v_lpips_stem_bwd_hip", "v2v_lpips_pool_hip", "v2v_lpips_pool_bwd_hip", "v2v_lpips_compare_workspace_bytes",
-           "v2v_lpips_compare_fwd_hip", "v2v_lpips_compare_bwd_hip")
 EV_MAKE_VOXEL_DISCRETE, EV_MAKE_VOXEL_INTERP, EV_BILINEAR = 0, 1, 2
 NORM_NONE, NORM_RADIX, NORM_COUNT = 0, 1, 2
 VOXEL_STATS_WORDS = 516
@@ -79,6 +55,140 @@ class V2VError(RuntimeError):
         self.code = code
 
 
+P, I, I64, U32, U64, F = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
+_ESIM = [P, I] + [I64] * 6 + [P, I64, U32, I, U64, U64]                                  # frames..clip_id0
+_ESIM_PADDED = _ESIM + [P, C.POINTER(EsimReplay), I, I, I, P, I, I64, I64, P]              # clip_keys..out_counts (the stream follows)
+
+# {entry point: (restype, argtypes)}, in the order of include/v2v_hip.h (tests/test_capi_contract.py compares the two)
+SIGNATURES = {
+    # library info / errors
+    "v2v_version": (I, []),
+    "v2v_last_error": (C.c_char_p, []),
+    "v2v_device_count": (I, []),
+    # log-intensity tables
+    "v2v_lut_get": (I, [I, P]),
+    "v2v_lut_set": (I, [I, P]),
+    # fused ESIM simulator + voxel binning
+    "v2v_esim_voxel_hip": (I, _ESIM + [C.POINTER(EsimReplay), I, I, I, P, I, P, P]),
+    "v2v_esim_voxel_keyed_hip": (I, _ESIM + [P, C.POINTER(EsimReplay), I, I, I, P, I, P, P]),
+    "v2v_esim_voxel_padded_hip": (I, _ESIM_PADDED + [P]),
+    "v2v_esim_voxel_bytes": (I64, [I] + [I64] * 4 + [I] * 4),
+    # synthetic clips
+    "v2v_synth_clips_hip": (I, [P, I] + [I64] * 4 + [U64, U64, P]),
+    "v2v_events_to_voxel_segmented_hip": (I, [P, P, P, P, I64, P, I64, I, I, I64, I64, P, P, P]),
+    # v2e-derived DVS model fused with voxel binning
+    "v2v_v2e_workspace_bytes": (I64, [I64, I64]),
+    "v2v_v2e_voxel_hip": (I, [P, I] + [I64] * 6 + [C.POINTER(V2EParams), I, U64, U64, C.POINTER(V2EReplay), I, I, I, P, I, P, P, P]),
+    # event list -> voxel grid
+    "v2v_events_to_voxel_hip": (I, [P, P, P, P, I64, I, I, I64, I64, P, P, P]),
+    # decode-side front end
+    "v2v_frontend_hip": (I, [P] + [I64] * 10 + [I, I, P, I64, P, P, P, P, P]),
+    "v2v_frontend_batch_hip": (I, [P] + [I64] * 5 + [P, I64, I64, I, P, I64, P, P, P]),
+    # voxel post-ops of the consumer
+    "v2v_postops_workspace_bytes": (I64, [I64]),
+    "v2v_normalize_pad_hip": (I, [P] + [I64] * 4 + [I, I, P, P, P]),
+    "v2v_normalize_pad_ex_hip": (I, [P] + [I64] * 6 + [I, I, P, P, P]),
+    "v2v_events_to_voxel_f32_hip": (I, [P, P, P, P, I64, I, I, I64, I64, P, P, P]),
+    "v2v_events_to_voxel_f32_segmented_hip": (I, [P, P, P, P, I64, P, I64, I, I, I, I64, I64, P, P, P]),
+    # the ConvLSTM step
+    "v2v_convlstm_packed_bytes": (I, [I64, C.POINTER(U64)]),
+    "v2v_convlstm_pack_weights_hip": (I, [P, I64, P, P]),
+    "v2v_convlstm_step_hip": (I, [P] * 5 + [I64] * 4 + [P, P, P, I, I, P]),
+    # the ConvGRU step (two launches behind one call)
+    "v2v_convgru_packed_bytes": (I, [I64, C.POINTER(U64), C.POINTER(U64)]),
+    "v2v_convgru_pack_weights_hip": (I, [P, P, P, I64, P, P, P]),
+    "v2v_convgru_step_hip": (I, [P] * 7 + [I64] * 4 + [P] * 5 + [I] * 3 + [P]),
+    # the 16-channel layer family (FireNet): one launch per layer
+    "v2v_convgru16_packed_elems": (I64, []),
+    "v2v_convgru16_pack_weights_hip": (I, [P] * 5),
+    "v2v_convgru16_step_hip": (I, [P] * 6 + [I64] * 3 + [P] * 3 + [I, P]),
+    "v2v_resblock16_packed_elems": (I64, []),
+    "v2v_resblock16_pack_weights_hip": (I, [P] * 4),
+    "v2v_resblock16_nhwc_hip": (I, [P] * 4 + [I64] * 3 + [P, P]),
+    "v2v_conv_head16_packed_elems": (I64, []),
+    "v2v_conv_head16_pack_weights_hip": (I, [P, I64, P, P]),
+    "v2v_conv_head16_nhwc_hip": (I, [P] * 3 + [I] + [I64] * 3 + [P, P]),
+    # convolution, head, 1x1, upsampling, layouts
+    "v2v_conv3x3_pack_weights_hip": (I, [P, I64, I64, P, P]),
+    "v2v_conv3x3_nhwc_hip": (I, [P, P, P, P, I] + [I64] * 5 + [P, I, P]),
+    "v2v_conv_packed_elems": (I64, [I64, I64, I]),
+    "v2v_conv_pack_weights_hip": (I, [P, I64, I64, I, P, P]),
+    "v2v_conv_nhwc_hip": (I, [P, P, P, P, I] + [I64] * 5 + [I, I, P, I, P]),
+    "v2v_upsample2x_nhwc_hip": (I, [P, P] + [I64] * 4 + [P, P]),
+    "v2v_conv_head_packed_elems": (I64, [I]),
+    "v2v_conv_head_pack_weights_hip": (I, [P, I64, I, P, P]),
+    "v2v_to_nhwc8_bf16_hip": (I, [P] + [I64] * 8 + [P, P]),
+    "v2v_to_nhwc8_bf16_scaled_hip": (I, [P] + [I64] * 8 + [P, P, P]),
+    "v2v_conv_head_nhwc_hip": (I, [P, P, P, I, I64, I64, I64, I, P, P]),
+    "v2v_conv1x1_nhwc_hip": (I, [P, P, P, P, I64, I64, I64, P, I, P]),
+    "v2v_nchw_to_nhwc_bf16_hip": (I, [P, I] + [I64] * 4 + [I, P, P]),
+    # backward passes (v2v_amd/train.py)
+    "v2v_convlstm_step_bwd_hip": (I, [P] * 7 + [I64] * 4 + [P, P, P]),
+    "v2v_relu_bwd_nhwc_hip": (I, [P, P, I64, I64, P, P]),
+    "v2v_conv_dgrad_packed_elems": (I64, [I64, I64, I]),
+    "v2v_conv_dgrad_pack_weights_hip": (I, [P, I64, I64, I, P, P, P]),
+    "v2v_conv_dgrad_workspace_bytes": (I64, [I64] * 5 + [I]),
+    "v2v_conv_dgrad_nhwc_hip": (I, [P, P, P] + [I64] * 5 + [I, I, P, P, P]),
+    "v2v_conv_wgrad_workspace_bytes": (I64, [I64] * 5 + [I]),
+    "v2v_conv_wgrad_nhwc_hip": (I, [P, P, I64, P, I64, I64, I64, I64, I64, I64, I, I, P, P, P, P]),
+    "v2v_upsample2x_bwd_nhwc_hip": (I, [P] + [I64] * 4 + [P, P]),
+    "v2v_conv1x1_bwd_workspace_bytes": (I64, [I64, I64]),
+    "v2v_conv1x1_bwd_nhwc_hip": (I, [P, P, P, P, I64, I64, P, P, P, P, P]),
+    # ESIM extras, voxel statistics and scales, clip frames
+    "v2v_esim_voxel_ex_hip": (I, _ESIM_PADDED + [C.POINTER(EsimExtras), P]),
+    "v2v_esim_voxel_stats_hip": (I, _ESIM_PADDED + [P, P]),
+    "v2v_voxel_scales_hip": (I, [P, I64, I64, P, P]),
+    "v2v_voxel_apply_scales_hip": (I, [P] + [I64] * 6 + [I, P, P, P]),
+    "v2v_voxel_scales_select_hip": (I, [P] + [I64] * 6 + [I, P, P, P]),
+    "v2v_clip_frames_f32_hip": (I, [P, I64, I64, P] + [I64] * 5 + [P, P]),
+    "v2v_clip_frames_f32_ex_hip": (I, [P, I64, P, I64, P] + [I64] * 6 + [P, P]),
+    "v2v_clip_frames_f32_bounded_hip": (I, [P, I64, P, I64, P, I64, P, I64] + [I64] * 5 + [P, P]),
+    # the plain UNet (EVFlowNet): stem, concat-skip upsampling + adjoint, prediction backward for 1..3 outputs
+    "v2v_conv_stem_packed_elems": (I64, []),
+    "v2v_conv_stem_pack_weights_hip": (I, [P, I64, P, P]),
+    "v2v_conv_stem_nhwc_hip": (I, [P, P, P, I, I64, I64, I64, P, P]),
+    "v2v_upsample2x_cat_nhwc_hip": (I, [P, I64, P, I64, I64, I64, I64, P, P]),
+    "v2v_upsample2x_cat_bwd_nhwc_hip": (I, [P] + [I64] * 6 + [P, P]),
+    "v2v_conv1x1_bwd_cout_workspace_bytes": (I64, [I64, I64, I64]),
+    "v2v_conv1x1_bwd_cout_nhwc_hip": (I, [P, P, P, P, I64, I64, I64, P, P, P, P, P]),
+    "v2v_conv_nhwc_like_hip": (I, [P, P, P, P, I] + [I64] * 5 + [I, I, P, I64, P]),
+    # HyperE2VID's dynamic decoder (v2v_amd/hyper.py): context staging, tanh, atoms, the dynamic convolution
+    "v2v_hyper_context_hip": (I, [P] + [I64] * 4 + [P] + [I64] * 4 + [P, P]),
+    "v2v_hyper_context_conv_hip": (I, [P, P, P] + [I64] * 4 + [P, P]),
+    "v2v_tanh_bf16_hip": (I, [P, I64, P, P]),
+    "v2v_hyper_atoms_hip": (I, [P, P, I64, P, P]),
+    "v2v_hyper_dynconv_packed_elems": (I64, [I64, I64, I, I]),
+    "v2v_hyper_dynconv_pack_weights_hip": (I, [P, I64, I64, I, P, P]),
+    "v2v_hyper_dynconv_nhwc_hip": (I, [P, P, P, P, I] + [I64] * 5 + [I, I, P, P]),
+    # the dynamic decoder's backward and BatchNorm on batch statistics (v2v_amd/train.py DynamicUpsampleFn)
+    "v2v_hyper_train_last_error": (C.c_char_p, []),                 # deprecated alias of v2v_last_error
+    "v2v_hyper_dynconv_pack_t_hip": (I, [P, P, P]),
+    "v2v_hyper_dynconv_df_hip": (I, [P, P, I64, P, P]),
+    "v2v_hyper_dynconv_datoms_hip": (I, [P, P, I64, I64, I64, P, P]),
+    "v2v_hyper_dynconv_dx_hip": (I, [P, P, I64, I64, I64, P, P]),
+    "v2v_hyper_dynconv_wgrad_workspace_bytes": (I64, [I64, I64, I64]),
+    "v2v_hyper_dynconv_wgrad_hip": (I, [P, P, P, I64, I64, I64, P, P, P, P]),
+    "v2v_hyper_bn_stats_hip": (I, [P, I64, I64, F, P, P, P, P]),
+    "v2v_hyper_bn_apply_hip": (I, [P] * 5 + [I64] * 3 + [I, P, P]),
+    "v2v_hyper_bn_bwd_hip": (I, [P, I] + [P] * 5 + [I64] * 3 + [I, P, P, P]),
+    "v2v_hyper_atoms_bwd_hip": (I, [P, P, P, I64, P, P]),
+    # the image losses of training (v2v_amd/loss_ops.py)
+    "v2v_tc_loss_workspace_bytes": (I64, [I64] * 4 + [I]),
+    "v2v_tc_loss_fwd_hip": (I, [P] * 5 + [I64] * 10 + [F] * 5 + [P] * 7),
+    "v2v_tc_loss_bwd_hip": (I, [P] * 5 + [I64] * 10 + [F] * 5 + [P, I] + [P] * 4),
+    "v2v_warp_bilinear_hip": (I, [P, P] + [I64] * 4 + [P, P]),
+    "v2v_warp_bilinear_adjoint_hip": (I, [P, P] + [I64] * 4 + [P, P, P]),
+    # the LPIPS-VGG perceptual loss (v2v_amd/lpips.py): stem, max-pool, compare, each forward and backward
+    "v2v_lpips_stem_hip": (I, [P, I] + [I64] * 4 + [P] * 4 + [I, P, P]),
+    "v2v_lpips_stem_bwd_hip": (I, [P] + [I64] * 4 + [P, P, I, P, P]),
+    "v2v_lpips_pool_hip": (I, [P] + [I64] * 4 + [P, P]),
+    "v2v_lpips_pool_bwd_hip": (I, [P, P, P, I] + [I64] * 4 + [P, P]),
+    "v2v_lpips_compare_workspace_bytes": (I64, [I64, I64]),
+    "v2v_lpips_compare_fwd_hip": (I, [P, P, P] + [I64] * 3 + [P, P, P]),
+    "v2v_lpips_compare_bwd_hip": (I, [P, P, P, P] + [I64] * 3 + [P, P]),
+}
+EXPORTS = tuple(SIGNATURES)
+
 _lib = None
 
 
@@ -91,191 +201,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C v2v_amd/csrc`).  v2v_amd has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    L.v2v_version.restype = C.c_int
-    L.v2v_last_error.restype = C.c_char_p
-    L.v2v_device_count.restype = C.c_int
-    L.v2v_lut_get.argtypes = [C.c_int, C.c_void_p]
-    L.v2v_lut_set.argtypes = [C.c_int, C.c_void_p]
-    L.v2v_esim_voxel_hip.restype = C.c_int
-    L.v2v_esim_voxel_hip.argtypes = [
-        C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,   # frames..frame_stride
-        C.c_void_p, C.c_int64, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64,                        # params..clip_id0
-        C.POINTER(EsimReplay), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.v2v_esim_voxel_keyed_hip.restype = C.c_int
-    L.v2v_esim_voxel_keyed_hip.argtypes = [
-        C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-        C.c_void_p, C.c_int64, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p,
-        C.POINTER(EsimReplay), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.v2v_esim_voxel_padded_hip.restype = C.c_int
-    L.v2v_esim_voxel_padded_hip.argtypes = [
-        C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-        C.c_void_p, C.c_int64, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p,
-        C.POINTER(EsimReplay), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
-    L.v2v_esim_voxel_stats_hip.restype = C.c_int
-    L.v2v_esim_voxel_stats_hip.argtypes = L.v2v_esim_voxel_padded_hip.argtypes[:-1] + [C.c_void_p, C.c_void_p]
-    L.v2v_clip_frames_f32_ex_hip.restype = C.c_int
-    L.v2v_clip_frames_f32_ex_hip.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                             C.c_int64, C.c_void_p, C.c_void_p]
-    L.v2v_clip_frames_f32_bounded_hip.restype = C.c_int
-    L.v2v_clip_frames_f32_bounded_hip.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_int64] * 5 + [C.c_void_p, C.c_void_p]
-    L.v2v_esim_voxel_ex_hip.restype = C.c_int
-    L.v2v_esim_voxel_ex_hip.argtypes = L.v2v_esim_voxel_padded_hip.argtypes[:-1] + [C.POINTER(EsimExtras), C.c_void_p]
-    L.v2v_voxel_scales_hip.restype = C.c_int
-    L.v2v_voxel_scales_hip.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
-    L.v2v_voxel_apply_scales_hip.restype = C.c_int
-    L.v2v_voxel_apply_scales_hip.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
-                                             C.c_void_p, C.c_void_p]
-    L.v2v_voxel_scales_select_hip.restype = C.c_int
-    L.v2v_voxel_scales_select_hip.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
-                                              C.c_void_p, C.c_void_p]
-    L.v2v_esim_voxel_bytes.restype = C.c_int64
-    L.v2v_esim_voxel_bytes.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.v2v_synth_clips_hip.restype = C.c_int
-    L.v2v_synth_clips_hip.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint64,
-                                      C.c_uint64, C.c_void_p]
-    L.v2v_events_to_voxel_hip.restype = C.c_int
-    L.v2v_events_to_voxel_hip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
-                                          C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.v2v_events_to_voxel_segmented_hip.restype = C.c_int
-    L.v2v_events_to_voxel_segmented_hip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                                    C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                                    C.c_void_p]
-    L.v2v_events_to_voxel_f32_segmented_hip.restype = C.c_int
-    L.v2v_events_to_voxel_f32_segmented_hip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                        C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.v2v_events_to_voxel_f32_hip.restype = C.c_int
-    L.v2v_events_to_voxel_f32_hip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
-                                              C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.v2v_frontend_hip.restype = C.c_int
-    L.v2v_frontend_hip.argtypes = [C.c_void_p] + [C.c_int64] * 10 + [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
-                                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.v2v_frontend_batch_hip.restype = C.c_int
-    L.v2v_frontend_batch_hip.argtypes = [C.c_void_p] + [C.c_int64] * 5 + [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
-                                                                           C.c_void_p, C.c_void_p, C.c_void_p]
-    L.v2v_postops_workspace_bytes.restype = C.c_int64
-    L.v2v_postops_workspace_bytes.argtypes = [C.c_int64]
-    L.v2v_normalize_pad_ex_hip.restype = C.c_int
-    L.v2v_normalize_pad_ex_hip.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]
-    L.v2v_normalize_pad_hip.restype = C.c_int
-    L.v2v_normalize_pad_hip.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]
-    L.v2v_convlstm_packed_bytes.restype = C.c_int
-    L.v2v_convlstm_packed_bytes.argtypes = [C.c_int64, C.POINTER(C.c_uint64)]
-    L.v2v_convlstm_pack_weights_hip.restype = C.c_int
-    L.v2v_convlstm_pack_weights_hip.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    L.v2v_convlstm_step_hip.restype = C.c_int
-    L.v2v_convlstm_step_hip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.v2v_conv3x3_pack_weights_hip.restype = C.c_int
-    L.v2v_conv3x3_pack_weights_hip.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
-    L.v2v_conv3x3_nhwc_hip.restype = C.c_int
-    L.v2v_conv3x3_nhwc_hip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                       C.c_void_p, C.c_int, C.c_void_p]
-    L.v2v_conv_pack_weights_hip.restype = C.c_int
-    L.v2v_conv_pack_weights_hip.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
-    L.v2v_conv_nhwc_hip.restype = C.c_int
-    L.v2v_conv_nhwc_hip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                    C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-    L.v2v_conv_packed_elems.restype = C.c_int64
-    L.v2v_conv_packed_elems.argtypes = [C.c_int64, C.c_int64, C.c_int]
-    L.v2v_conv_head_packed_elems.restype = C.c_int64
-    L.v2v_conv_head_packed_elems.argtypes = [C.c_int]
-    L.v2v_conv_head_pack_weights_hip.restype = C.c_int
-    L.v2v_conv_head_pack_weights_hip.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
-    L.v2v_to_nhwc8_bf16_hip.restype = C.c_int
-    L.v2v_to_nhwc8_bf16_hip.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
-    L.v2v_to_nhwc8_bf16_scaled_hip.restype = C.c_int
-    L.v2v_to_nhwc8_bf16_scaled_hip.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                               C.c_void_p, C.c_void_p]
-    L.v2v_conv_head_nhwc_hip.restype = C.c_int
-    L.v2v_conv_head_nhwc_hip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
-    L.v2v_conv1x1_nhwc_hip.restype = C.c_int
-    L.v2v_conv1x1_nhwc_hip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
-    L.v2v_upsample2x_nhwc_hip.restype = C.c_int
-    L.v2v_upsample2x_nhwc_hip.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
-    L.v2v_nchw_to_nhwc_bf16_hip.restype = C.c_int
-    L.v2v_nchw_to_nhwc_bf16_hip.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
-    L.v2v_clip_frames_f32_hip.restype = C.c_int
-    L.v2v_clip_frames_f32_hip.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                          C.c_void_p, C.c_void_p]
-    L.v2v_v2e_workspace_bytes.restype = C.c_int64
-    L.v2v_v2e_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
-    L.v2v_v2e_voxel_hip.restype = C.c_int
-    L.v2v_v2e_voxel_hip.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                    C.POINTER(V2EParams), C.c_int, C.c_uint64, C.c_uint64, C.POINTER(V2EReplay), C.c_int,
-                                    C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    # backward passes (v2v_amd/train.py)
-    P, I64 = C.c_void_p, C.c_int64
-    for name, res, args in (
-            ("v2v_convlstm_step_bwd_hip", C.c_int, [P] * 7 + [I64] * 4 + [P, P, P]),
-            ("v2v_relu_bwd_nhwc_hip", C.c_int, [P, P, I64, I64, P, P]),
-            ("v2v_conv_dgrad_packed_elems", I64, [I64, I64, C.c_int]),
-            ("v2v_conv_dgrad_pack_weights_hip", C.c_int, [P, I64, I64, C.c_int, P, P, P]),
-            ("v2v_conv_dgrad_workspace_bytes", I64, [I64] * 5 + [C.c_int]),
-            ("v2v_conv_dgrad_nhwc_hip", C.c_int, [P, P, P] + [I64] * 5 + [C.c_int, C.c_int, P, P, P]),
-            ("v2v_conv_wgrad_workspace_bytes", I64, [I64] * 5 + [C.c_int]),
-            ("v2v_conv_wgrad_nhwc_hip", C.c_int, [P, P, I64, P, I64, I64, I64, I64, I64, I64, C.c_int, C.c_int, P, P, P, P]),
-            ("v2v_upsample2x_bwd_nhwc_hip", C.c_int, [P] + [I64] * 4 + [P, P]),
-            ("v2v_conv1x1_bwd_workspace_bytes", I64, [I64, I64]),
-            ("v2v_conv1x1_bwd_nhwc_hip", C.c_int, [P, P, P, P, I64, I64, P, P, P, P, P]),
-            # the plain UNet (EVFlowNet): stem, concat-skip upsampling + adjoint, prediction backward for 1..3 outputs
-            ("v2v_conv_stem_packed_elems", I64, []),
-            ("v2v_conv_stem_pack_weights_hip", C.c_int, [P, I64, P, P]),
-            ("v2v_conv_stem_nhwc_hip", C.c_int, [P, P, P, C.c_int, I64, I64, I64, P, P]),
-            ("v2v_upsample2x_cat_nhwc_hip", C.c_int, [P, I64, P, I64, I64, I64, I64, P, P]),
-            ("v2v_upsample2x_cat_bwd_nhwc_hip", C.c_int, [P] + [I64] * 6 + [P, P]),
-            ("v2v_conv1x1_bwd_cout_workspace_bytes", I64, [I64, I64, I64]),
-            ("v2v_conv1x1_bwd_cout_nhwc_hip", C.c_int, [P, P, P, P, I64, I64, I64, P, P, P, P, P]),
-            ("v2v_conv_nhwc_like_hip", C.c_int, [P, P, P, P, C.c_int] + [I64] * 5 + [C.c_int, C.c_int, P, I64, P]),
-            # HyperE2VID's dynamic decoder (v2v_amd/hyper.py): context staging, tanh, atoms, the dynamic convolution
-            ("v2v_hyper_context_hip", C.c_int, [P] + [I64] * 4 + [P] + [I64] * 4 + [P, P]),
-            ("v2v_hyper_context_conv_hip", C.c_int, [P, P, P] + [I64] * 4 + [P, P]),
-            ("v2v_tanh_bf16_hip", C.c_int, [P, I64, P, P]),
-            ("v2v_hyper_atoms_hip", C.c_int, [P, P, I64, P, P]),
-            ("v2v_hyper_dynconv_packed_elems", I64, [I64, I64, C.c_int, C.c_int]),
-            ("v2v_hyper_dynconv_pack_weights_hip", C.c_int, [P, I64, I64, C.c_int, P, P]),
-            ("v2v_hyper_dynconv_nhwc_hip", C.c_int, [P, P, P, P, C.c_int] + [I64] * 5 + [C.c_int, C.c_int, P, P]),
-            # the dynamic decoder's backward and BatchNorm on batch statistics (v2v_amd/train.py DynamicUpsampleFn)
-            ("v2v_hyper_train_last_error", C.c_char_p, []),
-            ("v2v_hyper_dynconv_pack_t_hip", C.c_int, [P, P, P]),
-            ("v2v_hyper_dynconv_df_hip", C.c_int, [P, P, I64, P, P]),
-            ("v2v_hyper_dynconv_datoms_hip", C.c_int, [P, P, I64, I64, I64, P, P]),
-            ("v2v_hyper_dynconv_dx_hip", C.c_int, [P, P, I64, I64, I64, P, P]),
-            ("v2v_hyper_dynconv_wgrad_workspace_bytes", I64, [I64, I64, I64]),
-            ("v2v_hyper_dynconv_wgrad_hip", C.c_int, [P, P, P, I64, I64, I64, P, P, P, P]),
-            ("v2v_hyper_bn_stats_hip", C.c_int, [P, I64, I64, C.c_float, P, P, P, P]),
-            ("v2v_hyper_bn_apply_hip", C.c_int, [P] * 5 + [I64] * 3 + [C.c_int, P, P]),
-            ("v2v_hyper_bn_bwd_hip", C.c_int, [P, C.c_int] + [P] * 5 + [I64] * 3 + [C.c_int, P, P, P]),
-            ("v2v_hyper_atoms_bwd_hip", C.c_int, [P, P, P, I64, P, P]),
-            # the ConvGRU step (two launches behind one call)
-            ("v2v_convgru_packed_bytes", C.c_int, [I64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
-            ("v2v_convgru_pack_weights_hip", C.c_int, [P, P, P, I64, P, P, P]),
-            ("v2v_convgru_step_hip", C.c_int, [P] * 7 + [I64] * 4 + [P] * 5 + [C.c_int] * 3 + [P]),
-            # the 16-channel layer family (FireNet): one launch per layer
-            ("v2v_convgru16_packed_elems", I64, []),
-            ("v2v_convgru16_pack_weights_hip", C.c_int, [P] * 5),
-            ("v2v_convgru16_step_hip", C.c_int, [P] * 6 + [I64] * 3 + [P] * 3 + [C.c_int, P]),
-            ("v2v_resblock16_packed_elems", I64, []),
-            ("v2v_resblock16_pack_weights_hip", C.c_int, [P] * 4),
-            ("v2v_resblock16_nhwc_hip", C.c_int, [P] * 4 + [I64] * 3 + [P, P]),
-            ("v2v_conv_head16_packed_elems", I64, []),
-            ("v2v_conv_head16_pack_weights_hip", C.c_int, [P, I64, P, P]),
-            ("v2v_conv_head16_nhwc_hip", C.c_int, [P] * 3 + [C.c_int] + [I64] * 3 + [P, P]),
-            # the image losses of training (v2v_amd/loss_ops.py)
-            ("v2v_tc_loss_workspace_bytes", I64, [I64] * 4 + [C.c_int]),
-            ("v2v_tc_loss_fwd_hip", C.c_int, [P] * 5 + [I64] * 10 + [C.c_float] * 5 + [P] * 7),
-            ("v2v_tc_loss_bwd_hip", C.c_int, [P] * 5 + [I64] * 10 + [C.c_float] * 5 + [P, C.c_int] + [P] * 4),
-            ("v2v_warp_bilinear_hip", C.c_int, [P, P] + [I64] * 4 + [P, P]),
-            ("v2v_warp_bilinear_adjoint_hip", C.c_int, [P, P] + [I64] * 4 + [P, P, P]),
-            # the LPIPS-VGG perceptual loss (v2v_amd/lpips.py): stem, max-pool, compare, each forward and backward
-            ("v2v_lpips_stem_hip", C.c_int, [P, C.c_int] + [I64] * 4 + [P] * 4 + [C.c_int, P, P]),
-            ("v2v_lpips_stem_bwd_hip", C.c_int, [P] + [I64] * 4 + [P, P, C.c_int, P, P]),
-            ("v2v_lpips_pool_hip", C.c_int, [P] + [I64] * 4 + [P, P]),
-            ("v2v_lpips_pool_bwd_hip", C.c_int, [P, P, P, C.c_int] + [I64] * 4 + [P, P]),
-            ("v2v_lpips_compare_workspace_bytes", I64, [I64, I64]),
-            ("v2v_lpips_compare_fwd_hip", C.c_int, [P, P, P] + [I64] * 3 + [P, P, P]),
-            ("v2v_lpips_compare_bwd_hip", C.c_int, [P, P, P, P] + [I64] * 3 + [P, P])):
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     if L.v2v_version() != ABI_VERSION:
@@ -284,12 +210,11 @@ def lib():
     return L
 
 
-def check(rc: int, last_error: str = "v2v_last_error"):
-    """Map a v2v_status to the exception the reference would raise at the same spot.  last_error: the entry point that holds the text
-    (the dynamic decoder's training entry points keep theirs in v2v_hyper_train_last_error)."""
+def check(rc: int):
+    """Map a v2v_status to the exception the reference would raise at the same spot."""
     if rc == OK:
         return
-    msg = getattr(lib(), last_error)().decode()
+    msg = lib().v2v_last_error().decode()
     if rc == ERR_BINS:
         raise AssertionError(msg)            # reference: `assert (N-1) % (num_bins*frames_per_bin) == 0`
     if rc in (ERR_SHAPE, ERR_DTYPE, ERR_MODE, ERR_PARAM, ERR_NULL, ERR_ALIGN):

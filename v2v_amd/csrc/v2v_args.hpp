@@ -111,31 +111,23 @@ struct ConvLstmArgs {
     float *dc_prev;
 };
 hipError_t launch_convlstm_step(const ConvLstmArgs &a, int tile_rows, hipStream_t s);   // tile_rows: 0 auto, 64, 128 or 256
-hipError_t launch_convlstm_pack(const float *w, uint16_t *wp, int C, hipStream_t s);
 hipError_t launch_convlstm_step_bwd(const ConvLstmArgs &a, hipStream_t s);
 // the ConvGRU step (v2v_convgru_tu.hip; how the two launches read ConvLstmArgs: v2v_convgru.hpp).  tile: instance code, 0 = auto
 hipError_t launch_convgru_gates(const ConvLstmArgs &a, int tile, hipStream_t s);
 hipError_t launch_convgru_candidate(const ConvLstmArgs &a, int tile, hipStream_t s);
-hipError_t launch_convgru_pack(const float *w_u, const float *w_r, const float *w_o, uint16_t *wp_gates, uint16_t *wp_cand, int C, hipStream_t s);
 bool convgru_tile_ok(int C, int tile_gates, int tile_cand);
 // backward passes of the recurrent UNet (v2v_train_tu.hip)
 int64_t wgrad_slabs(int64_t M, int Cout, int64_t N);
 hipError_t launch_conv_wgrad(const uint16_t *dy, const uint16_t *x1, int C1, const uint16_t *x2, int C2, int Cin_out, float *dw, float *db, float *ws,
                              int B, int Hin, int Win, int Ho, int Wo, int Cout, int ks, int stride, hipStream_t s);
 hipError_t launch_relu_mask_stuff(const uint16_t *dy, const uint16_t *y, uint16_t *out, int B, int Ho, int Wo, int C, int stride, hipStream_t s);
-hipError_t launch_dgrad_flip(const float *w, float *wt, int Cout, int Cin, int ks, hipStream_t s);
 int64_t conv1x1_bwd_slabs(int64_t M);
 hipError_t launch_conv_nhwc(const ConvLstmArgs &a, int tile_rows, hipStream_t s, int64_t like_b = 0);   // like_b: batch the automatic tile is chosen for (0: a.B)
 int conv_tile_cols(int Cout);             // columns per tile of the instance launch_conv_nhwc takes for Cout (0: unsupported)
-hipError_t launch_conv_head(const uint16_t *x8, const uint16_t *wp, const float *bias, uint16_t *out, int B, int H, int W, int ks, int relu, hipStream_t s);
-hipError_t launch_conv_head_pack(const float *w, uint16_t *wp, int Cin, int ks, hipStream_t s);
-hipError_t launch_conv_stem(const uint16_t *x8, const uint16_t *wp, const float *bias, uint16_t *out, int B, int H, int W, int relu, hipStream_t s);
-hipError_t launch_conv_stem_pack(const float *w, uint16_t *wp, int Cin, hipStream_t s);
 hipError_t launch_upsample2x_cat_nhwc(const uint16_t *x, int C1, const uint16_t *skip, int C2, uint16_t *out, int B, int H, int W, hipStream_t s);
 hipError_t launch_upsample2x_cat_bwd(const uint16_t *dout, uint16_t *dx, int B, int H, int W, int Ctot, int c0, int C, hipStream_t s);
 hipError_t launch_conv1x1_bwd_cout(const float *dy, const uint16_t *x, const uint16_t *skip, const float *w, uint16_t *dx, float *dw, float *db, float *ws,
                                    int64_t M, int C, int Cout, hipStream_t s);
-hipError_t launch_to_nhwc8_bf16(const float *src, int64_t sb, int64_t sc, int64_t sh, int64_t sw, uint16_t *dst, int B, int C, int H, int W, const float *scales, hipStream_t s);
 hipError_t launch_conv1x1_nhwc(const uint16_t *x, const uint16_t *skip, const float *w, const float *bias, void *out, int out_bf16, int64_t M,
                                int C, int Cout, hipStream_t s);
 hipError_t launch_upsample2x_nhwc(const uint16_t *x, const uint16_t *skip, uint16_t *out, int B, int H, int W, int C, hipStream_t s);

@@ -1,6 +1,8 @@
-// v2v_capi.hip -- the C ABI of libv2v_hip.so (include/v2v_hip.h).  Argument validation, kernel
-// dispatch on (input dtype, vector width, bin mode, rng mode), error reporting.  Single translation unit:
-// the kernels live in the headers included below.  gfx950 only; no CPU fallback behind any entry point.
+// v2v_capi.hip -- the core of libv2v_hip.so's C ABI (include/v2v_hip.h) and the entry points of the front side: version, the error
+// slot every entry point of the library writes (v2v_status.hpp), the log-intensity tables, ESIM, v2e, events, the video front end, the
+// post-ops, the synthetic clips and the clip frames.  Argument validation, kernel dispatch on (input dtype, vector width, bin mode, rng
+// mode).  The kernels live in the headers included below.  The entry points of the network, loss, LPIPS and HyperE2VID families live in
+// the translation unit that launches their kernels (v2v_*_tu.hip).  gfx950 only; no CPU fallback behind any entry point.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,6 +12,7 @@
 #include <cstring>
 
 #include "../../include/v2v_hip.h"
+#include "v2v_status.hpp"
 #include "v2v_args.hpp"
 #include "v2v_launch.hpp"
 #include "v2v_rng.hpp"
@@ -18,14 +21,17 @@
 #include "v2v_postops.hpp"
 #include "v2v_synth.hpp"
 #include "v2v_assemble.hpp"
-#include "v2v_hyper.hpp"
-#include "v2v_narrow.hpp"
-#include "v2v_loss.hpp"
-#include "v2v_lpips.hpp"
 
 namespace {
 
-thread_local char g_err[512] = "";
+thread_local char g_err[512] = "";      // the library's one error slot (v2v_last_error)
+
+// SIMDs of the current device (4 per CU); 1024 when the query fails
+int simd_count() { return 4 * v2v::device_cus(); }
+
+}  // namespace
+
+namespace v2v {
 
 int fail(int code, const char *fmt, ...)
 {
@@ -41,12 +47,17 @@ int hip_fail(hipError_t e, const char *what)
     return fail(V2V_ERR_HIP, "%s: %s (%d)", what, hipGetErrorString(e), (int)e);
 }
 
-bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+int launched(const char *what)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? V2V_OK : hip_fail(e, what);
+}
 
-// SIMDs of the current device (4 per CU); 1024 when the query fails
-int simd_count() { return 4 * v2v::device_cus(); }
+}  // namespace v2v
 
-}  // namespace
+using v2v::aligned;
+using v2v::fail;
+using v2v::hip_fail;
 
 extern "C" {
 
@@ -120,78 +131,6 @@ int v2v_esim_voxel_keyed_hip(const void *frames, int in_dtype, int64_t B, int64_
     return v2v_esim_voxel_padded_hip(frames, in_dtype, B, N, H, W, clip_stride, frame_stride, params, params_stride, flags, rng_mode, seed,
                                      clip_id0, clip_keys, replay, bin_mode, num_bins, frames_per_bin, out_voxel, out_dtype, W, H * W,
                                      out_counts, stream);
-}
-
-static int esim_launch_impl(const void *frames, int in_dtype, int64_t B, int64_t N, int64_t H, int64_t W,
-                            int64_t clip_stride, int64_t frame_stride, const double *params, int64_t params_stride,
-                            uint32_t flags, int rng_mode, uint64_t seed, uint64_t clip_id0, const uint64_t *clip_keys,
-                            const v2v_esim_replay *replay, int bin_mode, int num_bins, int frames_per_bin,
-                            void *out_voxel, int out_dtype, int64_t out_row_pitch, int64_t out_plane_size, int64_t *out_counts, uint32_t *stats,
-                            const int32_t *frame_index, const int64_t *clip_offsets, const int32_t *stored_frames, int64_t frames_elems, void *stream);
-
-int v2v_esim_voxel_padded_hip(const void *frames, int in_dtype, int64_t B, int64_t N, int64_t H, int64_t W,
-                              int64_t clip_stride, int64_t frame_stride, const double *params, int64_t params_stride,
-                              uint32_t flags, int rng_mode, uint64_t seed, uint64_t clip_id0, const uint64_t *clip_keys,
-                              const v2v_esim_replay *replay, int bin_mode, int num_bins, int frames_per_bin,
-                              void *out_voxel, int out_dtype, int64_t out_row_pitch, int64_t out_plane_size, int64_t *out_counts, void *stream)
-{
-    return esim_launch_impl(frames, in_dtype, B, N, H, W, clip_stride, frame_stride, params, params_stride, flags, rng_mode, seed, clip_id0, clip_keys,
-                            replay, bin_mode, num_bins, frames_per_bin, out_voxel, out_dtype, out_row_pitch, out_plane_size, out_counts, nullptr, nullptr, nullptr, nullptr, 0, stream);
-}
-
-int v2v_esim_voxel_ex_hip(const void *frames, int in_dtype, int64_t B, int64_t N, int64_t H, int64_t W,
-                          int64_t clip_stride, int64_t frame_stride, const double *params, int64_t params_stride,
-                          uint32_t flags, int rng_mode, uint64_t seed, uint64_t clip_id0, const uint64_t *clip_keys,
-                          const v2v_esim_replay *replay, int bin_mode, int num_bins, int frames_per_bin,
-                          void *out_voxel, int out_dtype, int64_t out_row_pitch, int64_t out_plane_size, int64_t *out_counts,
-                          const v2v_esim_extras *extras, void *stream)
-{
-    if (!extras) return v2v_esim_voxel_padded_hip(frames, in_dtype, B, N, H, W, clip_stride, frame_stride, params, params_stride, flags, rng_mode, seed, clip_id0,
-                                                  clip_keys, replay, bin_mode, num_bins, frames_per_bin, out_voxel, out_dtype, out_row_pitch, out_plane_size,
-                                                  out_counts, stream);
-    if ((extras->frame_index == nullptr) != (extras->clip_offsets == nullptr))
-        return fail(V2V_ERR_NULL, "v2v_esim_voxel_ex_hip: frame_index and clip_offsets come together");
-    if (extras->frame_index) {
-        if (in_dtype != V2V_U8 || bin_mode != V2V_BIN_SUM || out_dtype != V2V_F32 || rng_mode == V2V_RNG_REPLAY || rng_mode == V2V_RNG_NONE ||
-            (flags & (V2V_FLAG_NOISE_EXTERNAL | V2V_FLAG_NO_NOISE | V2V_FLAG_SYMMETRIC)))
-            return fail(V2V_ERR_MODE, "indexed frames: uint8 clips, SUM bins, device noise, float32 grid, no NO_NOISE / NOISE_EXTERNAL / SYMMETRIC flag");
-        if (!aligned(extras->frame_index, 4) || !aligned(extras->clip_offsets, 8) || !aligned(extras->stored_frames, 4))
-            return fail(V2V_ERR_ALIGN, "frame_index / clip_offsets / stored_frames misaligned");
-        if (extras->frames_elems < 0) return fail(V2V_ERR_SHAPE, "frames_elems must be >= 0 (0: not stated)");
-    } else if (extras->stored_frames || extras->frames_elems) {
-        return fail(V2V_ERR_NULL, "v2v_esim_voxel_ex_hip: stored_frames / frames_elems bound the frame_index gather and come with it");
-    }
-    if (extras->stats) {
-        if (bin_mode != V2V_BIN_SUM || out_dtype != V2V_F32 || (flags & V2V_FLAG_NOISE_EXTERNAL))
-            return fail(V2V_ERR_MODE, "voxel statistics are kept for SUM-mode float32 grids without external noise (integer counts)");
-        if (!aligned(extras->stats, 4)) return fail(V2V_ERR_ALIGN, "stats must be 4-byte aligned");
-        if (B > 0) {
-            const hipError_t e = hipMemsetAsync(extras->stats, 0, sizeof(uint32_t) * (size_t)B * V2V_VOXEL_STATS_WORDS, static_cast<hipStream_t>(stream));
-            if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(stats)");
-        }
-    }
-    return esim_launch_impl(frames, in_dtype, B, N, H, W, clip_stride, frame_stride, params, params_stride, flags, rng_mode, seed, clip_id0, clip_keys,
-                            replay, bin_mode, num_bins, frames_per_bin, out_voxel, out_dtype, out_row_pitch, out_plane_size, out_counts, extras->stats,
-                            extras->frame_index, extras->clip_offsets, extras->stored_frames, extras->frames_elems, stream);
-}
-
-int v2v_esim_voxel_stats_hip(const void *frames, int in_dtype, int64_t B, int64_t N, int64_t H, int64_t W,
-                             int64_t clip_stride, int64_t frame_stride, const double *params, int64_t params_stride,
-                             uint32_t flags, int rng_mode, uint64_t seed, uint64_t clip_id0, const uint64_t *clip_keys,
-                             const v2v_esim_replay *replay, int bin_mode, int num_bins, int frames_per_bin,
-                             void *out_voxel, int out_dtype, int64_t out_row_pitch, int64_t out_plane_size, int64_t *out_counts, uint32_t *stats,
-                             void *stream)
-{
-    if (!stats) return fail(V2V_ERR_NULL, "v2v_esim_voxel_stats_hip: stats is NULL");
-    if (bin_mode != V2V_BIN_SUM || out_dtype != V2V_F32 || (flags & V2V_FLAG_NOISE_EXTERNAL))
-        return fail(V2V_ERR_MODE, "voxel statistics are kept for SUM-mode float32 grids without external noise (integer counts)");
-    if (!aligned(stats, 4)) return fail(V2V_ERR_ALIGN, "stats must be 4-byte aligned");
-    if (B > 0) {
-        const hipError_t e = hipMemsetAsync(stats, 0, sizeof(uint32_t) * (size_t)B * V2V_VOXEL_STATS_WORDS, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(stats)");
-    }
-    return esim_launch_impl(frames, in_dtype, B, N, H, W, clip_stride, frame_stride, params, params_stride, flags, rng_mode, seed, clip_id0, clip_keys,
-                            replay, bin_mode, num_bins, frames_per_bin, out_voxel, out_dtype, out_row_pitch, out_plane_size, out_counts, stats, nullptr, nullptr, nullptr, 0, stream);
 }
 
 int v2v_voxel_scales_hip(const uint32_t *stats, int64_t B, int64_t elems_per_sample, float *scales, void *stream)
@@ -347,6 +286,72 @@ static int esim_launch_impl(const void *frames, int in_dtype, int64_t B, int64_t
     e = in_dtype == V2V_U8 ? v2v::launch_esim_u8(vec, bin_mode, rng_mode, noise, out64, a, grid, lds, s)
                            : v2v::launch_esim_f32(vec, bin_mode, rng_mode, noise, out64, a, grid, lds, s);
     return e == hipSuccess ? V2V_OK : hip_fail(e, "esim_voxel_kernel launch");
+}
+
+int v2v_esim_voxel_padded_hip(const void *frames, int in_dtype, int64_t B, int64_t N, int64_t H, int64_t W,
+                              int64_t clip_stride, int64_t frame_stride, const double *params, int64_t params_stride,
+                              uint32_t flags, int rng_mode, uint64_t seed, uint64_t clip_id0, const uint64_t *clip_keys,
+                              const v2v_esim_replay *replay, int bin_mode, int num_bins, int frames_per_bin,
+                              void *out_voxel, int out_dtype, int64_t out_row_pitch, int64_t out_plane_size, int64_t *out_counts, void *stream)
+{
+    return esim_launch_impl(frames, in_dtype, B, N, H, W, clip_stride, frame_stride, params, params_stride, flags, rng_mode, seed, clip_id0, clip_keys,
+                            replay, bin_mode, num_bins, frames_per_bin, out_voxel, out_dtype, out_row_pitch, out_plane_size, out_counts, nullptr, nullptr, nullptr, nullptr, 0, stream);
+}
+
+// the statistics words of the _ex and _stats forms: this mode keeps them, the buffer is aligned, and it is zeroed on the stream
+static int esim_stats_begin(uint32_t *stats, int64_t B, uint32_t flags, int bin_mode, int out_dtype, void *stream)
+{
+    if (bin_mode != V2V_BIN_SUM || out_dtype != V2V_F32 || (flags & V2V_FLAG_NOISE_EXTERNAL))
+        return fail(V2V_ERR_MODE, "voxel statistics are kept for SUM-mode float32 grids without external noise (integer counts)");
+    if (!aligned(stats, 4)) return fail(V2V_ERR_ALIGN, "stats must be 4-byte aligned");
+    if (B > 0) {
+        const hipError_t e = hipMemsetAsync(stats, 0, sizeof(uint32_t) * (size_t)B * V2V_VOXEL_STATS_WORDS, static_cast<hipStream_t>(stream));
+        if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(stats)");
+    }
+    return V2V_OK;
+}
+
+int v2v_esim_voxel_ex_hip(const void *frames, int in_dtype, int64_t B, int64_t N, int64_t H, int64_t W,
+                          int64_t clip_stride, int64_t frame_stride, const double *params, int64_t params_stride,
+                          uint32_t flags, int rng_mode, uint64_t seed, uint64_t clip_id0, const uint64_t *clip_keys,
+                          const v2v_esim_replay *replay, int bin_mode, int num_bins, int frames_per_bin,
+                          void *out_voxel, int out_dtype, int64_t out_row_pitch, int64_t out_plane_size, int64_t *out_counts,
+                          const v2v_esim_extras *extras, void *stream)
+{
+    if (!extras) return v2v_esim_voxel_padded_hip(frames, in_dtype, B, N, H, W, clip_stride, frame_stride, params, params_stride, flags, rng_mode, seed, clip_id0,
+                                                  clip_keys, replay, bin_mode, num_bins, frames_per_bin, out_voxel, out_dtype, out_row_pitch, out_plane_size,
+                                                  out_counts, stream);
+    if ((extras->frame_index == nullptr) != (extras->clip_offsets == nullptr))
+        return fail(V2V_ERR_NULL, "v2v_esim_voxel_ex_hip: frame_index and clip_offsets come together");
+    if (extras->frame_index) {
+        if (in_dtype != V2V_U8 || bin_mode != V2V_BIN_SUM || out_dtype != V2V_F32 || rng_mode == V2V_RNG_REPLAY || rng_mode == V2V_RNG_NONE ||
+            (flags & (V2V_FLAG_NOISE_EXTERNAL | V2V_FLAG_NO_NOISE | V2V_FLAG_SYMMETRIC)))
+            return fail(V2V_ERR_MODE, "indexed frames: uint8 clips, SUM bins, device noise, float32 grid, no NO_NOISE / NOISE_EXTERNAL / SYMMETRIC flag");
+        if (!aligned(extras->frame_index, 4) || !aligned(extras->clip_offsets, 8) || !aligned(extras->stored_frames, 4))
+            return fail(V2V_ERR_ALIGN, "frame_index / clip_offsets / stored_frames misaligned");
+        if (extras->frames_elems < 0) return fail(V2V_ERR_SHAPE, "frames_elems must be >= 0 (0: not stated)");
+    } else if (extras->stored_frames || extras->frames_elems) {
+        return fail(V2V_ERR_NULL, "v2v_esim_voxel_ex_hip: stored_frames / frames_elems bound the frame_index gather and come with it");
+    }
+    if (extras->stats) {
+        if (const int rc = esim_stats_begin(extras->stats, B, flags, bin_mode, out_dtype, stream)) return rc;
+    }
+    return esim_launch_impl(frames, in_dtype, B, N, H, W, clip_stride, frame_stride, params, params_stride, flags, rng_mode, seed, clip_id0, clip_keys,
+                            replay, bin_mode, num_bins, frames_per_bin, out_voxel, out_dtype, out_row_pitch, out_plane_size, out_counts, extras->stats,
+                            extras->frame_index, extras->clip_offsets, extras->stored_frames, extras->frames_elems, stream);
+}
+
+int v2v_esim_voxel_stats_hip(const void *frames, int in_dtype, int64_t B, int64_t N, int64_t H, int64_t W,
+                             int64_t clip_stride, int64_t frame_stride, const double *params, int64_t params_stride,
+                             uint32_t flags, int rng_mode, uint64_t seed, uint64_t clip_id0, const uint64_t *clip_keys,
+                             const v2v_esim_replay *replay, int bin_mode, int num_bins, int frames_per_bin,
+                             void *out_voxel, int out_dtype, int64_t out_row_pitch, int64_t out_plane_size, int64_t *out_counts, uint32_t *stats,
+                             void *stream)
+{
+    if (!stats) return fail(V2V_ERR_NULL, "v2v_esim_voxel_stats_hip: stats is NULL");
+    if (const int rc = esim_stats_begin(stats, B, flags, bin_mode, out_dtype, stream)) return rc;
+    return esim_launch_impl(frames, in_dtype, B, N, H, W, clip_stride, frame_stride, params, params_stride, flags, rng_mode, seed, clip_id0, clip_keys,
+                            replay, bin_mode, num_bins, frames_per_bin, out_voxel, out_dtype, out_row_pitch, out_plane_size, out_counts, stats, nullptr, nullptr, nullptr, 0, stream);
 }
 
 int v2v_clip_frames_f32_hip(const void *src, int64_t clip_stride, int64_t frame_stride, const int32_t *pick, int64_t B, int64_t L, int64_t H,
@@ -819,867 +824,6 @@ int v2v_events_to_voxel_f32_segmented_hip(const double *ts, const int64_t *xs, c
     if (!seg_offsets) return fail(V2V_ERR_NULL, "v2v_events_to_voxel_f32_segmented_hip: seg_offsets is NULL");
     return events_f32_launch(nullptr, ts, xs, ys, ps, n, seg_offsets, n_segments, min_events, discrete, num_bins, H, W, out_voxel, dropped,
                              stream, "v2v_events_to_voxel_f32_segmented_hip");
-}
-
-int v2v_convlstm_packed_bytes(int64_t C, uint64_t *bytes)
-{
-    if (!bytes) return fail(V2V_ERR_NULL, "v2v_convlstm_packed_bytes: bytes is NULL");
-    if (C < 64 || C % 64 != 0) return fail(V2V_ERR_SHAPE, "ConvLSTM kernel needs C %% 64 == 0 (got %lld)", (long long)C);
-    *bytes = (uint64_t)4 * C * 2 * C * 9 * 2;
-    return V2V_OK;
-}
-
-int v2v_convlstm_pack_weights_hip(const float *gates_weight, int64_t C, void *packed, void *stream)
-{
-    if (!gates_weight || !packed) return fail(V2V_ERR_NULL, "v2v_convlstm_pack_weights_hip: gates_weight/packed is NULL");
-    if (C < 64 || C % 64 != 0 || C > 4096) return fail(V2V_ERR_SHAPE, "ConvLSTM kernel needs C %% 64 == 0, C <= 4096 (got %lld)", (long long)C);
-    if (!aligned(gates_weight, 4) || !aligned(packed, 16)) return fail(V2V_ERR_ALIGN, "gates_weight needs 4-byte, packed 16-byte alignment");
-    const hipError_t e = v2v::launch_convlstm_pack(gates_weight, static_cast<uint16_t *>(packed), (int)C, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "convlstm_pack_kernel launch");
-}
-
-int v2v_convlstm_step_hip(const void *x, const void *h_prev, const float *c_prev, const void *packed, const float *gates_bias,
-                          int64_t B, int64_t H, int64_t W, int64_t C, void *h_state, float *c_state, void *h_nchw, int h_nchw_dtype, int tile_rows, void *stream)
-{
-    if (h_nchw && h_nchw_dtype != V2V_F32 && h_nchw_dtype != V2V_BF16) return fail(V2V_ERR_DTYPE, "h_nchw_dtype must be V2V_F32 or V2V_BF16");
-    if (!x || !packed || !gates_bias || !h_state || !c_state) return fail(V2V_ERR_NULL, "v2v_convlstm_step_hip: x/packed/gates_bias/h_state/c_state is NULL");
-    if (B < 1 || H < 1 || W < 1 || C < 64 || C % 64 != 0 || C > 4096) return fail(V2V_ERR_SHAPE, "need B,H,W >= 1 and C %% 64 == 0, C <= 4096");
-    if (tile_rows != 0 && tile_rows != 64 && tile_rows != 128 && tile_rows != 256) return fail(V2V_ERR_PARAM, "tile_rows must be 0 (auto), 64, 128 or 256");
-    if ((H * W) % 4 != 0 || B * H * W * C > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "ConvLSTM kernel needs (H*W) %% 4 == 0 and B*H*W*C < 2^31 (got %lldx%lldx%lldx%lld)",
-                    (long long)B, (long long)H, (long long)W, (long long)C);
-    if (h_state == h_prev || h_state == x) return fail(V2V_ERR_PARAM, "h_state must not alias h_prev or x (neighbouring tiles read them)");
-    if (!aligned(x, 16) || !aligned(h_prev, 16) || !aligned(packed, 16) || !aligned(h_state, 2) || !aligned(c_prev, 4) || !aligned(c_state, 4) ||
-        !aligned(gates_bias, 4) || !aligned(h_nchw, 16))
-        return fail(V2V_ERR_ALIGN, "x/h_prev/packed/h_nchw need 16-byte alignment");
-    v2v::ConvLstmArgs a{};
-    a.x = static_cast<const uint16_t *>(x); a.h_prev = static_cast<const uint16_t *>(h_prev); a.c_prev = c_prev;
-    a.wp = static_cast<const uint16_t *>(packed); a.bias = gates_bias;
-    a.h_state = static_cast<uint16_t *>(h_state); a.c_state = c_state; a.h_nchw = h_nchw; a.h_nchw_bf16 = h_nchw_dtype == V2V_BF16;
-    a.B = (int)B; a.H = (int)H; a.W = (int)W; a.C = (int)C;
-    const hipError_t e = v2v::launch_convlstm_step(a, tile_rows, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "convlstm_step_kernel launch");
-}
-
-int v2v_convgru_packed_bytes(int64_t C, uint64_t *gates_bytes, uint64_t *cand_bytes)
-{
-    if (!gates_bytes || !cand_bytes) return fail(V2V_ERR_NULL, "v2v_convgru_packed_bytes: gates_bytes/cand_bytes is NULL");
-    if (C < 64 || C % 64 != 0 || C > 4096) return fail(V2V_ERR_SHAPE, "ConvGRU kernel needs C %% 64 == 0, C <= 4096 (got %lld)", (long long)C);
-    *gates_bytes = (uint64_t)2 * C * 2 * C * 9 * 2;
-    *cand_bytes = (uint64_t)C * 2 * C * 9 * 2;
-    return V2V_OK;
-}
-
-int v2v_convgru_pack_weights_hip(const float *update_weight, const float *reset_weight, const float *out_weight, int64_t C, void *packed_gates,
-                                 void *packed_cand, void *stream)
-{
-    if (!update_weight || !reset_weight || !out_weight || !packed_gates || !packed_cand)
-        return fail(V2V_ERR_NULL, "v2v_convgru_pack_weights_hip: a weight or packed pointer is NULL");
-    if (C < 64 || C % 64 != 0 || C > 4096) return fail(V2V_ERR_SHAPE, "ConvGRU kernel needs C %% 64 == 0, C <= 4096 (got %lld)", (long long)C);
-    if (!aligned(update_weight, 4) || !aligned(reset_weight, 4) || !aligned(out_weight, 4) || !aligned(packed_gates, 16) || !aligned(packed_cand, 16))
-        return fail(V2V_ERR_ALIGN, "weights need 4-byte, packed streams 16-byte alignment");
-    const hipError_t e = v2v::launch_convgru_pack(update_weight, reset_weight, out_weight, static_cast<uint16_t *>(packed_gates),
-                                                  static_cast<uint16_t *>(packed_cand), (int)C, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "convgru_pack_kernel launch");
-}
-
-int v2v_convgru_step_hip(const void *x, const void *h_prev, const float *h_prev_f32, const void *packed_gates, const void *packed_cand,
-                         const float *gates_bias, const float *out_bias, int64_t B, int64_t H, int64_t W, int64_t C, float *u_ws, void *hr_ws,
-                         void *h_state, float *h_state_f32, void *h_nchw, int h_nchw_dtype, int tile_gates, int tile_cand, void *stream)
-{
-    if (h_nchw && h_nchw_dtype != V2V_F32 && h_nchw_dtype != V2V_BF16) return fail(V2V_ERR_DTYPE, "h_nchw_dtype must be V2V_F32 or V2V_BF16");
-    if (!x || !packed_gates || !packed_cand || !gates_bias || !out_bias || !u_ws || !hr_ws || !h_state || !h_state_f32)
-        return fail(V2V_ERR_NULL, "v2v_convgru_step_hip: x/packed_gates/packed_cand/gates_bias/out_bias/u_ws/hr_ws/h_state/h_state_f32 is NULL");
-    if ((h_prev == nullptr) != (h_prev_f32 == nullptr)) return fail(V2V_ERR_NULL, "h_prev and h_prev_f32 come together (both NULL: the zero state)");
-    if (B < 1 || H < 1 || W < 1 || C < 64 || C % 64 != 0 || C > 4096) return fail(V2V_ERR_SHAPE, "need B,H,W >= 1 and C %% 64 == 0, C <= 4096");
-    if ((H * W) % 4 != 0 || B * H * W * C > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "ConvGRU kernel needs (H*W) %% 4 == 0 and B*H*W*C < 2^31 (got %lldx%lldx%lldx%lld)",
-                    (long long)B, (long long)H, (long long)W, (long long)C);
-    if (!v2v::convgru_tile_ok((int)C, tile_gates, tile_cand))
-        return fail(V2V_ERR_PARAM, "tile_gates / tile_cand must be 0 (auto) or an instance code 1..5 whose columns divide C (got %d, %d for C = %lld)",
-                    tile_gates, tile_cand, (long long)C);
-    if (h_state == h_prev || h_state == x || h_state == hr_ws || hr_ws == h_prev || hr_ws == x || static_cast<void *>(u_ws) == static_cast<void *>(h_state_f32) ||
-        u_ws == h_prev_f32)
-        return fail(V2V_ERR_PARAM, "h_state / hr_ws must not alias x, h_prev or each other, u_ws not the fp32 states (neighbouring tiles read them)");
-    if (!aligned(x, 16) || !aligned(h_prev, 16) || !aligned(hr_ws, 16) || !aligned(packed_gates, 16) || !aligned(packed_cand, 16) || !aligned(h_state, 2) ||
-        !aligned(h_prev_f32, 4) || !aligned(h_state_f32, 4) || !aligned(u_ws, 4) || !aligned(gates_bias, 4) || !aligned(out_bias, 4) || !aligned(h_nchw, 16))
-        return fail(V2V_ERR_ALIGN, "x/h_prev/hr_ws/packed_gates/packed_cand/h_nchw need 16-byte alignment");
-    v2v::ConvLstmArgs g{};
-    g.x = static_cast<const uint16_t *>(x); g.h_prev = static_cast<const uint16_t *>(h_prev); g.c_prev = h_prev_f32;
-    g.wp = static_cast<const uint16_t *>(packed_gates); g.bias = gates_bias;
-    g.h_state = static_cast<uint16_t *>(hr_ws); g.c_state = u_ws;
-    g.B = (int)B; g.H = (int)H; g.W = (int)W; g.C = (int)C;
-    hipError_t e = v2v::launch_convgru_gates(g, tile_gates, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "ConvGRU gates launch");
-    v2v::ConvLstmArgs c{};
-    c.x = g.x; c.h_prev = h_prev ? static_cast<const uint16_t *>(hr_ws) : nullptr; c.c_prev = h_prev_f32;
-    c.wp = static_cast<const uint16_t *>(packed_cand); c.bias = out_bias; c.dh = u_ws;
-    c.h_state = static_cast<uint16_t *>(h_state); c.c_state = h_state_f32; c.h_nchw = h_nchw; c.h_nchw_bf16 = h_nchw_dtype == V2V_BF16;
-    c.B = (int)B; c.H = (int)H; c.W = (int)W; c.C = (int)C;
-    e = v2v::launch_convgru_candidate(c, tile_cand, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "ConvGRU candidate launch");
-}
-
-// ---- the 16-channel layer family (v2v_narrow.hpp): one launch per layer ----
-namespace {
-int narrow_shape(const char *who, int64_t B, int64_t H, int64_t W, v2v::NarrowArgs &a)
-{
-    if (B < 1 || H < 1 || W < 1 || B * H * W * 16 > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "%s: need B,H,W >= 1 and B*H*W*16 < 2^31 (got %lldx%lldx%lld)", who, (long long)B, (long long)H, (long long)W);
-    a.B = (int)B; a.H = (int)H; a.W = (int)W; a.tiles_x = (int)((W + 15) / 16); a.tiles_y = (int)((H + 15) / 16);
-    if (B * a.tiles_x * a.tiles_y > 0x7FFFFFFFLL) return fail(V2V_ERR_SHAPE, "%s: too many tiles", who);
-    return V2V_OK;
-}
-}  // namespace
-
-int64_t v2v_convgru16_packed_elems(void) { return (int64_t)v2v::kGru16Frags * v2v::kNarrowFragElems; }
-int64_t v2v_resblock16_packed_elems(void) { return (int64_t)v2v::kRes16Frags * v2v::kNarrowFragElems; }
-int64_t v2v_conv_head16_packed_elems(void) { return (int64_t)v2v::kHead16Frags * v2v::kNarrowFragElems; }
-
-int v2v_convgru16_pack_weights_hip(const float *update_weight, const float *reset_weight, const float *out_weight, void *packed, void *stream)
-{
-    if (!update_weight || !reset_weight || !out_weight || !packed) return fail(V2V_ERR_NULL, "v2v_convgru16_pack_weights_hip: a weight or packed pointer is NULL");
-    if (!aligned(update_weight, 4) || !aligned(reset_weight, 4) || !aligned(out_weight, 4) || !aligned(packed, 16))
-        return fail(V2V_ERR_ALIGN, "weights need 4-byte, packed 16-byte alignment");
-    const hipError_t e = v2v::launch_convgru16_pack(update_weight, reset_weight, out_weight, static_cast<uint16_t *>(packed), static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "narrow_pack_kernel launch");
-}
-
-int v2v_convgru16_step_hip(const void *x, const void *h_prev, const float *h_prev_f32, const void *packed, const float *gates_bias,
-                           const float *out_bias, int64_t B, int64_t H, int64_t W, void *h_state, float *h_state_f32, void *h_nchw,
-                           int h_nchw_dtype, void *stream)
-{
-    if (h_nchw && h_nchw_dtype != V2V_F32 && h_nchw_dtype != V2V_BF16) return fail(V2V_ERR_DTYPE, "h_nchw_dtype must be V2V_F32 or V2V_BF16");
-    if (!x || !packed || !gates_bias || !out_bias || !h_state || !h_state_f32)
-        return fail(V2V_ERR_NULL, "v2v_convgru16_step_hip: x/packed/gates_bias/out_bias/h_state/h_state_f32 is NULL");
-    if ((h_prev == nullptr) != (h_prev_f32 == nullptr)) return fail(V2V_ERR_NULL, "h_prev and h_prev_f32 come together (both NULL: the zero state)");
-    v2v::NarrowArgs a{};
-    if (const int rc = narrow_shape("v2v_convgru16_step_hip", B, H, W, a)) return rc;
-    if (h_state == h_prev || h_state == x || (h_prev_f32 && h_state_f32 == h_prev_f32) ||
-        (h_nchw && (h_nchw == x || h_nchw == h_prev || h_nchw == h_prev_f32)))
-        return fail(V2V_ERR_PARAM, "h_state must not alias h_prev or x, h_state_f32 not h_prev_f32 (neighbouring tiles read them)");
-    if (!aligned(x, 16) || !aligned(h_prev, 16) || !aligned(packed, 16) || !aligned(h_state, 16) || !aligned(h_prev_f32, 4) || !aligned(h_state_f32, 4) ||
-        !aligned(gates_bias, 4) || !aligned(out_bias, 4) || !aligned(h_nchw, 4))
-        return fail(V2V_ERR_ALIGN, "x/h_prev/packed/h_state need 16-byte alignment");
-    a.x = static_cast<const uint16_t *>(x); a.h_prev = static_cast<const uint16_t *>(h_prev); a.h_prev_f32 = h_prev_f32;
-    a.wp = static_cast<const uint16_t *>(packed); a.bias1 = gates_bias; a.bias2 = out_bias;
-    a.out = static_cast<uint16_t *>(h_state); a.out_f32 = h_state_f32; a.h_nchw = h_nchw; a.h_nchw_bf16 = h_nchw_dtype == V2V_BF16;
-    const hipError_t e = v2v::launch_convgru16(a, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "narrow_two_conv_kernel<0> (ConvGRU) launch");
-}
-
-int v2v_resblock16_pack_weights_hip(const float *w1, const float *w2, void *packed, void *stream)
-{
-    if (!w1 || !w2 || !packed) return fail(V2V_ERR_NULL, "v2v_resblock16_pack_weights_hip: w1/w2/packed is NULL");
-    if (!aligned(w1, 4) || !aligned(w2, 4) || !aligned(packed, 16)) return fail(V2V_ERR_ALIGN, "weights need 4-byte, packed 16-byte alignment");
-    const hipError_t e = v2v::launch_resblock16_pack(w1, w2, static_cast<uint16_t *>(packed), static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "narrow_pack_kernel launch");
-}
-
-int v2v_resblock16_nhwc_hip(const void *x, const void *packed, const float *b1, const float *b2, int64_t B, int64_t H, int64_t W, void *out, void *stream)
-{
-    if (!x || !packed || !b1 || !b2 || !out) return fail(V2V_ERR_NULL, "v2v_resblock16_nhwc_hip: x/packed/b1/b2/out is NULL");
-    v2v::NarrowArgs a{};
-    if (const int rc = narrow_shape("v2v_resblock16_nhwc_hip", B, H, W, a)) return rc;
-    if (out == x) return fail(V2V_ERR_PARAM, "out must not alias x (neighbouring tiles read it)");
-    if (!aligned(x, 16) || !aligned(packed, 16) || !aligned(out, 16) || !aligned(b1, 4) || !aligned(b2, 4)) return fail(V2V_ERR_ALIGN, "x/packed/out need 16-byte alignment");
-    a.x = static_cast<const uint16_t *>(x); a.wp = static_cast<const uint16_t *>(packed); a.bias1 = b1; a.bias2 = b2; a.out = static_cast<uint16_t *>(out);
-    const hipError_t e = v2v::launch_resblock16(a, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "narrow_two_conv_kernel<1> (residual block) launch");
-}
-
-int v2v_conv_head16_pack_weights_hip(const float *weight, int64_t Cin, void *packed, void *stream)
-{
-    if (!weight || !packed) return fail(V2V_ERR_NULL, "v2v_conv_head16_pack_weights_hip: weight/packed is NULL");
-    if (Cin < 1 || Cin > 8) return fail(V2V_ERR_SHAPE, "need 1 <= Cin <= 8 (16 output channels, 3x3)");
-    if (!aligned(weight, 4) || !aligned(packed, 16)) return fail(V2V_ERR_ALIGN, "weight needs 4-byte, packed 16-byte alignment");
-    const hipError_t e = v2v::launch_conv_head16_pack(weight, (int)Cin, static_cast<uint16_t *>(packed), static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "narrow_pack_kernel launch");
-}
-
-int v2v_conv_head16_nhwc_hip(const void *x8, const void *packed, const float *bias, int relu, int64_t B, int64_t H, int64_t W, void *out, void *stream)
-{
-    if (!x8 || !packed || !bias || !out) return fail(V2V_ERR_NULL, "v2v_conv_head16_nhwc_hip: x8/packed/bias/out is NULL");
-    v2v::NarrowArgs a{};
-    if (const int rc = narrow_shape("v2v_conv_head16_nhwc_hip", B, H, W, a)) return rc;
-    if (out == x8) return fail(V2V_ERR_PARAM, "out must not alias x8");
-    if (!aligned(x8, 16) || !aligned(packed, 16) || !aligned(out, 16) || !aligned(bias, 4)) return fail(V2V_ERR_ALIGN, "x8/packed/out need 16-byte alignment");
-    a.x = static_cast<const uint16_t *>(x8); a.wp = static_cast<const uint16_t *>(packed); a.bias1 = bias; a.relu = relu ? 1 : 0; a.out = static_cast<uint16_t *>(out);
-    const hipError_t e = v2v::launch_conv_head16(a, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "narrow_head_kernel launch");
-}
-
-int64_t v2v_conv_packed_elems(int64_t Cin, int64_t Cout, int ks)
-{
-    if ((ks != 3 && ks != 5) || Cout < 1 || Cout > 4096 || v2v::conv_tile_cols((int)Cout) == 0) return -1;
-    if (Cin == 32) return (Cout == 64 || Cout == 128) ? Cout * ((ks * ks + 1) / 2) * 64 : -1;      // two taps per 64-wide chunk
-    if (Cin < 64 || Cin % 64 != 0 || Cin > 4096) return -1;
-    return Cout * Cin * ks * ks;
-}
-
-int v2v_conv_pack_weights_hip(const float *weight, int64_t Cin, int64_t Cout, int ks, void *packed, void *stream)
-{
-    if (!weight || !packed) return fail(V2V_ERR_NULL, "v2v_conv_pack_weights_hip: weight/packed is NULL");
-    if (v2v_conv_packed_elems(Cin, Cout, ks) < 0)
-        return fail(V2V_ERR_SHAPE, "conv kernel needs Cin %% 64 == 0 (or Cin 32 with Cout 64 / 128), Cout in {32, 64, 128} or a multiple of 256, ks 3 or 5 (got %lld -> %lld, ks %d)",
-                    (long long)Cin, (long long)Cout, ks);
-    if (!aligned(weight, 4) || !aligned(packed, 16)) return fail(V2V_ERR_ALIGN, "weight needs 4-byte, packed 16-byte alignment");
-    const hipError_t e = v2v::launch_conv_pack(weight, static_cast<uint16_t *>(packed), (int)Cin, (int)Cout, ks, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv_pack_kernel launch");
-}
-
-int v2v_conv_nhwc_hip(const void *x, const void *packed, const float *bias, const void *residual, int relu, int64_t B, int64_t Hin,
-                      int64_t Win, int64_t Cin, int64_t Cout, int ks, int stride, void *out, int tile_rows, void *stream)
-{
-    if (!x || !packed || !bias || !out) return fail(V2V_ERR_NULL, "v2v_conv_nhwc_hip: x/packed/bias/out is NULL");
-    if ((ks != 3 && ks != 5) || (stride != 1 && stride != 2)) return fail(V2V_ERR_PARAM, "ks must be 3 or 5, stride 1 or 2");
-    if (B < 1 || Hin < 1 || Win < 1 || v2v_conv_packed_elems(Cin, Cout, ks) < 0)
-        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, Cin %% 64 == 0 (or Cin 32 with Cout 64 / 128), Cout in {32, 64, 128} or a multiple of 256");
-    const int64_t H = (Hin - 1) / stride + 1, W = (Win - 1) / stride + 1;          // output size for pad = ks / 2
-    if (tile_rows != 0 && tile_rows != 128 && tile_rows != 256 && tile_rows != 16 && (Cout % 256 != 0 || (tile_rows != 32 && tile_rows != 64)))
-        return fail(V2V_ERR_PARAM, "tile_rows must be 0 (auto), 128 or 256 (and 32 or 64 for Cout %% 256 == 0)");
-    const bool halo_fits = Cin % 64 == 0 && Cout % 256 != 0 && stride == 1 && H % 16 == 0 && W % 16 == 0 && (ks == 3 || Cout <= 64);   // see launch_conv_nhwc
-    const bool halo = halo_fits && (tile_rows == 16 || (tile_rows == 0 && ks == 5));
-    if (tile_rows == 16 && !halo) return fail(V2V_ERR_PARAM, "tile_rows 16 (halo tiles) needs stride 1, H and W multiples of 16 and Cout 32 / 64 (128 for 3x3)");
-    if ((H * W) % 4 != 0 || B * Hin * Win * Cin > 0x7FFFFFFFLL || B * H * W * Cout > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "conv kernel needs (Hout*Wout) %% 4 == 0 and tensors below 2^31 elements");
-    if (out == x) return fail(V2V_ERR_PARAM, "out must not alias x (neighbouring tiles read it)");
-    if (!aligned(x, 16) || !aligned(packed, 16) || !aligned(out, 2) || !aligned(residual, 2) || !aligned(bias, 4))
-        return fail(V2V_ERR_ALIGN, "x/packed need 16-byte alignment");
-    v2v::ConvLstmArgs a{};
-    a.x = static_cast<const uint16_t *>(x); a.wp = static_cast<const uint16_t *>(packed); a.bias = bias;
-    a.residual = static_cast<const uint16_t *>(residual); a.out_nhwc = static_cast<uint16_t *>(out);
-    a.n_cols = (int)Cout; a.relu = relu ? 1 : 0; a.ks = ks; a.stride = stride; a.Hin = (int)Hin; a.Win = (int)Win;
-    a.B = (int)B; a.H = (int)H; a.W = (int)W; a.C = (int)Cin;
-    const hipError_t e = v2v::launch_conv_nhwc(a, tile_rows, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv (convlstm_step_kernel, EPI = 1) launch");
-}
-
-int64_t v2v_conv_head_packed_elems(int ks) { return (ks == 3 || ks == 5) ? (int64_t)((ks * ks + 7) / 8) * 32 * 64 : -1; }
-
-int v2v_conv_head_pack_weights_hip(const float *weight, int64_t Cin, int ks, void *packed, void *stream)
-{
-    if (!weight || !packed) return fail(V2V_ERR_NULL, "v2v_conv_head_pack_weights_hip: weight/packed is NULL");
-    if (Cin < 1 || Cin > 8 || (ks != 3 && ks != 5)) return fail(V2V_ERR_SHAPE, "need 1 <= Cin <= 8 and ks 3 or 5 (32 output channels)");
-    if (!aligned(packed, 16)) return fail(V2V_ERR_ALIGN, "packed needs 16-byte alignment");
-    const hipError_t e = v2v::launch_conv_head_pack(weight, static_cast<uint16_t *>(packed), (int)Cin, ks, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv_head_pack_kernel launch");
-}
-
-int v2v_to_nhwc8_bf16_hip(const float *src, int64_t stride_b, int64_t stride_c, int64_t stride_h, int64_t stride_w, int64_t B, int64_t C,
-                          int64_t H, int64_t W, void *dst, void *stream)
-{
-    return v2v_to_nhwc8_bf16_scaled_hip(src, stride_b, stride_c, stride_h, stride_w, B, C, H, W, nullptr, dst, stream);
-}
-
-int v2v_to_nhwc8_bf16_scaled_hip(const float *src, int64_t stride_b, int64_t stride_c, int64_t stride_h, int64_t stride_w, int64_t B, int64_t C,
-                                 int64_t H, int64_t W, const float *scales, void *dst, void *stream)
-{
-    if (!src || !dst) return fail(V2V_ERR_NULL, "v2v_to_nhwc8_bf16_hip: src/dst is NULL");
-    if (B < 1 || C < 1 || C > 8 || H < 1 || W < 1 || B * H * W > 0x7FFFFFFFLL) return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, 1 <= C <= 8, B*H*W < 2^31");
-    if (!aligned(dst, 16) || !aligned(src, 4) || (scales && !aligned(scales, 4))) return fail(V2V_ERR_ALIGN, "dst needs 16-byte alignment");
-    const hipError_t e = v2v::launch_to_nhwc8_bf16(src, stride_b, stride_c, stride_h, stride_w, static_cast<uint16_t *>(dst), (int)B, (int)C, (int)H, (int)W,
-                                                   scales, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "to_nhwc8_bf16_kernel launch");
-}
-
-int v2v_conv_head_nhwc_hip(const void *x8, const void *packed, const float *bias, int relu, int64_t B, int64_t H, int64_t W, int ks, void *out, void *stream)
-{
-    if (!x8 || !packed || !bias || !out) return fail(V2V_ERR_NULL, "v2v_conv_head_nhwc_hip: x8/packed/bias/out is NULL");
-    if (ks != 3 && ks != 5) return fail(V2V_ERR_PARAM, "ks must be 3 or 5");
-    if (B < 1 || H < 16 || W < 16 || H % 16 != 0 || W % 16 != 0 || B * H * W * 32 > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "need B >= 1, H and W multiples of 16, output below 2^31 elements");
-    if (!aligned(x8, 16) || !aligned(packed, 16) || !aligned(out, 2) || !aligned(bias, 4)) return fail(V2V_ERR_ALIGN, "x8/packed need 16-byte alignment");
-    const hipError_t e = v2v::launch_conv_head(static_cast<const uint16_t *>(x8), static_cast<const uint16_t *>(packed), bias, static_cast<uint16_t *>(out),
-                                               (int)B, (int)H, (int)W, ks, relu ? 1 : 0, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv_head_kernel launch");
-}
-
-int v2v_conv1x1_nhwc_hip(const void *x, const void *skip, const float *weight, const float *bias, int64_t M, int64_t C, int64_t Cout,
-                         void *out, int out_dtype, void *stream)
-{
-    if (!x || !weight || !bias || !out) return fail(V2V_ERR_NULL, "v2v_conv1x1_nhwc_hip: x/weight/bias/out is NULL");
-    if (out_dtype != V2V_F32 && out_dtype != V2V_BF16) return fail(V2V_ERR_DTYPE, "out_dtype must be V2V_F32 or V2V_BF16");
-    if (M < 1 || C < 8 || C > 512 || (C & (C - 1)) != 0 || Cout < 1 || Cout > 3 || M * (C / 8) > 0x7FFFFFFFLL * 256)
-        return fail(V2V_ERR_SHAPE, "need M >= 1, C a power of two in 8..512, Cout 1..3");
-    if (!aligned(x, 16) || !aligned(skip, 16) || !aligned(out, out_dtype == V2V_F32 ? 4 : 2)) return fail(V2V_ERR_ALIGN, "x/skip need 16-byte alignment");
-    const hipError_t e = v2v::launch_conv1x1_nhwc(static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(skip), weight, bias, out,
-                                                  out_dtype == V2V_BF16, M, (int)C, (int)Cout, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv1x1_nhwc_kernel launch");
-}
-
-int v2v_upsample2x_nhwc_hip(const void *x, const void *skip, int64_t B, int64_t H, int64_t W, int64_t C, void *out, void *stream)
-{
-    if (!x || !out) return fail(V2V_ERR_NULL, "v2v_upsample2x_nhwc_hip: x/out is NULL");
-    if (B < 1 || H < 1 || W < 1 || C < 8 || C % 8 != 0 || B * H * W * C > (1LL << 36))
-        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C %% 8 == 0 and an input below 2^36 elements");
-    if (!aligned(x, 16) || !aligned(out, 16) || !aligned(skip, 16)) return fail(V2V_ERR_ALIGN, "x/skip/out need 16-byte alignment");
-    if (out == x || out == skip) return fail(V2V_ERR_PARAM, "out must not alias x or skip");
-    const hipError_t e = v2v::launch_upsample2x_nhwc(static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(skip), static_cast<uint16_t *>(out),
-                                                     (int)B, (int)H, (int)W, (int)C, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "upsample2x_nhwc_bf16_kernel launch");
-}
-
-int v2v_conv3x3_pack_weights_hip(const float *weight, int64_t Cin, int64_t Cout, void *packed, void *stream)
-{
-    return v2v_conv_pack_weights_hip(weight, Cin, Cout, 3, packed, stream);
-}
-
-int v2v_conv3x3_nhwc_hip(const void *x, const void *packed, const float *bias, const void *residual, int relu, int64_t B, int64_t H,
-                         int64_t W, int64_t Cin, int64_t Cout, void *out, int tile_rows, void *stream)
-{
-    return v2v_conv_nhwc_hip(x, packed, bias, residual, relu, B, H, W, Cin, Cout, 3, 1, out, tile_rows, stream);
-}
-
-int v2v_nchw_to_nhwc_bf16_hip(const void *src, int src_dtype, int64_t B, int64_t C, int64_t H, int64_t W, int relu, void *dst, void *stream)
-{
-    if (!src || !dst) return fail(V2V_ERR_NULL, "v2v_nchw_to_nhwc_bf16_hip: src/dst is NULL");
-    if (src_dtype != V2V_F32 && src_dtype != V2V_BF16) return fail(V2V_ERR_DTYPE, "src_dtype must be V2V_F32 or V2V_BF16");
-    if (B < 1 || H < 1 || W < 1 || C < 64 || C % 64 != 0 || (H * W) % 64 != 0 || B * (C / 64) * (H * W / 64) > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C %% 64 == 0, (H*W) %% 64 == 0");
-    if (!aligned(src, src_dtype == V2V_F32 ? 4 : 2) || !aligned(dst, 2)) return fail(V2V_ERR_ALIGN, "buffers misaligned");
-    const hipError_t e = v2v::launch_nchw_to_nhwc_bf16(src, src_dtype == V2V_BF16, static_cast<uint16_t *>(dst), (int)B, (int)C, (int)(H * W),
-                                                       relu ? 1 : 0, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "nchw_to_nhwc_bf16_kernel launch");
-}
-
-
-// ---- backward passes (training; kernels in v2v_train_tu.hip and the EPI = 2 step) ------------------------------------------------
-int v2v_convlstm_step_bwd_hip(const void *x, const void *h_prev, const float *c_prev, const void *packed, const float *bias, const float *dh,
-                              const float *dc, int64_t B, int64_t H, int64_t W, int64_t C, void *dgates, float *dc_prev, void *stream)
-{
-    if (!x || !packed || !bias || !dh || !dgates || !dc_prev) return fail(V2V_ERR_NULL, "v2v_convlstm_step_bwd_hip: x/packed/bias/dh/dgates/dc_prev is NULL");
-    if (B < 1 || H < 1 || W < 1 || C < 64 || C % 64 != 0 || C > 4096 || (H * W) % 4 != 0 || B * H * W * 4 * C > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C %% 64 == 0, C <= 4096, (H*W) %% 4 == 0, tensors below 2^31 elements");
-    if (dgates == x || dgates == h_prev) return fail(V2V_ERR_PARAM, "dgates must not alias x or h_prev (neighbouring tiles read them)");
-    if (!aligned(x, 16) || !aligned(h_prev, 16) || !aligned(packed, 16) || !aligned(c_prev, 4) || !aligned(dh, 4) || !aligned(dc, 4)
-        || !aligned(dgates, 2) || !aligned(dc_prev, 4) || !aligned(bias, 4))
-        return fail(V2V_ERR_ALIGN, "x/h_prev/packed need 16-byte alignment, c_prev/dh/dc/dc_prev/bias 4-byte, dgates 2-byte");
-    v2v::ConvLstmArgs a{};
-    a.x = static_cast<const uint16_t *>(x); a.h_prev = static_cast<const uint16_t *>(h_prev); a.c_prev = c_prev;
-    a.wp = static_cast<const uint16_t *>(packed); a.bias = bias;
-    a.B = (int)B; a.H = (int)H; a.W = (int)W; a.C = (int)C;
-    a.dh = dh; a.dc = dc; a.dgates = static_cast<uint16_t *>(dgates); a.dc_prev = dc_prev;
-    const hipError_t e = v2v::launch_convlstm_step_bwd(a, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "convlstm_step_kernel (EPI = 2) launch");
-}
-
-int v2v_relu_bwd_nhwc_hip(const void *dy, const void *y, int64_t M, int64_t C, void *out, void *stream)
-{
-    if (!dy || !out) return fail(V2V_ERR_NULL, "v2v_relu_bwd_nhwc_hip: dy/out is NULL");
-    if (M < 1 || C < 8 || C % 8 != 0 || M * C > 0x7FFFFFFFLL) return fail(V2V_ERR_SHAPE, "need M >= 1, C %% 8 == 0, M*C below 2^31");
-    if (!aligned(dy, 16) || !aligned(y, 16) || !aligned(out, 16)) return fail(V2V_ERR_ALIGN, "dy/y/out need 16-byte alignment");
-    const hipError_t e = v2v::launch_relu_mask_stuff(static_cast<const uint16_t *>(dy), static_cast<const uint16_t *>(y), static_cast<uint16_t *>(out),
-                                                     1, 1, (int)M, (int)C, 1, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "relu_mask_stuff_kernel launch");
-}
-
-int64_t v2v_conv_dgrad_packed_elems(int64_t Cin, int64_t Cout, int ks) { return v2v_conv_packed_elems(Cout, Cin, ks); }
-
-int v2v_conv_dgrad_pack_weights_hip(const float *weight, int64_t Cin, int64_t Cout, int ks, float *scratch, void *packed, void *stream)
-{
-    if (!weight || !scratch || !packed) return fail(V2V_ERR_NULL, "v2v_conv_dgrad_pack_weights_hip: weight/scratch/packed is NULL");
-    if ((ks != 3 && ks != 5) || v2v_conv_dgrad_packed_elems(Cin, Cout, ks) < 0)
-        return fail(V2V_ERR_SHAPE, "the transposed convolution (Cout -> Cin, ks 3 or 5) is not a shape the convolution kernel takes");
-    if (!aligned(packed, 16) || !aligned(scratch, 4)) return fail(V2V_ERR_ALIGN, "packed needs 16-byte alignment");
-    hipError_t e = v2v::launch_dgrad_flip(weight, scratch, (int)Cout, (int)Cin, ks, static_cast<hipStream_t>(stream));
-    if (e == hipSuccess) e = v2v::launch_conv_pack(scratch, static_cast<uint16_t *>(packed), (int)Cout, (int)Cin, ks, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "dgrad weight packing launch");
-}
-
-int64_t v2v_conv_dgrad_workspace_bytes(int64_t B, int64_t Hin, int64_t Win, int64_t Cin, int64_t Cout, int stride)
-{
-    if (B < 1 || Hin < 1 || Win < 1 || Cin < 1 || Cout < 1 || (stride != 1 && stride != 2)) return -1;
-    return (Cin * 4 + 255) / 256 * 256 + (stride == 2 ? B * Hin * Win * Cout * 2 : 0);
-}
-
-int v2v_conv_dgrad_nhwc_hip(const void *dy, const void *packed, const void *residual, int64_t B, int64_t Hin, int64_t Win, int64_t Cin, int64_t Cout,
-                            int ks, int stride, void *workspace, void *dx, void *stream)
-{
-    if (!dy || !packed || !workspace || !dx) return fail(V2V_ERR_NULL, "v2v_conv_dgrad_nhwc_hip: dy/packed/workspace/dx is NULL");
-    if ((ks != 3 && ks != 5) || (stride != 1 && stride != 2)) return fail(V2V_ERR_PARAM, "ks must be 3 or 5, stride 1 or 2");
-    if (B < 1 || Hin < 1 || Win < 1 || v2v_conv_dgrad_packed_elems(Cin, Cout, ks) < 0 || Hin % stride != 0 || Win % stride != 0 || (Hin * Win) % 4 != 0
-        || B * Hin * Win * (Cin > Cout ? Cin : Cout) > 0x7FFFFFFFLL || Cout % 8 != 0)
-        return fail(V2V_ERR_SHAPE, "need the transposed convolution Cout -> Cin to be a shape the convolution kernel takes, Hin, Win multiples "
-                                   "of the stride, (Hin*Win) %% 4 == 0, tensors below 2^31 elements");
-    if (dx == dy) return fail(V2V_ERR_PARAM, "dx must not alias dy");
-    if (!aligned(dy, 16) || !aligned(packed, 16) || !aligned(workspace, 256) || !aligned(dx, 2) || !aligned(residual, 2))
-        return fail(V2V_ERR_ALIGN, "dy/packed need 16-byte, workspace 256-byte alignment");
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    float *zero_bias = static_cast<float *>(workspace);
-    hipError_t e = hipMemsetAsync(zero_bias, 0, Cin * 4, s);
-    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(zero bias)");
-    const uint16_t *src = static_cast<const uint16_t *>(dy);
-    if (stride == 2) {
-        uint16_t *grid = reinterpret_cast<uint16_t *>(static_cast<unsigned char *>(workspace) + (Cin * 4 + 255) / 256 * 256);
-        e = v2v::launch_relu_mask_stuff(src, nullptr, grid, (int)B, (int)(Hin / 2), (int)(Win / 2), (int)Cout, 2, s);
-        if (e != hipSuccess) return hip_fail(e, "relu_mask_stuff_kernel launch");
-        src = grid;
-    }
-    v2v::ConvLstmArgs a{};
-    a.x = src; a.wp = static_cast<const uint16_t *>(packed); a.bias = zero_bias;
-    a.residual = static_cast<const uint16_t *>(residual); a.out_nhwc = static_cast<uint16_t *>(dx);
-    a.n_cols = (int)Cin; a.relu = 0; a.ks = ks; a.stride = 1; a.Hin = (int)Hin; a.Win = (int)Win;
-    a.B = (int)B; a.H = (int)Hin; a.W = (int)Win; a.C = (int)Cout;
-    e = v2v::launch_conv_nhwc(a, 0, s);
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "dgrad (convlstm_step_kernel, EPI = 1) launch");
-}
-
-int64_t v2v_conv_wgrad_workspace_bytes(int64_t B, int64_t Ho, int64_t Wo, int64_t Cin, int64_t Cout, int ks)
-{
-    if (B < 1 || Ho < 1 || Wo < 1 || Cin < 1 || Cout < 32 || Cout % 32 != 0 || (ks != 1 && ks != 3 && ks != 5)) return -1;
-    const int64_t N = (int64_t)ks * ks * Cin, Npad = (N + 127) / 128 * 128;
-    const int64_t S = v2v::wgrad_slabs(B * Ho * Wo, (int)Cout, N);
-    return S * Cout * (Npad + 1) * 4;
-}
-
-int v2v_conv_wgrad_nhwc_hip(const void *dy, const void *x1, int64_t C1, const void *x2, int64_t C2, int64_t Cin_out, int64_t B, int64_t Hin, int64_t Win,
-                            int64_t Cout, int ks, int stride, void *workspace, float *dw, float *db, void *stream)
-{
-    if (!dy || !x1 || !workspace || !dw) return fail(V2V_ERR_NULL, "v2v_conv_wgrad_nhwc_hip: dy/x1/workspace/dw is NULL");
-    if ((ks != 1 && ks != 3 && ks != 5) || (stride != 1 && stride != 2)) return fail(V2V_ERR_PARAM, "ks must be 1, 3 or 5, stride 1 or 2");
-    const int64_t Ho = (Hin - 1) / stride + 1, Wo = (Win - 1) / stride + 1;
-    if (B < 1 || Hin < 1 || Win < 1 || C1 < 1 || C2 < 0 || Cin_out < 1 || Cin_out > C1 + C2 || Cout < 32 || Cout % 32 != 0
-        || B * Hin * Win * (C1 > C2 ? C1 : C2) > 0x7FFFFFFFLL || B * Ho * Wo * Cout > 0x7FFFFFFFLL || (int64_t)ks * ks * (C1 + C2) > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C1 >= 1, 1 <= Cin_out <= C1 + C2, Cout a multiple of 32, tensors below 2^31 elements");
-    if (!aligned(dy, 2) || !aligned(x1, 2) || !aligned(x2, 2) || !aligned(workspace, 4) || !aligned(dw, 4) || !aligned(db, 4))
-        return fail(V2V_ERR_ALIGN, "buffers misaligned");
-    const hipError_t e = v2v::launch_conv_wgrad(static_cast<const uint16_t *>(dy), static_cast<const uint16_t *>(x1), (int)C1,
-                                                static_cast<const uint16_t *>(x2), (int)C2, (int)Cin_out, dw, db, static_cast<float *>(workspace),
-                                                (int)B, (int)Hin, (int)Win, (int)Ho, (int)Wo, (int)Cout, ks, stride, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv_wgrad_kernel launch");
-}
-
-int v2v_upsample2x_bwd_nhwc_hip(const void *dout, int64_t B, int64_t H, int64_t W, int64_t C, void *dx, void *stream)
-{
-    if (!dout || !dx) return fail(V2V_ERR_NULL, "v2v_upsample2x_bwd_nhwc_hip: dout/dx is NULL");
-    if (B < 1 || H < 1 || W < 1 || C < 8 || C % 8 != 0 || B * 4 * H * W * C > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C %% 8 == 0, tensors below 2^31 elements");
-    if (!aligned(dout, 16) || !aligned(dx, 16)) return fail(V2V_ERR_ALIGN, "dout/dx need 16-byte alignment");
-    const hipError_t e = v2v::launch_upsample2x_cat_bwd(static_cast<const uint16_t *>(dout), static_cast<uint16_t *>(dx), (int)B, (int)H, (int)W, (int)C,
-                                                        0, (int)C, static_cast<hipStream_t>(stream));    // the whole tensor as one slice
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "upsample2x_cat_bwd_kernel launch");
-}
-
-int64_t v2v_conv1x1_bwd_workspace_bytes(int64_t M, int64_t C)
-{
-    if (M < 1 || C < 8 || C > 128 || (C & (C - 1)) != 0) return -1;
-    return v2v::conv1x1_bwd_slabs(M) * (C + 1) * 4;
-}
-
-int v2v_conv1x1_bwd_nhwc_hip(const float *dy, const void *x, const void *skip, const float *weight, int64_t M, int64_t C, void *dx, float *dw, float *db,
-                             void *workspace, void *stream)
-{
-    if (!dy || !x || !weight || !dx || !dw || !db || !workspace) return fail(V2V_ERR_NULL, "v2v_conv1x1_bwd_nhwc_hip: a required pointer is NULL");
-    if (M < 1 || C < 8 || C > 128 || (C & (C - 1)) != 0 || M * C > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "need M >= 1 and C a power of two in 8..128 (one output channel)");
-    if (!aligned(dy, 4) || !aligned(x, 16) || !aligned(skip, 16) || !aligned(dx, 16) || !aligned(weight, 4) || !aligned(workspace, 4))
-        return fail(V2V_ERR_ALIGN, "x/skip/dx need 16-byte alignment, dy/weight/workspace 4-byte");
-    const hipError_t e = v2v::launch_conv1x1_bwd_cout(dy, static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(skip), weight,
-                                                      static_cast<uint16_t *>(dx), dw, db, static_cast<float *>(workspace), M, (int)C, 1,
-                                                      static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv1x1_bwd_cout_kernel launch");
-}
-
-// ---- the plain UNet (EVFlowNet): stem, concat-skip upsampling and its adjoint, the prediction backward for 1..3 outputs ----------------
-int64_t v2v_conv_stem_packed_elems(void) { return 2 * 64 * 64; }
-
-int v2v_conv_stem_pack_weights_hip(const float *weight, int64_t Cin, void *packed, void *stream)
-{
-    if (!weight || !packed) return fail(V2V_ERR_NULL, "v2v_conv_stem_pack_weights_hip: weight/packed is NULL");
-    if (Cin < 1 || Cin > 8) return fail(V2V_ERR_SHAPE, "need 1 <= Cin <= 8 (64 output channels, 3x3)");
-    if (!aligned(weight, 4) || !aligned(packed, 16)) return fail(V2V_ERR_ALIGN, "weight needs 4-byte, packed 16-byte alignment");
-    const hipError_t e = v2v::launch_conv_stem_pack(weight, static_cast<uint16_t *>(packed), (int)Cin, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv_stem_pack_kernel launch");
-}
-
-int v2v_conv_stem_nhwc_hip(const void *x8, const void *packed, const float *bias, int relu, int64_t B, int64_t H, int64_t W, void *out, void *stream)
-{
-    if (!x8 || !packed || !bias || !out) return fail(V2V_ERR_NULL, "v2v_conv_stem_nhwc_hip: x8/packed/bias/out is NULL");
-    if (B < 1 || H < 16 || W < 16 || H % 16 != 0 || W % 16 != 0 || B * H * W * 16 > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "need B >= 1, H and W multiples of 16, output below 2^31 elements");
-    if (!aligned(x8, 16) || !aligned(packed, 16) || !aligned(out, 2) || !aligned(bias, 4)) return fail(V2V_ERR_ALIGN, "x8/packed need 16-byte alignment");
-    if (out == x8) return fail(V2V_ERR_PARAM, "out must not alias x8");
-    const hipError_t e = v2v::launch_conv_stem(static_cast<const uint16_t *>(x8), static_cast<const uint16_t *>(packed), bias, static_cast<uint16_t *>(out),
-                                               (int)B, (int)H, (int)W, relu ? 1 : 0, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv_stem_kernel launch");
-}
-
-int v2v_upsample2x_cat_nhwc_hip(const void *x, int64_t C1, const void *skip, int64_t C2, int64_t B, int64_t H, int64_t W, void *out, void *stream)
-{
-    if (!x || !out || (C2 > 0 && !skip)) return fail(V2V_ERR_NULL, "v2v_upsample2x_cat_nhwc_hip: x/out (or skip with C2 > 0) is NULL");
-    if (B < 1 || H < 1 || W < 1 || C1 < 8 || C1 % 8 != 0 || C2 < 0 || C2 % 8 != 0 || B * 4 * H * W * (C1 + C2) > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C1 %% 8 == 0, C2 %% 8 == 0 and an output below 2^31 elements");
-    if (skip && C2 == 0) return fail(V2V_ERR_PARAM, "skip given with C2 == 0");
-    if (!aligned(x, 16) || !aligned(out, 16) || !aligned(skip, 16)) return fail(V2V_ERR_ALIGN, "x/skip/out need 16-byte alignment");
-    if (out == x || out == skip) return fail(V2V_ERR_PARAM, "out must not alias x or skip");
-    const hipError_t e = v2v::launch_upsample2x_cat_nhwc(static_cast<const uint16_t *>(x), (int)C1, static_cast<const uint16_t *>(skip), (int)C2,
-                                                         static_cast<uint16_t *>(out), (int)B, (int)H, (int)W, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "upsample2x_cat_nhwc_bf16_kernel launch");
-}
-
-int v2v_upsample2x_cat_bwd_nhwc_hip(const void *dout, int64_t B, int64_t H, int64_t W, int64_t Ctot, int64_t c0, int64_t C, void *dx, void *stream)
-{
-    if (!dout || !dx) return fail(V2V_ERR_NULL, "v2v_upsample2x_cat_bwd_nhwc_hip: dout/dx is NULL");
-    if (B < 1 || H < 1 || W < 1 || C < 8 || C % 8 != 0 || Ctot % 8 != 0 || c0 < 0 || c0 % 8 != 0 || c0 + C > Ctot || B * 4 * H * W * Ctot > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C, c0 and Ctot multiples of 8, c0 + C <= Ctot, tensors below 2^31 elements");
-    if (!aligned(dout, 16) || !aligned(dx, 16)) return fail(V2V_ERR_ALIGN, "dout/dx need 16-byte alignment");
-    if (dx == dout) return fail(V2V_ERR_PARAM, "dx must not alias dout");
-    const hipError_t e = v2v::launch_upsample2x_cat_bwd(static_cast<const uint16_t *>(dout), static_cast<uint16_t *>(dx), (int)B, (int)H, (int)W, (int)Ctot,
-                                                        (int)c0, (int)C, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "upsample2x_cat_bwd_kernel launch");
-}
-
-int64_t v2v_conv1x1_bwd_cout_workspace_bytes(int64_t M, int64_t C, int64_t Cout)
-{
-    if (M < 1 || C < 8 || C > 128 || (C & (C - 1)) != 0 || Cout < 1 || Cout > 3) return -1;
-    return v2v::conv1x1_bwd_slabs(M) * Cout * (C + 1) * 4;
-}
-
-int v2v_conv1x1_bwd_cout_nhwc_hip(const float *dy, const void *x, const void *skip, const float *weight, int64_t M, int64_t C, int64_t Cout, void *dx,
-                                  float *dw, float *db, void *workspace, void *stream)
-{
-    if (!dy || !x || !weight || !dx || !dw || !db || !workspace) return fail(V2V_ERR_NULL, "v2v_conv1x1_bwd_cout_nhwc_hip: a required pointer is NULL");
-    if (M < 1 || C < 8 || C > 128 || (C & (C - 1)) != 0 || Cout < 1 || Cout > 3 || M * C > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "need M >= 1, C a power of two in 8..128, Cout 1..3");
-    if (!aligned(dy, 4) || !aligned(x, 16) || !aligned(skip, 16) || !aligned(dx, 16) || !aligned(weight, 4) || !aligned(workspace, 4) || !aligned(dw, 4)
-        || !aligned(db, 4))
-        return fail(V2V_ERR_ALIGN, "x/skip/dx need 16-byte alignment, dy/weight/dw/db/workspace 4-byte");
-    const hipError_t e = v2v::launch_conv1x1_bwd_cout(dy, static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(skip), weight,
-                                                      static_cast<uint16_t *>(dx), dw, db, static_cast<float *>(workspace), M, (int)C, (int)Cout,
-                                                      static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv1x1_bwd_cout_kernel launch");
-}
-
-int v2v_conv_nhwc_like_hip(const void *x, const void *packed, const float *bias, const void *residual, int relu, int64_t B, int64_t Hin, int64_t Win,
-                           int64_t Cin, int64_t Cout, int ks, int stride, void *out, int64_t B_like, void *stream)
-{
-    if (!x || !packed || !bias || !out) return fail(V2V_ERR_NULL, "v2v_conv_nhwc_like_hip: x/packed/bias/out is NULL");
-    if ((ks != 3 && ks != 5) || (stride != 1 && stride != 2) || B_like < 0) return fail(V2V_ERR_PARAM, "ks must be 3 or 5, stride 1 or 2, B_like >= 0");
-    if (B < 1 || Hin < 1 || Win < 1 || v2v_conv_packed_elems(Cin, Cout, ks) < 0)
-        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, Cin %% 64 == 0 (or Cin 32 with Cout 64 / 128), Cout in {32, 64, 128} or a multiple of 256");
-    const int64_t H = (Hin - 1) / stride + 1, W = (Win - 1) / stride + 1;
-    if ((H * W) % 4 != 0 || B * Hin * Win * Cin > 0x7FFFFFFFLL || B * H * W * Cout > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "conv kernel needs (Hout*Wout) %% 4 == 0 and tensors below 2^31 elements");
-    if (out == x) return fail(V2V_ERR_PARAM, "out must not alias x (neighbouring tiles read it)");
-    if (!aligned(x, 16) || !aligned(packed, 16) || !aligned(out, 2) || !aligned(residual, 2) || !aligned(bias, 4))
-        return fail(V2V_ERR_ALIGN, "x/packed need 16-byte alignment");
-    v2v::ConvLstmArgs a{};
-    a.x = static_cast<const uint16_t *>(x); a.wp = static_cast<const uint16_t *>(packed); a.bias = bias;
-    a.residual = static_cast<const uint16_t *>(residual); a.out_nhwc = static_cast<uint16_t *>(out);
-    a.n_cols = (int)Cout; a.relu = relu ? 1 : 0; a.ks = ks; a.stride = stride; a.Hin = (int)Hin; a.Win = (int)Win;
-    a.B = (int)B; a.H = (int)H; a.W = (int)W; a.C = (int)Cin;
-    const hipError_t e = v2v::launch_conv_nhwc(a, 0, static_cast<hipStream_t>(stream), B_like);
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv (convlstm_step_kernel, EPI = 1) launch");
-}
-
-
-int v2v_hyper_context_hip(const float *events, int64_t stride_b, int64_t stride_c, int64_t stride_h, int64_t stride_w, const float *prev, int64_t B,
-                          int64_t C, int64_t H, int64_t W, void *dst, void *stream)
-{
-    if (!events || !prev || !dst) return fail(V2V_ERR_NULL, "v2v_hyper_context_hip: events/prev/dst is NULL");
-    if (B < 1 || C < 1 || C > 7 || H < 4 || W < 4 || H % 4 != 0 || W % 4 != 0 || B * H * W > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "need B >= 1, 1 <= C <= 7, H and W multiples of 4, B*H*W < 2^31");
-    if (!aligned(dst, 16) || !aligned(events, 4) || !aligned(prev, 4)) return fail(V2V_ERR_ALIGN, "dst needs 16-byte alignment");
-    const hipError_t e = v2v::launch_hyper_context(events, stride_b, stride_c, stride_h, stride_w, prev, static_cast<uint16_t *>(dst), (int)B, (int)C, (int)H,
-                                                   (int)W, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "hyper_context_kernel launch");
-}
-
-int v2v_hyper_context_conv_hip(const void *x8, const float *weight, const float *bias, int64_t B, int64_t h, int64_t w, int64_t Cin, void *out, void *stream)
-{
-    if (!x8 || !weight || !bias || !out) return fail(V2V_ERR_NULL, "v2v_hyper_context_conv_hip: x8/weight/bias/out is NULL");
-    if (B < 1 || h < 1 || w < 1 || Cin < 1 || Cin > 8 || B * h * w * 32 > 0x7FFFFFFFLL) return fail(V2V_ERR_SHAPE, "need B,h,w >= 1, 1 <= Cin <= 8, output below 2^31 elements");
-    if (out == x8) return fail(V2V_ERR_PARAM, "out must not alias x8 (neighbouring pixels read it)");
-    if (!aligned(x8, 16) || !aligned(out, 16) || !aligned(weight, 4) || !aligned(bias, 4)) return fail(V2V_ERR_ALIGN, "x8/out need 16-byte alignment");
-    const hipError_t e = v2v::launch_hyper_context_conv(static_cast<const uint16_t *>(x8), weight, bias, static_cast<uint16_t *>(out), (int)B, (int)h, (int)w, (int)Cin,
-                                                        static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "hyper_context_conv_kernel launch");
-}
-
-int v2v_tanh_bf16_hip(const void *x, int64_t n, void *out, void *stream)
-{
-    if (!x || !out) return fail(V2V_ERR_NULL, "v2v_tanh_bf16_hip: x/out is NULL");
-    if (n < 8 || n % 8 != 0 || n > 0x7FFFFFFFLL) return fail(V2V_ERR_SHAPE, "need n a multiple of 8 below 2^31");
-    if (!aligned(x, 16) || !aligned(out, 16)) return fail(V2V_ERR_ALIGN, "x/out need 16-byte alignment");
-    const hipError_t e = v2v::launch_hyper_tanh(static_cast<const uint16_t *>(x), static_cast<uint16_t *>(out), n / 8, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "hyper_tanh_kernel launch");
-}
-
-int v2v_hyper_atoms_hip(const void *coeff, const float *bases, int64_t M, float *atoms, void *stream)
-{
-    if (!coeff || !bases || !atoms) return fail(V2V_ERR_NULL, "v2v_hyper_atoms_hip: coeff/bases/atoms is NULL");
-    if (M < 1 || M * v2v::kHyAtomElems > 0x7FFFFFFFLL) return fail(V2V_ERR_SHAPE, "need M >= 1 and M * 150 < 2^31");
-    if (!aligned(coeff, 2) || !aligned(bases, 4) || !aligned(atoms, 4)) return fail(V2V_ERR_ALIGN, "bases/atoms need 4-byte alignment");
-    const hipError_t e = v2v::launch_hyper_atoms(static_cast<const uint16_t *>(coeff), bases, atoms, M, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "hyper_atoms_kernel launch");
-}
-
-int64_t v2v_hyper_dynconv_packed_elems(int64_t Cin, int64_t Cout, int atoms, int ks)
-{
-    return (Cin == v2v::kHyCin && Cout == v2v::kHyCout && atoms == v2v::kHyAtoms && ks == 5) ? Cin * Cout * atoms : -1;
-}
-
-int v2v_hyper_dynconv_pack_weights_hip(const float *weight, int64_t Cin, int64_t Cout, int atoms, void *packed, void *stream)
-{
-    if (!weight || !packed) return fail(V2V_ERR_NULL, "v2v_hyper_dynconv_pack_weights_hip: weight/packed is NULL");
-    if (v2v_hyper_dynconv_packed_elems(Cin, Cout, atoms, 5) < 0) return fail(V2V_ERR_SHAPE, "the dynamic convolution takes Cin 256, Cout 128, 6 atoms");
-    if (!aligned(weight, 4) || !aligned(packed, 16)) return fail(V2V_ERR_ALIGN, "weight needs 4-byte, packed 16-byte alignment");
-    const hipError_t e = v2v::launch_hyper_dynconv_pack(weight, static_cast<uint16_t *>(packed), static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "hyper_dynconv_pack_kernel launch");
-}
-
-int v2v_hyper_dynconv_nhwc_hip(const void *x, const float *atoms, const void *packed, const float *bias, int relu, int64_t B, int64_t H, int64_t W,
-                               int64_t Cin, int64_t Cout, int n_atoms, int ks, void *out, void *stream)
-{
-    if (!x || !atoms || !packed || !bias || !out) return fail(V2V_ERR_NULL, "v2v_hyper_dynconv_nhwc_hip: x/atoms/packed/bias/out is NULL");
-    if (v2v_hyper_dynconv_packed_elems(Cin, Cout, n_atoms, ks) < 0)
-        return fail(V2V_ERR_SHAPE, "the dynamic convolution takes Cin 256, Cout 128, 6 atoms, a 5 x 5 window (got %lld -> %lld, %d atoms, ks %d)",
-                    (long long)Cin, (long long)Cout, n_atoms, ks);
-    if (B < 1 || H < 1 || W < 1 || B * H * W * Cin > 0x7FFFFFFFLL) return fail(V2V_ERR_SHAPE, "need B,H,W >= 1 and tensors below 2^31 elements");
-    if (out == x) return fail(V2V_ERR_PARAM, "out must not alias x (neighbouring tiles read it)");
-    if (!aligned(x, 16) || !aligned(packed, 16) || !aligned(atoms, 8) || !aligned(out, 2) || !aligned(bias, 4))
-        return fail(V2V_ERR_ALIGN, "x/packed need 16-byte, atoms 8-byte alignment");
-    const hipError_t e = v2v::launch_hyper_dynconv(static_cast<const uint16_t *>(x), atoms, static_cast<const uint16_t *>(packed), bias,
-                                                   static_cast<uint16_t *>(out), (int)B, (int)H, (int)W, relu ? 1 : 0, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "hyper_dynconv_kernel launch");
-}
-
-// ---- the image losses of training (v2v_loss.hpp) ------------------------------------------------------------------------------------------
-namespace {
-
-constexpr int64_t kLossMaxPixels = (int64_t)1 << 22;       // the fixed-point accumulator of the warp adjoint holds h*w contributions of < 2^38
-
-int loss_shape_check(const char *who, int64_t n_img, int64_t c, int64_t h, int64_t w)
-{
-    if (n_img < 0 || c < 1) return fail(V2V_ERR_SHAPE, "%s: need a non-negative image count and c >= 1 (got %lld, %lld)", who, (long long)n_img, (long long)c);
-    if (h < 2 || w < 2) return fail(V2V_ERR_SHAPE, "%s: h and w must be at least 2, the sampling grid divides by h - 1 and w - 1 (got %lld x %lld)", who, (long long)h, (long long)w);
-    if (h * w > kLossMaxPixels) return fail(V2V_ERR_SHAPE, "%s: h*w = %lld is above 2^22, the bound of the adjoint's fixed-point accumulator", who, (long long)(h * w));
-    const int64_t tiles = (h * w + v2v::kLossTile - 1) / v2v::kLossTile;
-    if (c > 65536 || n_img * tiles > 0x7FFFFFFFLL || n_img * c > ((int64_t)1 << 40) / (h * w))
-        return fail(V2V_ERR_SHAPE, "%s: %lld images of %lld x %lld x %lld are more than one launch takes", who, (long long)n_img, (long long)c, (long long)h, (long long)w);
-    return V2V_OK;
-}
-
-int64_t loss_round16(int64_t b) { return (b + 15) / 16 * 16; }
-
-// backward workspace: acc int64 [E] | maxbits u32 [n_img] (these two are zeroed by every call) | dwarp f32 [E] | dp1 f32 [E]
-struct LossWorkspace {
-    unsigned long long *acc;
-    unsigned *maxbits;
-    float *dwarp, *dp1;
-    int64_t zero_bytes, bytes;
-};
-
-LossWorkspace loss_workspace(void *base, int64_t n_img, int64_t c, int64_t h, int64_t w)
-{
-    const int64_t e = n_img * c * h * w;
-    char *p = static_cast<char *>(base);
-    LossWorkspace ws;
-    ws.acc = reinterpret_cast<unsigned long long *>(p);
-    ws.maxbits = reinterpret_cast<unsigned *>(p + loss_round16(8 * e));
-    ws.zero_bytes = loss_round16(8 * e) + loss_round16(4 * n_img);
-    ws.dwarp = reinterpret_cast<float *>(p + ws.zero_bytes);
-    ws.dp1 = reinterpret_cast<float *>(p + ws.zero_bytes + loss_round16(4 * e));
-    ws.bytes = ws.zero_bytes + 2 * loss_round16(4 * e);
-    return ws;
-}
-
-int loss_args(const char *who, v2v::LossArgs &a, const float *image0, const float *image1, const float *processed0, const float *processed1, const float *flow,
-              int64_t outer, int64_t inner, int64_t so, int64_t si, int64_t fso, int64_t fsi, int64_t tc_first, int64_t c, int64_t h, int64_t w, float alpha,
-              float flow_sign, float w_tc, float w_l1, float w_l2)
-{
-    if (!image1 || !processed1) return fail(V2V_ERR_NULL, "%s: image1/processed1 is NULL", who);
-    if (outer < 0 || inner < 0) return fail(V2V_ERR_SHAPE, "%s: outer and inner must not be negative", who);
-    if (const int rc = loss_shape_check(who, outer * inner, c, h, w)) return rc;
-    if (tc_first < 0) return fail(V2V_ERR_PARAM, "%s: tc_first must not be negative", who);
-    if (w_tc != 0.0f && tc_first < inner && (!image0 || !processed0 || !flow)) return fail(V2V_ERR_NULL, "%s: image0/processed0/flow is NULL with a temporal term", who);
-    if (!aligned(image1, 4) || !aligned(processed1, 4) || !aligned(image0, 4) || !aligned(processed0, 4) || !aligned(flow, 4))
-        return fail(V2V_ERR_ALIGN, "%s: float32 pointers need 4-byte alignment", who);
-    a = v2v::LossArgs{image0, image1, processed0, processed1, flow, inner, so, si, fso, fsi, tc_first, outer * inner,
-                      (int)c, (int)h, (int)w, (int)((h * w + v2v::kLossTile - 1) / v2v::kLossTile), alpha, flow_sign, w_tc, w_l1, w_l2};
-    return V2V_OK;
-}
-
-}  // namespace
-
-int64_t v2v_tc_loss_workspace_bytes(int64_t n_img, int64_t c, int64_t h, int64_t w, int backward)
-{
-    if (const int rc = loss_shape_check("v2v_tc_loss_workspace_bytes", n_img, c, h, w)) return rc;
-    if (backward) return loss_workspace(nullptr, n_img, c, h, w).bytes;
-    return loss_round16(n_img * ((h * w + v2v::kLossTile - 1) / v2v::kLossTile) * 3 * 4);
-}
-
-int v2v_tc_loss_fwd_hip(const float *image0, const float *image1, const float *processed0, const float *processed1, const float *flow, int64_t outer,
-                        int64_t inner, int64_t img_stride_outer, int64_t img_stride_inner, int64_t flow_stride_outer, int64_t flow_stride_inner,
-                        int64_t tc_first, int64_t c, int64_t h, int64_t w, float alpha, float flow_sign, float w_tc, float w_l1, float w_l2, float *losses,
-                        float *image0_warped, float *processed0_warped, float *visibility_mask, float *error_map, void *workspace, void *stream)
-{
-    v2v::LossArgs a;
-    if (const int rc = loss_args("v2v_tc_loss_fwd_hip", a, image0, image1, processed0, processed1, flow, outer, inner, img_stride_outer, img_stride_inner,
-                                 flow_stride_outer, flow_stride_inner, tc_first, c, h, w, alpha, flow_sign, w_tc, w_l1, w_l2))
-        return rc;
-    if (!losses || !workspace) return fail(V2V_ERR_NULL, "v2v_tc_loss_fwd_hip: losses/workspace is NULL");
-    if (!aligned(losses, 4) || !aligned(workspace, 16)) return fail(V2V_ERR_ALIGN, "v2v_tc_loss_fwd_hip: losses needs 4-byte, workspace 16-byte alignment");
-    if (a.n_img == 0) return V2V_OK;
-    const hipError_t e = v2v::launch_tc_loss_fwd(a, static_cast<float *>(workspace), losses, image0_warped, processed0_warped, visibility_mask, error_map,
-                                                 static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "tc_loss_fwd_kernel launch");
-}
-
-int v2v_tc_loss_bwd_hip(const float *image0, const float *image1, const float *processed0, const float *processed1, const float *flow, int64_t outer,
-                        int64_t inner, int64_t img_stride_outer, int64_t img_stride_inner, int64_t flow_stride_outer, int64_t flow_stride_inner,
-                        int64_t tc_first, int64_t c, int64_t h, int64_t w, float alpha, float flow_sign, float w_tc, float w_l1, float w_l2, const float *gout,
-                        int chain, float *dprocessed1, float *dprocessed0, void *workspace, void *stream)
-{
-    v2v::LossArgs a;
-    if (const int rc = loss_args("v2v_tc_loss_bwd_hip", a, image0, image1, processed0, processed1, flow, outer, inner, img_stride_outer, img_stride_inner,
-                                 flow_stride_outer, flow_stride_inner, tc_first, c, h, w, alpha, flow_sign, w_tc, w_l1, w_l2))
-        return rc;
-    const bool tc = w_tc != 0.0f && tc_first < inner;
-    if (!gout || !dprocessed1 || !workspace || (tc && !chain && !dprocessed0)) return fail(V2V_ERR_NULL, "v2v_tc_loss_bwd_hip: gout/dprocessed1/dprocessed0/workspace is NULL");
-    if (chain && tc && (tc_first < 1 || processed0 != processed1 + (tc_first - 1) * img_stride_inner))
-        return fail(V2V_ERR_PARAM, "v2v_tc_loss_bwd_hip: chain needs tc_first >= 1 and processed0 = processed1 + (tc_first - 1) * img_stride_inner");
-    if (!aligned(gout, 4) || !aligned(dprocessed1, 4) || !aligned(dprocessed0, 4) || !aligned(workspace, 16))
-        return fail(V2V_ERR_ALIGN, "v2v_tc_loss_bwd_hip: float32 pointers need 4-byte, workspace 16-byte alignment");
-    if (a.n_img == 0) return V2V_OK;
-    const LossWorkspace ws = loss_workspace(workspace, a.n_img, c, h, w);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (tc) {
-        const hipError_t e = hipMemsetAsync(workspace, 0, (size_t)ws.zero_bytes, s);
-        if (e != hipSuccess) return hip_fail(e, "v2v_tc_loss_bwd_hip: clearing the accumulator");
-    }
-    const hipError_t e = v2v::launch_tc_loss_bwd(a, gout, chain ? 1 : 0, dprocessed1, dprocessed0, ws.acc, ws.dwarp, ws.dp1, ws.maxbits, s);
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "tc_loss_bwd_kernel launch");
-}
-
-int v2v_warp_bilinear_hip(const float *img, const float *flow, int64_t n, int64_t c, int64_t h, int64_t w, float *out, void *stream)
-{
-    if (!img || !flow || !out) return fail(V2V_ERR_NULL, "v2v_warp_bilinear_hip: img/flow/out is NULL");
-    if (const int rc = loss_shape_check("v2v_warp_bilinear_hip", n, c, h, w)) return rc;
-    if (!aligned(img, 4) || !aligned(flow, 4) || !aligned(out, 4)) return fail(V2V_ERR_ALIGN, "v2v_warp_bilinear_hip: float32 pointers need 4-byte alignment");
-    if (out == img) return fail(V2V_ERR_PARAM, "v2v_warp_bilinear_hip: out must not alias img");
-    if (n == 0) return V2V_OK;
-    const hipError_t e = v2v::launch_warp_bilinear(img, flow, n, (int)c, (int)h, (int)w, out, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "warp_bilinear_kernel launch");
-}
-
-int v2v_warp_bilinear_adjoint_hip(const float *dout, const float *flow, int64_t n, int64_t c, int64_t h, int64_t w, float *din, void *workspace, void *stream)
-{
-    if (!dout || !flow || !din || !workspace) return fail(V2V_ERR_NULL, "v2v_warp_bilinear_adjoint_hip: dout/flow/din/workspace is NULL");
-    if (const int rc = loss_shape_check("v2v_warp_bilinear_adjoint_hip", n, c, h, w)) return rc;
-    if (!aligned(dout, 4) || !aligned(flow, 4) || !aligned(din, 4) || !aligned(workspace, 16))
-        return fail(V2V_ERR_ALIGN, "v2v_warp_bilinear_adjoint_hip: float32 pointers need 4-byte, workspace 16-byte alignment");
-    if (n == 0) return V2V_OK;
-    const LossWorkspace ws = loss_workspace(workspace, n, c, h, w);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemsetAsync(workspace, 0, (size_t)ws.zero_bytes, s);
-    if (e != hipSuccess) return hip_fail(e, "v2v_warp_bilinear_adjoint_hip: clearing the accumulator");
-    e = v2v::launch_warp_bilinear_adjoint(dout, flow, n, (int)c, (int)h, (int)w, din, ws.acc, ws.maxbits, s);
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "warp_adjoint_kernel launch");
-}
-
-// ---- the LPIPS-VGG perceptual loss (v2v_lpips.hpp) ---------------------------------------------------------------------------------------------
-namespace {
-
-int lpips_image_check(const char *who, int64_t B, int64_t Cin, int64_t H, int64_t W)
-{
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || H > 32768 || W > 32768) return fail(V2V_ERR_SHAPE, "%s: need 1 <= B <= 65535 and 1 <= H, W <= 32768 (got %lld, %lld x %lld)", who, (long long)B, (long long)H, (long long)W);
-    if (Cin != 1 && Cin != 3) return fail(V2V_ERR_SHAPE, "%s: the image has 1 or 3 channels (got %lld)", who, (long long)Cin);
-    if (B * H * W * 64 > 0x7FFFFFFFLL) return fail(V2V_ERR_SHAPE, "%s: [B,H,W,64] must stay below 2^31 elements", who);
-    return V2V_OK;
-}
-
-int lpips_pool_check(const char *who, int64_t B, int64_t H, int64_t W, int64_t C)
-{
-    if (B < 1 || H < 2 || W < 2 || H % 2 != 0 || W % 2 != 0 || C < 8 || C % 8 != 0 || H > 32768 || W > 32768 || C > 4096 || B * H * W * C > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "%s: need B >= 1, H and W even, C a multiple of 8, the tensor below 2^31 elements (got %lld x %lld x %lld x %lld)", who,
-                    (long long)B, (long long)H, (long long)W, (long long)C);
-    return V2V_OK;
-}
-
-int lpips_compare_check(const char *who, int64_t n_img, int64_t HW, int64_t Cc)
-{
-    if (Cc != 64 && Cc != 128 && Cc != 256 && Cc != 512) return fail(V2V_ERR_SHAPE, "%s: Cc must be 64, 128, 256 or 512 (got %lld)", who, (long long)Cc);
-    if (n_img < 1 || n_img > 65535 || HW < 1 || HW > 0x7FFFFFFFLL / 512 || n_img * HW * Cc > 0x7FFFFFFFLL)
-        return fail(V2V_ERR_SHAPE, "%s: need 1 <= n_img <= 65535, HW >= 1 and [n_img,HW,Cc] below 2^31 elements (got %lld, %lld)", who, (long long)n_img, (long long)HW);
-    return V2V_OK;
-}
-
-}  // namespace
-
-int v2v_lpips_stem_hip(const void *x, int x_dtype, int64_t B, int64_t Cin, int64_t H, int64_t W, const float *weight, const float *bias, const float *shift,
-                       const float *scale, int normalize, void *out, void *stream)
-{
-    if (!x || !weight || !bias || !shift || !scale || !out) return fail(V2V_ERR_NULL, "v2v_lpips_stem_hip: x/weight/bias/shift/scale/out is NULL");
-    if (x_dtype != V2V_F32 && x_dtype != V2V_BF16) return fail(V2V_ERR_DTYPE, "v2v_lpips_stem_hip: x_dtype must be V2V_F32 or V2V_BF16");
-    if (const int rc = lpips_image_check("v2v_lpips_stem_hip", B, Cin, H, W)) return rc;
-    if (!aligned(x, x_dtype == V2V_F32 ? 4 : 2) || !aligned(weight, 4) || !aligned(bias, 4) || !aligned(shift, 4) || !aligned(scale, 4) || !aligned(out, 16))
-        return fail(V2V_ERR_ALIGN, "v2v_lpips_stem_hip: out needs 16-byte alignment, float32 pointers 4-byte");
-    const hipError_t e = v2v::launch_lpips_stem(x, x_dtype == V2V_BF16, (int)B, (int)Cin, (int)H, (int)W, weight, bias, shift, scale, normalize ? 1 : 0,
-                                                static_cast<uint16_t *>(out), static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "lpips_stem_kernel launch");
-}
-
-int v2v_lpips_stem_bwd_hip(const void *dz, int64_t B, int64_t Cin, int64_t H, int64_t W, const float *weight, const float *scale, int normalize,
-                           float *dpred, void *stream)
-{
-    if (!dz || !weight || !scale || !dpred) return fail(V2V_ERR_NULL, "v2v_lpips_stem_bwd_hip: dz/weight/scale/dpred is NULL");
-    if (const int rc = lpips_image_check("v2v_lpips_stem_bwd_hip", B, Cin, H, W)) return rc;
-    if (!aligned(dz, 16) || !aligned(weight, 4) || !aligned(scale, 4) || !aligned(dpred, 4))
-        return fail(V2V_ERR_ALIGN, "v2v_lpips_stem_bwd_hip: dz needs 16-byte alignment, float32 pointers 4-byte");
-    const hipError_t e = v2v::launch_lpips_stem_bwd(static_cast<const uint16_t *>(dz), (int)B, (int)Cin, (int)H, (int)W, weight, scale, normalize ? 1 : 0, dpred,
-                                                    static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "lpips_stem_bwd_kernel launch");
-}
-
-int v2v_lpips_pool_hip(const void *x, int64_t B, int64_t H, int64_t W, int64_t C, void *out, void *stream)
-{
-    if (!x || !out) return fail(V2V_ERR_NULL, "v2v_lpips_pool_hip: x/out is NULL");
-    if (const int rc = lpips_pool_check("v2v_lpips_pool_hip", B, H, W, C)) return rc;
-    if (!aligned(x, 16) || !aligned(out, 16)) return fail(V2V_ERR_ALIGN, "v2v_lpips_pool_hip: x/out need 16-byte alignment");
-    const hipError_t e = v2v::launch_lpips_pool(static_cast<const uint16_t *>(x), (int)B, (int)H, (int)W, (int)C, static_cast<uint16_t *>(out),
-                                                static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "lpips_pool_kernel launch");
-}
-
-int v2v_lpips_pool_bwd_hip(const void *dy, const void *x, const void *dtap, int relu_mask, int64_t B, int64_t H, int64_t W, int64_t C, void *dx, void *stream)
-{
-    if (!dy || !x || !dx) return fail(V2V_ERR_NULL, "v2v_lpips_pool_bwd_hip: dy/x/dx is NULL");
-    if (const int rc = lpips_pool_check("v2v_lpips_pool_bwd_hip", B, H, W, C)) return rc;
-    if (!aligned(dy, 16) || !aligned(x, 16) || !aligned(dtap, 16) || !aligned(dx, 16)) return fail(V2V_ERR_ALIGN, "v2v_lpips_pool_bwd_hip: dy/x/dtap/dx need 16-byte alignment");
-    if (dx == dy) return fail(V2V_ERR_PARAM, "v2v_lpips_pool_bwd_hip: dx must not alias dy");
-    const hipError_t e = v2v::launch_lpips_pool_bwd(static_cast<const uint16_t *>(dy), static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(dtap),
-                                                    relu_mask ? 1 : 0, (int)B, (int)H, (int)W, (int)C, static_cast<uint16_t *>(dx), static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "lpips_pool_bwd_kernel launch");
-}
-
-int64_t v2v_lpips_compare_workspace_bytes(int64_t n_img, int64_t HW)
-{
-    if (n_img < 1 || HW < 1) return V2V_ERR_SHAPE;
-    return (n_img * ((HW + v2v::kLpCmpTile - 1) / v2v::kLpCmpTile) * 4 + 15) / 16 * 16;
-}
-
-int v2v_lpips_compare_fwd_hip(const void *f0, const void *f1, const float *w, int64_t n_img, int64_t HW, int64_t Cc, float *dist, void *workspace, void *stream)
-{
-    if (!f0 || !f1 || !w || !dist || !workspace) return fail(V2V_ERR_NULL, "v2v_lpips_compare_fwd_hip: f0/f1/w/dist/workspace is NULL");
-    if (const int rc = lpips_compare_check("v2v_lpips_compare_fwd_hip", n_img, HW, Cc)) return rc;
-    if (!aligned(f0, 16) || !aligned(f1, 16) || !aligned(w, 4) || !aligned(dist, 4) || !aligned(workspace, 16))
-        return fail(V2V_ERR_ALIGN, "v2v_lpips_compare_fwd_hip: f0/f1/workspace need 16-byte alignment, w/dist 4-byte");
-    const hipError_t e = v2v::launch_lpips_compare_fwd(static_cast<const uint16_t *>(f0), static_cast<const uint16_t *>(f1), w, (int)n_img, (int)HW, (int)Cc,
-                                                       static_cast<float *>(workspace), dist, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "lpips_compare_fwd_kernel launch");
-}
-
-int v2v_lpips_compare_bwd_hip(const void *f0, const void *f1, const float *w, const float *ddist, int64_t n_img, int64_t HW, int64_t Cc, void *df0, void *stream)
-{
-    if (!f0 || !f1 || !w || !ddist || !df0) return fail(V2V_ERR_NULL, "v2v_lpips_compare_bwd_hip: f0/f1/w/ddist/df0 is NULL");
-    if (const int rc = lpips_compare_check("v2v_lpips_compare_bwd_hip", n_img, HW, Cc)) return rc;
-    if (!aligned(f0, 16) || !aligned(f1, 16) || !aligned(w, 4) || !aligned(ddist, 4) || !aligned(df0, 16))
-        return fail(V2V_ERR_ALIGN, "v2v_lpips_compare_bwd_hip: f0/f1/df0 need 16-byte alignment, w/ddist 4-byte");
-    const hipError_t e = v2v::launch_lpips_compare_bwd(static_cast<const uint16_t *>(f0), static_cast<const uint16_t *>(f1), w, ddist, (int)n_img, (int)HW, (int)Cc,
-                                                       static_cast<uint16_t *>(df0), static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? V2V_OK : hip_fail(e, "lpips_compare_bwd_kernel launch");
 }
 
 }  // extern "C"

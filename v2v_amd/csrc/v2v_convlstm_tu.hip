@@ -1,6 +1,10 @@
-// v2v_convlstm_tu.hip -- translation unit of the fused ConvLSTM step: launchers.
+// v2v_convlstm_tu.hip -- translation unit of the fused ConvLSTM step and of the layers that share its kernels'
+// header: convolution, head, stem, 1x1, upsampling, layout.  The launchers that choose an instance, then the C entry points
+// (include/v2v_hip.h).
+#include "../../include/v2v_hip.h"
 #include "v2v_convlstm.hpp"
 #include "v2v_args.hpp"
+#include "v2v_status.hpp"
 
 namespace v2v {
 
@@ -119,13 +123,6 @@ hipError_t launch_conv_pack(const float *w, uint16_t *wp, int Cin, int Cout, int
     return hipGetLastError();
 }
 
-hipError_t launch_convlstm_pack(const float *w, uint16_t *wp, int C, hipStream_t s)
-{
-    const int64_t n = (int64_t)4 * C * 2 * C * 9;
-    hipLaunchKernelGGL(convlstm_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, wp, C);
-    return hipGetLastError();
-}
-
 hipError_t launch_nchw_to_nhwc_bf16(const void *src, bool src_bf16, uint16_t *dst, int B, int C, int HW, int relu, hipStream_t s)
 {
     const int64_t blocks = (int64_t)B * (C / 64) * (HW / 64);
@@ -133,27 +130,6 @@ hipError_t launch_nchw_to_nhwc_bf16(const void *src, bool src_bf16, uint16_t *ds
         hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel<uint16_t>, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const uint16_t *>(src), dst, C, HW, relu);
     else
         hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const float *>(src), dst, C, HW, relu);
-    return hipGetLastError();
-}
-
-hipError_t launch_conv_head(const uint16_t *x8, const uint16_t *wp, const float *bias, uint16_t *out, int B, int H, int W, int ks, int relu, hipStream_t s)
-{
-    const int pw = 16 + 2 * (ks >> 1), lds = ((pw * pw * 16 + 16 + 127) & ~127) + ((ks * ks + 7) / 8) * 32 * 128;
-    hipLaunchKernelGGL(conv_head_kernel, dim3((unsigned)(B * (H / 16) * (W / 16))), dim3(256), lds, s, x8, wp, bias, out, B, H, W, ks, relu);
-    return hipGetLastError();
-}
-
-hipError_t launch_conv_head_pack(const float *w, uint16_t *wp, int Cin, int ks, hipStream_t s)
-{
-    const int n = ((ks * ks + 7) / 8) * 32 * 64;
-    hipLaunchKernelGGL(conv_head_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, wp, Cin, ks);
-    return hipGetLastError();
-}
-
-hipError_t launch_to_nhwc8_bf16(const float *src, int64_t sb, int64_t sc, int64_t sh, int64_t sw, uint16_t *dst, int B, int C, int H, int W, const float *scales, hipStream_t s)
-{
-    const int64_t n = (int64_t)B * H * W;
-    hipLaunchKernelGGL(to_nhwc8_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, sb, sc, sh, sw, dst, B, C, H, W, scales);
     return hipGetLastError();
 }
 
@@ -168,18 +144,6 @@ hipError_t launch_conv1x1_nhwc(const uint16_t *x, const uint16_t *skip, const fl
     case 3: hipLaunchKernelGGL(conv1x1_nhwc_kernel<3>, grid, block, 0, s, x, skip, w, bias, out, out_bf16, M, C); break;
     default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
-}
-
-hipError_t launch_conv_stem(const uint16_t *x8, const uint16_t *wp, const float *bias, uint16_t *out, int B, int H, int W, int relu, hipStream_t s)
-{
-    hipLaunchKernelGGL(conv_stem_kernel, dim3((unsigned)(B * (H / (2 * kStemT)) * (W / (2 * kStemT)))), dim3(256), kStemLdsBytes, s, x8, wp, bias, out, B, H, W, relu);
-    return hipGetLastError();
-}
-
-hipError_t launch_conv_stem_pack(const float *w, uint16_t *wp, int Cin, hipStream_t s)
-{
-    hipLaunchKernelGGL(conv_stem_pack_kernel, dim3(2 * 64 * 64 / 256), dim3(256), 0, s, w, wp, Cin);
     return hipGetLastError();
 }
 
@@ -219,3 +183,288 @@ hipError_t launch_upsample2x_nhwc(const uint16_t *x, const uint16_t *skip, uint1
 }
 
 }  // namespace v2v
+
+using v2v::aligned;
+using v2v::fail;
+using v2v::hip_fail;
+using v2v::launched;
+
+extern "C" {
+
+int v2v_convlstm_packed_bytes(int64_t C, uint64_t *bytes)
+{
+    if (!bytes) return fail(V2V_ERR_NULL, "v2v_convlstm_packed_bytes: bytes is NULL");
+    if (C < 64 || C % 64 != 0) return fail(V2V_ERR_SHAPE, "ConvLSTM kernel needs C %% 64 == 0 (got %lld)", (long long)C);
+    *bytes = (uint64_t)4 * C * 2 * C * 9 * 2;
+    return V2V_OK;
+}
+
+int v2v_convlstm_pack_weights_hip(const float *gates_weight, int64_t C, void *packed, void *stream)
+{
+    if (!gates_weight || !packed) return fail(V2V_ERR_NULL, "v2v_convlstm_pack_weights_hip: gates_weight/packed is NULL");
+    if (C < 64 || C % 64 != 0 || C > 4096) return fail(V2V_ERR_SHAPE, "ConvLSTM kernel needs C %% 64 == 0, C <= 4096 (got %lld)", (long long)C);
+    if (!aligned(gates_weight, 4) || !aligned(packed, 16)) return fail(V2V_ERR_ALIGN, "gates_weight needs 4-byte, packed 16-byte alignment");
+    const int64_t n = (int64_t)4 * C * 2 * C * 9;
+    hipLaunchKernelGGL(v2v::convlstm_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), gates_weight,
+                       static_cast<uint16_t *>(packed), (int)C);
+    return launched("convlstm_pack_kernel launch");
+}
+
+int v2v_convlstm_step_hip(const void *x, const void *h_prev, const float *c_prev, const void *packed, const float *gates_bias,
+                          int64_t B, int64_t H, int64_t W, int64_t C, void *h_state, float *c_state, void *h_nchw, int h_nchw_dtype, int tile_rows, void *stream)
+{
+    if (h_nchw && h_nchw_dtype != V2V_F32 && h_nchw_dtype != V2V_BF16) return fail(V2V_ERR_DTYPE, "h_nchw_dtype must be V2V_F32 or V2V_BF16");
+    if (!x || !packed || !gates_bias || !h_state || !c_state) return fail(V2V_ERR_NULL, "v2v_convlstm_step_hip: x/packed/gates_bias/h_state/c_state is NULL");
+    if (B < 1 || H < 1 || W < 1 || C < 64 || C % 64 != 0 || C > 4096) return fail(V2V_ERR_SHAPE, "need B,H,W >= 1 and C %% 64 == 0, C <= 4096");
+    if (tile_rows != 0 && tile_rows != 64 && tile_rows != 128 && tile_rows != 256) return fail(V2V_ERR_PARAM, "tile_rows must be 0 (auto), 64, 128 or 256");
+    if ((H * W) % 4 != 0 || B * H * W * C > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "ConvLSTM kernel needs (H*W) %% 4 == 0 and B*H*W*C < 2^31 (got %lldx%lldx%lldx%lld)",
+                    (long long)B, (long long)H, (long long)W, (long long)C);
+    if (h_state == h_prev || h_state == x) return fail(V2V_ERR_PARAM, "h_state must not alias h_prev or x (neighbouring tiles read them)");
+    if (!aligned(x, 16) || !aligned(h_prev, 16) || !aligned(packed, 16) || !aligned(h_state, 2) || !aligned(c_prev, 4) || !aligned(c_state, 4) ||
+        !aligned(gates_bias, 4) || !aligned(h_nchw, 16))
+        return fail(V2V_ERR_ALIGN, "x/h_prev/packed/h_nchw need 16-byte alignment");
+    v2v::ConvLstmArgs a{};
+    a.x = static_cast<const uint16_t *>(x); a.h_prev = static_cast<const uint16_t *>(h_prev); a.c_prev = c_prev;
+    a.wp = static_cast<const uint16_t *>(packed); a.bias = gates_bias;
+    a.h_state = static_cast<uint16_t *>(h_state); a.c_state = c_state; a.h_nchw = h_nchw; a.h_nchw_bf16 = h_nchw_dtype == V2V_BF16;
+    a.B = (int)B; a.H = (int)H; a.W = (int)W; a.C = (int)C;
+    const hipError_t e = v2v::launch_convlstm_step(a, tile_rows, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "convlstm_step_kernel launch");
+}
+
+int64_t v2v_conv_packed_elems(int64_t Cin, int64_t Cout, int ks)
+{
+    if ((ks != 3 && ks != 5) || Cout < 1 || Cout > 4096 || v2v::conv_tile_cols((int)Cout) == 0) return -1;
+    if (Cin == 32) return (Cout == 64 || Cout == 128) ? Cout * ((ks * ks + 1) / 2) * 64 : -1;      // two taps per 64-wide chunk
+    if (Cin < 64 || Cin % 64 != 0 || Cin > 4096) return -1;
+    return Cout * Cin * ks * ks;
+}
+
+int v2v_conv_pack_weights_hip(const float *weight, int64_t Cin, int64_t Cout, int ks, void *packed, void *stream)
+{
+    if (!weight || !packed) return fail(V2V_ERR_NULL, "v2v_conv_pack_weights_hip: weight/packed is NULL");
+    if (v2v_conv_packed_elems(Cin, Cout, ks) < 0)
+        return fail(V2V_ERR_SHAPE, "conv kernel needs Cin %% 64 == 0 (or Cin 32 with Cout 64 / 128), Cout in {32, 64, 128} or a multiple of 256, ks 3 or 5 (got %lld -> %lld, ks %d)",
+                    (long long)Cin, (long long)Cout, ks);
+    if (!aligned(weight, 4) || !aligned(packed, 16)) return fail(V2V_ERR_ALIGN, "weight needs 4-byte, packed 16-byte alignment");
+    const hipError_t e = v2v::launch_conv_pack(weight, static_cast<uint16_t *>(packed), (int)Cin, (int)Cout, ks, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv_pack_kernel launch");
+}
+
+int v2v_conv_nhwc_hip(const void *x, const void *packed, const float *bias, const void *residual, int relu, int64_t B, int64_t Hin,
+                      int64_t Win, int64_t Cin, int64_t Cout, int ks, int stride, void *out, int tile_rows, void *stream)
+{
+    if (!x || !packed || !bias || !out) return fail(V2V_ERR_NULL, "v2v_conv_nhwc_hip: x/packed/bias/out is NULL");
+    if ((ks != 3 && ks != 5) || (stride != 1 && stride != 2)) return fail(V2V_ERR_PARAM, "ks must be 3 or 5, stride 1 or 2");
+    if (B < 1 || Hin < 1 || Win < 1 || v2v_conv_packed_elems(Cin, Cout, ks) < 0)
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, Cin %% 64 == 0 (or Cin 32 with Cout 64 / 128), Cout in {32, 64, 128} or a multiple of 256");
+    const int64_t H = (Hin - 1) / stride + 1, W = (Win - 1) / stride + 1;          // output size for pad = ks / 2
+    if (tile_rows != 0 && tile_rows != 128 && tile_rows != 256 && tile_rows != 16 && (Cout % 256 != 0 || (tile_rows != 32 && tile_rows != 64)))
+        return fail(V2V_ERR_PARAM, "tile_rows must be 0 (auto), 128 or 256 (and 32 or 64 for Cout %% 256 == 0)");
+    const bool halo_fits = Cin % 64 == 0 && Cout % 256 != 0 && stride == 1 && H % 16 == 0 && W % 16 == 0 && (ks == 3 || Cout <= 64);   // see launch_conv_nhwc
+    const bool halo = halo_fits && (tile_rows == 16 || (tile_rows == 0 && ks == 5));
+    if (tile_rows == 16 && !halo) return fail(V2V_ERR_PARAM, "tile_rows 16 (halo tiles) needs stride 1, H and W multiples of 16 and Cout 32 / 64 (128 for 3x3)");
+    if ((H * W) % 4 != 0 || B * Hin * Win * Cin > 0x7FFFFFFFLL || B * H * W * Cout > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "conv kernel needs (Hout*Wout) %% 4 == 0 and tensors below 2^31 elements");
+    if (out == x) return fail(V2V_ERR_PARAM, "out must not alias x (neighbouring tiles read it)");
+    if (!aligned(x, 16) || !aligned(packed, 16) || !aligned(out, 2) || !aligned(residual, 2) || !aligned(bias, 4))
+        return fail(V2V_ERR_ALIGN, "x/packed need 16-byte alignment");
+    v2v::ConvLstmArgs a{};
+    a.x = static_cast<const uint16_t *>(x); a.wp = static_cast<const uint16_t *>(packed); a.bias = bias;
+    a.residual = static_cast<const uint16_t *>(residual); a.out_nhwc = static_cast<uint16_t *>(out);
+    a.n_cols = (int)Cout; a.relu = relu ? 1 : 0; a.ks = ks; a.stride = stride; a.Hin = (int)Hin; a.Win = (int)Win;
+    a.B = (int)B; a.H = (int)H; a.W = (int)W; a.C = (int)Cin;
+    const hipError_t e = v2v::launch_conv_nhwc(a, tile_rows, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv (convlstm_step_kernel, EPI = 1) launch");
+}
+
+int64_t v2v_conv_head_packed_elems(int ks) { return (ks == 3 || ks == 5) ? (int64_t)((ks * ks + 7) / 8) * 32 * 64 : -1; }
+
+int v2v_conv_head_pack_weights_hip(const float *weight, int64_t Cin, int ks, void *packed, void *stream)
+{
+    if (!weight || !packed) return fail(V2V_ERR_NULL, "v2v_conv_head_pack_weights_hip: weight/packed is NULL");
+    if (Cin < 1 || Cin > 8 || (ks != 3 && ks != 5)) return fail(V2V_ERR_SHAPE, "need 1 <= Cin <= 8 and ks 3 or 5 (32 output channels)");
+    if (!aligned(packed, 16)) return fail(V2V_ERR_ALIGN, "packed needs 16-byte alignment");
+    const int n = ((ks * ks + 7) / 8) * 32 * 64;
+    hipLaunchKernelGGL(v2v::conv_head_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), weight,
+                       static_cast<uint16_t *>(packed), (int)Cin, ks);
+    return launched("conv_head_pack_kernel launch");
+}
+
+int v2v_to_nhwc8_bf16_hip(const float *src, int64_t stride_b, int64_t stride_c, int64_t stride_h, int64_t stride_w, int64_t B, int64_t C,
+                          int64_t H, int64_t W, void *dst, void *stream)
+{
+    return v2v_to_nhwc8_bf16_scaled_hip(src, stride_b, stride_c, stride_h, stride_w, B, C, H, W, nullptr, dst, stream);
+}
+
+int v2v_to_nhwc8_bf16_scaled_hip(const float *src, int64_t stride_b, int64_t stride_c, int64_t stride_h, int64_t stride_w, int64_t B, int64_t C,
+                                 int64_t H, int64_t W, const float *scales, void *dst, void *stream)
+{
+    if (!src || !dst) return fail(V2V_ERR_NULL, "v2v_to_nhwc8_bf16_hip: src/dst is NULL");
+    if (B < 1 || C < 1 || C > 8 || H < 1 || W < 1 || B * H * W > 0x7FFFFFFFLL) return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, 1 <= C <= 8, B*H*W < 2^31");
+    if (!aligned(dst, 16) || !aligned(src, 4) || (scales && !aligned(scales, 4))) return fail(V2V_ERR_ALIGN, "dst needs 16-byte alignment");
+    const int64_t n = B * H * W;
+    hipLaunchKernelGGL(v2v::to_nhwc8_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), src, stride_b, stride_c,
+                       stride_h, stride_w, static_cast<uint16_t *>(dst), (int)B, (int)C, (int)H, (int)W, scales);
+    return launched("to_nhwc8_bf16_kernel launch");
+}
+
+int v2v_conv_head_nhwc_hip(const void *x8, const void *packed, const float *bias, int relu, int64_t B, int64_t H, int64_t W, int ks, void *out, void *stream)
+{
+    if (!x8 || !packed || !bias || !out) return fail(V2V_ERR_NULL, "v2v_conv_head_nhwc_hip: x8/packed/bias/out is NULL");
+    if (ks != 3 && ks != 5) return fail(V2V_ERR_PARAM, "ks must be 3 or 5");
+    if (B < 1 || H < 16 || W < 16 || H % 16 != 0 || W % 16 != 0 || B * H * W * 32 > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need B >= 1, H and W multiples of 16, output below 2^31 elements");
+    if (!aligned(x8, 16) || !aligned(packed, 16) || !aligned(out, 2) || !aligned(bias, 4)) return fail(V2V_ERR_ALIGN, "x8/packed need 16-byte alignment");
+    const int pw = 16 + 2 * (ks >> 1), lds = ((pw * pw * 16 + 16 + 127) & ~127) + ((ks * ks + 7) / 8) * 32 * 128;
+    hipLaunchKernelGGL(v2v::conv_head_kernel, dim3((unsigned)(B * (H / 16) * (W / 16))), dim3(256), lds, static_cast<hipStream_t>(stream),
+                       static_cast<const uint16_t *>(x8), static_cast<const uint16_t *>(packed), bias, static_cast<uint16_t *>(out), (int)B, (int)H, (int)W, ks,
+                       relu ? 1 : 0);
+    return launched("conv_head_kernel launch");
+}
+
+int v2v_conv1x1_nhwc_hip(const void *x, const void *skip, const float *weight, const float *bias, int64_t M, int64_t C, int64_t Cout,
+                         void *out, int out_dtype, void *stream)
+{
+    if (!x || !weight || !bias || !out) return fail(V2V_ERR_NULL, "v2v_conv1x1_nhwc_hip: x/weight/bias/out is NULL");
+    if (out_dtype != V2V_F32 && out_dtype != V2V_BF16) return fail(V2V_ERR_DTYPE, "out_dtype must be V2V_F32 or V2V_BF16");
+    if (M < 1 || C < 8 || C > 512 || (C & (C - 1)) != 0 || Cout < 1 || Cout > 3 || M * (C / 8) > 0x7FFFFFFFLL * 256)
+        return fail(V2V_ERR_SHAPE, "need M >= 1, C a power of two in 8..512, Cout 1..3");
+    if (!aligned(x, 16) || !aligned(skip, 16) || !aligned(out, out_dtype == V2V_F32 ? 4 : 2)) return fail(V2V_ERR_ALIGN, "x/skip need 16-byte alignment");
+    const hipError_t e = v2v::launch_conv1x1_nhwc(static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(skip), weight, bias, out,
+                                                  out_dtype == V2V_BF16, M, (int)C, (int)Cout, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv1x1_nhwc_kernel launch");
+}
+
+int v2v_upsample2x_nhwc_hip(const void *x, const void *skip, int64_t B, int64_t H, int64_t W, int64_t C, void *out, void *stream)
+{
+    if (!x || !out) return fail(V2V_ERR_NULL, "v2v_upsample2x_nhwc_hip: x/out is NULL");
+    if (B < 1 || H < 1 || W < 1 || C < 8 || C % 8 != 0 || B * H * W * C > (1LL << 36))
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C %% 8 == 0 and an input below 2^36 elements");
+    if (!aligned(x, 16) || !aligned(out, 16) || !aligned(skip, 16)) return fail(V2V_ERR_ALIGN, "x/skip/out need 16-byte alignment");
+    if (out == x || out == skip) return fail(V2V_ERR_PARAM, "out must not alias x or skip");
+    const hipError_t e = v2v::launch_upsample2x_nhwc(static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(skip), static_cast<uint16_t *>(out),
+                                                     (int)B, (int)H, (int)W, (int)C, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "upsample2x_nhwc_bf16_kernel launch");
+}
+
+int v2v_conv3x3_pack_weights_hip(const float *weight, int64_t Cin, int64_t Cout, void *packed, void *stream)
+{
+    return v2v_conv_pack_weights_hip(weight, Cin, Cout, 3, packed, stream);
+}
+
+int v2v_conv3x3_nhwc_hip(const void *x, const void *packed, const float *bias, const void *residual, int relu, int64_t B, int64_t H,
+                         int64_t W, int64_t Cin, int64_t Cout, void *out, int tile_rows, void *stream)
+{
+    return v2v_conv_nhwc_hip(x, packed, bias, residual, relu, B, H, W, Cin, Cout, 3, 1, out, tile_rows, stream);
+}
+
+int v2v_nchw_to_nhwc_bf16_hip(const void *src, int src_dtype, int64_t B, int64_t C, int64_t H, int64_t W, int relu, void *dst, void *stream)
+{
+    if (!src || !dst) return fail(V2V_ERR_NULL, "v2v_nchw_to_nhwc_bf16_hip: src/dst is NULL");
+    if (src_dtype != V2V_F32 && src_dtype != V2V_BF16) return fail(V2V_ERR_DTYPE, "src_dtype must be V2V_F32 or V2V_BF16");
+    if (B < 1 || H < 1 || W < 1 || C < 64 || C % 64 != 0 || (H * W) % 64 != 0 || B * (C / 64) * (H * W / 64) > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C %% 64 == 0, (H*W) %% 64 == 0");
+    if (!aligned(src, src_dtype == V2V_F32 ? 4 : 2) || !aligned(dst, 2)) return fail(V2V_ERR_ALIGN, "buffers misaligned");
+    const hipError_t e = v2v::launch_nchw_to_nhwc_bf16(src, src_dtype == V2V_BF16, static_cast<uint16_t *>(dst), (int)B, (int)C, (int)(H * W),
+                                                       relu ? 1 : 0, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "nchw_to_nhwc_bf16_kernel launch");
+}
+
+// the data gradient of a convolution runs on the forward convolution's instances (weights packed by v2v_conv_dgrad_pack_weights_hip,
+// v2v_train_tu.hip), so its entry point lives with them
+int v2v_conv_dgrad_nhwc_hip(const void *dy, const void *packed, const void *residual, int64_t B, int64_t Hin, int64_t Win, int64_t Cin, int64_t Cout,
+                            int ks, int stride, void *workspace, void *dx, void *stream)
+{
+    if (!dy || !packed || !workspace || !dx) return fail(V2V_ERR_NULL, "v2v_conv_dgrad_nhwc_hip: dy/packed/workspace/dx is NULL");
+    if ((ks != 3 && ks != 5) || (stride != 1 && stride != 2)) return fail(V2V_ERR_PARAM, "ks must be 3 or 5, stride 1 or 2");
+    if (B < 1 || Hin < 1 || Win < 1 || v2v_conv_dgrad_packed_elems(Cin, Cout, ks) < 0 || Hin % stride != 0 || Win % stride != 0 || (Hin * Win) % 4 != 0
+        || B * Hin * Win * (Cin > Cout ? Cin : Cout) > 0x7FFFFFFFLL || Cout % 8 != 0)
+        return fail(V2V_ERR_SHAPE, "need the transposed convolution Cout -> Cin to be a shape the convolution kernel takes, Hin, Win multiples "
+                                   "of the stride, (Hin*Win) %% 4 == 0, tensors below 2^31 elements");
+    if (dx == dy) return fail(V2V_ERR_PARAM, "dx must not alias dy");
+    if (!aligned(dy, 16) || !aligned(packed, 16) || !aligned(workspace, 256) || !aligned(dx, 2) || !aligned(residual, 2))
+        return fail(V2V_ERR_ALIGN, "dy/packed need 16-byte, workspace 256-byte alignment");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    float *zero_bias = static_cast<float *>(workspace);
+    hipError_t e = hipMemsetAsync(zero_bias, 0, Cin * 4, s);
+    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(zero bias)");
+    const uint16_t *src = static_cast<const uint16_t *>(dy);
+    if (stride == 2) {
+        uint16_t *grid = reinterpret_cast<uint16_t *>(static_cast<unsigned char *>(workspace) + (Cin * 4 + 255) / 256 * 256);
+        e = v2v::launch_relu_mask_stuff(src, nullptr, grid, (int)B, (int)(Hin / 2), (int)(Win / 2), (int)Cout, 2, s);
+        if (e != hipSuccess) return hip_fail(e, "relu_mask_stuff_kernel launch");
+        src = grid;
+    }
+    v2v::ConvLstmArgs a{};
+    a.x = src; a.wp = static_cast<const uint16_t *>(packed); a.bias = zero_bias;
+    a.residual = static_cast<const uint16_t *>(residual); a.out_nhwc = static_cast<uint16_t *>(dx);
+    a.n_cols = (int)Cin; a.relu = 0; a.ks = ks; a.stride = 1; a.Hin = (int)Hin; a.Win = (int)Win;
+    a.B = (int)B; a.H = (int)Hin; a.W = (int)Win; a.C = (int)Cout;
+    e = v2v::launch_conv_nhwc(a, 0, s);
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "dgrad (convlstm_step_kernel, EPI = 1) launch");
+}
+
+// ---- the plain UNet (EVFlowNet): stem, concat-skip upsampling, the time-folded convolution ----------------------------------------------
+int64_t v2v_conv_stem_packed_elems(void) { return 2 * 64 * 64; }
+
+int v2v_conv_stem_pack_weights_hip(const float *weight, int64_t Cin, void *packed, void *stream)
+{
+    if (!weight || !packed) return fail(V2V_ERR_NULL, "v2v_conv_stem_pack_weights_hip: weight/packed is NULL");
+    if (Cin < 1 || Cin > 8) return fail(V2V_ERR_SHAPE, "need 1 <= Cin <= 8 (64 output channels, 3x3)");
+    if (!aligned(weight, 4) || !aligned(packed, 16)) return fail(V2V_ERR_ALIGN, "weight needs 4-byte, packed 16-byte alignment");
+    hipLaunchKernelGGL(v2v::conv_stem_pack_kernel, dim3(2 * 64 * 64 / 256), dim3(256), 0, static_cast<hipStream_t>(stream), weight, static_cast<uint16_t *>(packed),
+                       (int)Cin);
+    return launched("conv_stem_pack_kernel launch");
+}
+
+int v2v_conv_stem_nhwc_hip(const void *x8, const void *packed, const float *bias, int relu, int64_t B, int64_t H, int64_t W, void *out, void *stream)
+{
+    if (!x8 || !packed || !bias || !out) return fail(V2V_ERR_NULL, "v2v_conv_stem_nhwc_hip: x8/packed/bias/out is NULL");
+    if (B < 1 || H < 16 || W < 16 || H % 16 != 0 || W % 16 != 0 || B * H * W * 16 > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need B >= 1, H and W multiples of 16, output below 2^31 elements");
+    if (!aligned(x8, 16) || !aligned(packed, 16) || !aligned(out, 2) || !aligned(bias, 4)) return fail(V2V_ERR_ALIGN, "x8/packed need 16-byte alignment");
+    if (out == x8) return fail(V2V_ERR_PARAM, "out must not alias x8");
+    hipLaunchKernelGGL(v2v::conv_stem_kernel, dim3((unsigned)(B * (H / (2 * v2v::kStemT)) * (W / (2 * v2v::kStemT)))), dim3(256), v2v::kStemLdsBytes,
+                       static_cast<hipStream_t>(stream), static_cast<const uint16_t *>(x8), static_cast<const uint16_t *>(packed), bias,
+                       static_cast<uint16_t *>(out), (int)B, (int)H, (int)W, relu ? 1 : 0);
+    return launched("conv_stem_kernel launch");
+}
+
+int v2v_upsample2x_cat_nhwc_hip(const void *x, int64_t C1, const void *skip, int64_t C2, int64_t B, int64_t H, int64_t W, void *out, void *stream)
+{
+    if (!x || !out || (C2 > 0 && !skip)) return fail(V2V_ERR_NULL, "v2v_upsample2x_cat_nhwc_hip: x/out (or skip with C2 > 0) is NULL");
+    if (B < 1 || H < 1 || W < 1 || C1 < 8 || C1 % 8 != 0 || C2 < 0 || C2 % 8 != 0 || B * 4 * H * W * (C1 + C2) > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C1 %% 8 == 0, C2 %% 8 == 0 and an output below 2^31 elements");
+    if (skip && C2 == 0) return fail(V2V_ERR_PARAM, "skip given with C2 == 0");
+    if (!aligned(x, 16) || !aligned(out, 16) || !aligned(skip, 16)) return fail(V2V_ERR_ALIGN, "x/skip/out need 16-byte alignment");
+    if (out == x || out == skip) return fail(V2V_ERR_PARAM, "out must not alias x or skip");
+    const hipError_t e = v2v::launch_upsample2x_cat_nhwc(static_cast<const uint16_t *>(x), (int)C1, static_cast<const uint16_t *>(skip), (int)C2,
+                                                         static_cast<uint16_t *>(out), (int)B, (int)H, (int)W, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "upsample2x_cat_nhwc_bf16_kernel launch");
+}
+
+int v2v_conv_nhwc_like_hip(const void *x, const void *packed, const float *bias, const void *residual, int relu, int64_t B, int64_t Hin, int64_t Win,
+                           int64_t Cin, int64_t Cout, int ks, int stride, void *out, int64_t B_like, void *stream)
+{
+    if (!x || !packed || !bias || !out) return fail(V2V_ERR_NULL, "v2v_conv_nhwc_like_hip: x/packed/bias/out is NULL");
+    if ((ks != 3 && ks != 5) || (stride != 1 && stride != 2) || B_like < 0) return fail(V2V_ERR_PARAM, "ks must be 3 or 5, stride 1 or 2, B_like >= 0");
+    if (B < 1 || Hin < 1 || Win < 1 || v2v_conv_packed_elems(Cin, Cout, ks) < 0)
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, Cin %% 64 == 0 (or Cin 32 with Cout 64 / 128), Cout in {32, 64, 128} or a multiple of 256");
+    const int64_t H = (Hin - 1) / stride + 1, W = (Win - 1) / stride + 1;
+    if ((H * W) % 4 != 0 || B * Hin * Win * Cin > 0x7FFFFFFFLL || B * H * W * Cout > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "conv kernel needs (Hout*Wout) %% 4 == 0 and tensors below 2^31 elements");
+    if (out == x) return fail(V2V_ERR_PARAM, "out must not alias x (neighbouring tiles read it)");
+    if (!aligned(x, 16) || !aligned(packed, 16) || !aligned(out, 2) || !aligned(residual, 2) || !aligned(bias, 4))
+        return fail(V2V_ERR_ALIGN, "x/packed need 16-byte alignment");
+    v2v::ConvLstmArgs a{};
+    a.x = static_cast<const uint16_t *>(x); a.wp = static_cast<const uint16_t *>(packed); a.bias = bias;
+    a.residual = static_cast<const uint16_t *>(residual); a.out_nhwc = static_cast<uint16_t *>(out);
+    a.n_cols = (int)Cout; a.relu = relu ? 1 : 0; a.ks = ks; a.stride = stride; a.Hin = (int)Hin; a.Win = (int)Win;
+    a.B = (int)B; a.H = (int)H; a.W = (int)W; a.C = (int)Cin;
+    const hipError_t e = v2v::launch_conv_nhwc(a, 0, static_cast<hipStream_t>(stream), B_like);
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv (convlstm_step_kernel, EPI = 1) launch");
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // v2v_hyper.hpp -- HyperE2VID's per-pixel dynamic decoder (model/hyper_model.py:33-60, model/hyper/hyper_dynamic.py) on gfx950.
 //
 // The layer replaces decoders[0] of the recurrent UNet:  y = relu(DynamicConv(up2(x + skip), atoms(context(events, prev_image)))).
-// Kernels in this file (launchers in v2v_hyper_tu.hip; this header alone, without V2V_HYPER_KERNELS, only declares the launchers):
+// Kernels in this file (launched by the C entry points in v2v_hyper_tu.hip; the training kernels further down by those in v2v_hyper_train_tu.hip):
 //   hyper_context_kernel   cat(events, prev_recs) bilinearly downsampled x1/4 -> bf16 NHWC8 (the head kernel's input layout); for the exact
 //                          factor 4 the source coordinate 4 d + 1.5 gives weights 1/2, 1/2 on pixels 4 d + 1, 4 d + 2 of either axis: the
 //                          mean of the central 2 x 2 of every 4 x 4 block (checked against the golden's `layer__context`)
@@ -38,15 +38,6 @@ namespace v2v {
 
 constexpr int kHyCin = 256, kHyCout = 128, kHyAtoms = 6, kHyTaps = 25, kHyCoeff = 72, kHyCoeffPad = 128, kHyBases = 12;
 constexpr int kHyAtomElems = kHyAtoms * kHyTaps;                         // 150 float32 per pixel
-
-hipError_t launch_hyper_context(const float *ev, int64_t sb, int64_t sc, int64_t sh, int64_t sw, const float *prev, uint16_t *dst, int B, int C, int H, int W,
-                                hipStream_t s);
-hipError_t launch_hyper_context_conv(const uint16_t *x8, const float *w, const float *bias, uint16_t *out, int B, int h, int wd, int Cin, hipStream_t s);
-hipError_t launch_hyper_tanh(const uint16_t *x, uint16_t *out, int64_t n8, hipStream_t s);
-hipError_t launch_hyper_atoms(const uint16_t *coeff, const float *bases, float *atoms, int64_t M, hipStream_t s);
-hipError_t launch_hyper_dynconv_pack(const float *w, uint16_t *wp, hipStream_t s);
-hipError_t launch_hyper_dynconv(const uint16_t *x, const float *atoms, const uint16_t *wp, const float *bias, uint16_t *out, int B, int H, int W, int relu,
-                                hipStream_t s);
 
 #if defined(V2V_HYPER_KERNELS) || defined(V2V_HYPER_TRAIN_KERNELS)   // what the forward and the backward kernels share
 

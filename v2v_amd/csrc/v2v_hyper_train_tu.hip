@@ -1,33 +1,16 @@
 // v2v_hyper_train_tu.hip -- translation unit of the dynamic decoder's BACKWARD (the training kernels of v2v_hyper.hpp) and its C entry points
-// (include/v2v_hip.h).  A translation unit of its own, error text included, so that the inference objects do not change with it.
+// (include/v2v_hip.h).
 #define V2V_HYPER_TRAIN_KERNELS
-#include <cstdarg>
-#include <cstdio>
-
 #include "../../include/v2v_hip.h"
 #include "v2v_hyper.hpp"
 #include "v2v_launch.hpp"
+#include "v2v_status.hpp"
+
+using v2v::aligned;
+using v2v::fail;
+using v2v::launched;
 
 namespace {
-
-thread_local char g_train_err[512] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_train_err, sizeof(g_train_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? V2V_OK : fail(V2V_ERR_HIP, "%s: %s (%d)", what, hipGetErrorString(e), (int)e);
-}
-
-bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 bool dyn_shape(int64_t B, int64_t H, int64_t W) { return B >= 1 && H >= 1 && W >= 1 && B * H * W * v2v::kHyFCols <= 0x7FFFFFFFLL * 4; }
 
@@ -40,7 +23,7 @@ int db_splits(int64_t M) { return (int)(M < 64 ? M : 64); }
 
 extern "C" {
 
-const char *v2v_hyper_train_last_error(void) { return g_train_err; }
+const char *v2v_hyper_train_last_error(void) { return v2v_last_error(); }     // deprecated alias, kept for clients linked against ABI 6
 
 int v2v_hyper_dynconv_pack_t_hip(const float *weight, void *packed_t, void *stream)
 {

@@ -1,6 +1,6 @@
 // v2v_loss.hpp -- the image losses of training (utils/loss.py:6-69 temporal consistency, model/loss.py l1_loss / l2_loss) as device kernels.
 //
-// Kernels in this file (launchers in v2v_loss_tu.hip; this header alone, without V2V_LOSS_KERNELS, only declares the launchers):
+// Kernels in this file (launched by the C entry points in v2v_loss_tu.hip):
 //   tc_loss_fwd_kernel         one launch for a list of images (outer x inner): warp image0 and clamp(processed0) by the flow, visibility mask,
 //                              tc_map, |processed1 - image1| and its square; one partial (tc, l1, l2) per workgroup into a fixed slot
 //   loss_reduce_kernel         per image: the partials in a fixed order -> weight * mean
@@ -34,16 +34,6 @@ struct LossArgs {
     int c, h, w, tiles;
     float alpha, flow_sign, w_tc, w_l1, w_l2;
 };
-
-hipError_t launch_tc_loss_fwd(const LossArgs &a, float *partials, float *losses, float *image0_warped, float *processed0_warped, float *visibility,
-                              float *error_map, hipStream_t s);
-// chain != 0: processed0 of image (a, b) IS processed1 of image (a, b - 1); dprocessed1 then also receives what the next step scatters
-// (dprocessed0 unused).  Buffers: acc int64 [n_img*c*h*w] and maxbits [n_img] zeroed by the caller, dwarp / dp1 float [n_img*c*h*w].
-hipError_t launch_tc_loss_bwd(const LossArgs &a, const float *gout, int chain, float *dprocessed1, float *dprocessed0, unsigned long long *acc, float *dwarp,
-                              float *dp1, unsigned *maxbits, hipStream_t s);
-hipError_t launch_warp_bilinear(const float *img, const float *flow, int64_t n, int c, int h, int w, float *out, hipStream_t s);
-hipError_t launch_warp_bilinear_adjoint(const float *dout, const float *flow, int64_t n, int c, int h, int w, float *din, unsigned long long *acc, unsigned *maxbits,
-                                        hipStream_t s);
 
 #ifdef V2V_LOSS_KERNELS
 

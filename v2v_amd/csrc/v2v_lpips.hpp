@@ -2,7 +2,7 @@
 // that are not a 64..512-channel 3x3 convolution; those twelve convolutions and their data gradients run on the convolution kernel of
 // v2v_convlstm.hpp (conv_nhwc / the dgrad-packed stream), this file adds what sits around them.
 //
-// Kernels in this file (launchers in v2v_lpips_tu.hip; this header alone, without V2V_LPIPS_KERNELS, only declares the launchers):
+// Kernels in this file (launched by the C entry points in v2v_lpips_tu.hip):
 //   lpips_stem_kernel            [B,1|3,H,W] float32 / bf16 -> optional 2x - 1, (x - shift) / scale, 3x3 conv 3 -> 64, bias, ReLU -> bf16 NHWC.
 //                                K = 27 on the vector ALU: a 16 x 16 pixel tile with its halo, scaled, in LDS (zero padding is zero AFTER the
 //                                scaling layer), the 27 x 64 weights in LDS (wave-uniform broadcast reads), one pixel per thread
@@ -29,18 +29,6 @@ namespace v2v {
 constexpr int kLpStemTile = 16;                 // the stem's tile: 16 x 16 pixels = 256 threads
 constexpr int kLpCmpTile = 64;                  // pixels per workgroup of the compare kernels
 constexpr float kLpEps = 1e-10f;                // normalize_tensor's eps (PerceptualSimilarity/models/__init__.py:48-50)
-
-hipError_t launch_lpips_stem(const void *x, int x_bf16, int B, int Cin, int H, int W, const float *weight, const float *bias, const float *shift,
-                             const float *scale, int normalize, uint16_t *out, hipStream_t s);
-hipError_t launch_lpips_stem_bwd(const uint16_t *dz, int B, int Cin, int H, int W, const float *weight, const float *scale, int normalize, float *dpred,
-                                 hipStream_t s);
-hipError_t launch_lpips_pool(const uint16_t *x, int B, int H, int W, int C, uint16_t *out, hipStream_t s);
-hipError_t launch_lpips_pool_bwd(const uint16_t *dy, const uint16_t *x, const uint16_t *dtap, int relu_mask, int B, int H, int W, int C, uint16_t *dx,
-                                 hipStream_t s);
-hipError_t launch_lpips_compare_fwd(const uint16_t *f0, const uint16_t *f1, const float *w, int n_img, int HW, int Cc, float *partials, float *dist,
-                                    hipStream_t s);
-hipError_t launch_lpips_compare_bwd(const uint16_t *f0, const uint16_t *f1, const float *w, const float *ddist, int n_img, int HW, int Cc, uint16_t *df0,
-                                    hipStream_t s);
 
 #ifdef V2V_LPIPS_KERNELS
 

@@ -1,6 +1,6 @@
 // v2v_narrow.hpp -- the 16-channel layer family (FireNet, model/model.py:264-311): activations NHWC bf16 [B,H,W,16] = 32 bytes per pixel,
 // bf16 operands, fp32 accumulation on the matrix cores (v_mfma_f32_16x16x32_bf16: 16 pixels x 16 output channels x K = 32 per instruction).
-// Kernels are compiled by v2v_narrow_tu.hip only (V2V_NARROW_KERNELS); v2v_capi.hip includes this header for the argument struct and launchers.
+// Kernels are compiled by v2v_narrow_tu.hip only (V2V_NARROW_KERNELS), which also holds the family's C entry points and their launches.
 //
 // One skeleton, "two dependent 3x3 convolutions through LDS" (narrow_two_conv_kernel): a workgroup of 4 waves owns a 16 x 16 pixel tile.
 //   stage 0   the tile + a 2-pixel halo (20 x 20) of the inputs -> LDS, zero outside the image
@@ -44,14 +44,6 @@ struct NarrowArgs {
 };
 
 constexpr int kGru16Frags = 27, kRes16Frags = 10, kHead16Frags = 3, kNarrowFragElems = 512;
-
-// v2v_narrow_tu.hip
-hipError_t launch_convgru16(const NarrowArgs &a, hipStream_t s);
-hipError_t launch_resblock16(const NarrowArgs &a, hipStream_t s);
-hipError_t launch_conv_head16(const NarrowArgs &a, hipStream_t s);
-hipError_t launch_convgru16_pack(const float *w_u, const float *w_r, const float *w_o, uint16_t *wp, hipStream_t s);
-hipError_t launch_resblock16_pack(const float *w1, const float *w2, uint16_t *wp, hipStream_t s);
-hipError_t launch_conv_head16_pack(const float *w, int Cin, uint16_t *wp, hipStream_t s);
 
 }  // namespace v2v
 

@@ -7,10 +7,13 @@
 // conv1x1_bwd_cout_kernel + conv1x1_bwd_cout_reduce_kernel (the prediction layer, 1..3 outputs).  The ConvLSTM step's backward is an epilogue of convlstm_step_kernel (EPI = 2,
 // v2v_convlstm.hpp).  Numerics: bf16 MFMA operands, fp32 accumulation, fp32 parameter gradients; no float atomics anywhere, so every
 // gradient is bitwise reproducible from run to run.
+// The C entry points of the backward operators (include/v2v_hip.h) follow the kernels and their launchers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/v2v_hip.h"
 #include "v2v_args.hpp"
+#include "v2v_status.hpp"
 
 namespace v2v {
 
@@ -185,13 +188,6 @@ __global__ void __launch_bounds__(256) dgrad_flip_kernel(const float *w, float *
     wt[i] = w[((int64_t)co * Cin + ci) * taps + (taps - 1 - tap)];
 }
 
-hipError_t launch_dgrad_flip(const float *w, float *wt, int Cout, int Cin, int ks, hipStream_t s)
-{
-    const int64_t n = (int64_t)Cout * Cin * ks * ks;
-    hipLaunchKernelGGL(dgrad_flip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, wt, Cout, Cin, ks);
-    return hipGetLastError();
-}
-
 // ---- adjoint of the x2 bilinear upsampling (align_corners=False, clamped edges) -------------------------------------------------
 // Forward (upsample2x_nhwc_bf16_kernel / upsample2x_cat_nhwc_bf16_kernel): output row 2m reads rows (max(m-1, 0), m) with weights
 // (0.25, 0.75), row 2m+1 reads (m, min(m+1, H-1)) with (0.75, 0.25); columns alike.  Gather form: input row k receives from output
@@ -350,3 +346,153 @@ hipError_t launch_conv1x1_bwd_cout(const float *dy, const uint16_t *x, const uin
 }
 
 }  // namespace v2v
+
+using v2v::aligned;
+using v2v::fail;
+using v2v::hip_fail;
+
+extern "C" {
+
+int v2v_convlstm_step_bwd_hip(const void *x, const void *h_prev, const float *c_prev, const void *packed, const float *bias, const float *dh,
+                              const float *dc, int64_t B, int64_t H, int64_t W, int64_t C, void *dgates, float *dc_prev, void *stream)
+{
+    if (!x || !packed || !bias || !dh || !dgates || !dc_prev) return fail(V2V_ERR_NULL, "v2v_convlstm_step_bwd_hip: x/packed/bias/dh/dgates/dc_prev is NULL");
+    if (B < 1 || H < 1 || W < 1 || C < 64 || C % 64 != 0 || C > 4096 || (H * W) % 4 != 0 || B * H * W * 4 * C > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C %% 64 == 0, C <= 4096, (H*W) %% 4 == 0, tensors below 2^31 elements");
+    if (dgates == x || dgates == h_prev) return fail(V2V_ERR_PARAM, "dgates must not alias x or h_prev (neighbouring tiles read them)");
+    if (!aligned(x, 16) || !aligned(h_prev, 16) || !aligned(packed, 16) || !aligned(c_prev, 4) || !aligned(dh, 4) || !aligned(dc, 4)
+        || !aligned(dgates, 2) || !aligned(dc_prev, 4) || !aligned(bias, 4))
+        return fail(V2V_ERR_ALIGN, "x/h_prev/packed need 16-byte alignment, c_prev/dh/dc/dc_prev/bias 4-byte, dgates 2-byte");
+    v2v::ConvLstmArgs a{};
+    a.x = static_cast<const uint16_t *>(x); a.h_prev = static_cast<const uint16_t *>(h_prev); a.c_prev = c_prev;
+    a.wp = static_cast<const uint16_t *>(packed); a.bias = bias;
+    a.B = (int)B; a.H = (int)H; a.W = (int)W; a.C = (int)C;
+    a.dh = dh; a.dc = dc; a.dgates = static_cast<uint16_t *>(dgates); a.dc_prev = dc_prev;
+    const hipError_t e = v2v::launch_convlstm_step_bwd(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "convlstm_step_kernel (EPI = 2) launch");
+}
+
+int v2v_relu_bwd_nhwc_hip(const void *dy, const void *y, int64_t M, int64_t C, void *out, void *stream)
+{
+    if (!dy || !out) return fail(V2V_ERR_NULL, "v2v_relu_bwd_nhwc_hip: dy/out is NULL");
+    if (M < 1 || C < 8 || C % 8 != 0 || M * C > 0x7FFFFFFFLL) return fail(V2V_ERR_SHAPE, "need M >= 1, C %% 8 == 0, M*C below 2^31");
+    if (!aligned(dy, 16) || !aligned(y, 16) || !aligned(out, 16)) return fail(V2V_ERR_ALIGN, "dy/y/out need 16-byte alignment");
+    const hipError_t e = v2v::launch_relu_mask_stuff(static_cast<const uint16_t *>(dy), static_cast<const uint16_t *>(y), static_cast<uint16_t *>(out),
+                                                     1, 1, (int)M, (int)C, 1, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "relu_mask_stuff_kernel launch");
+}
+
+int64_t v2v_conv_dgrad_packed_elems(int64_t Cin, int64_t Cout, int ks) { return v2v_conv_packed_elems(Cout, Cin, ks); }
+
+int v2v_conv_dgrad_pack_weights_hip(const float *weight, int64_t Cin, int64_t Cout, int ks, float *scratch, void *packed, void *stream)
+{
+    if (!weight || !scratch || !packed) return fail(V2V_ERR_NULL, "v2v_conv_dgrad_pack_weights_hip: weight/scratch/packed is NULL");
+    if ((ks != 3 && ks != 5) || v2v_conv_dgrad_packed_elems(Cin, Cout, ks) < 0)
+        return fail(V2V_ERR_SHAPE, "the transposed convolution (Cout -> Cin, ks 3 or 5) is not a shape the convolution kernel takes");
+    if (!aligned(packed, 16) || !aligned(scratch, 4)) return fail(V2V_ERR_ALIGN, "packed needs 16-byte alignment");
+    const int64_t n = Cout * Cin * ks * ks;
+    hipLaunchKernelGGL(v2v::dgrad_flip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), weight, scratch, (int)Cout,
+                       (int)Cin, ks);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = v2v::launch_conv_pack(scratch, static_cast<uint16_t *>(packed), (int)Cout, (int)Cin, ks, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "dgrad weight packing launch");
+}
+
+// (v2v_conv_dgrad_nhwc_hip itself runs on the forward convolution's instances and lives with them, in v2v_convlstm_tu.hip)
+int64_t v2v_conv_dgrad_workspace_bytes(int64_t B, int64_t Hin, int64_t Win, int64_t Cin, int64_t Cout, int stride)
+{
+    if (B < 1 || Hin < 1 || Win < 1 || Cin < 1 || Cout < 1 || (stride != 1 && stride != 2)) return -1;
+    return (Cin * 4 + 255) / 256 * 256 + (stride == 2 ? B * Hin * Win * Cout * 2 : 0);
+}
+
+int64_t v2v_conv_wgrad_workspace_bytes(int64_t B, int64_t Ho, int64_t Wo, int64_t Cin, int64_t Cout, int ks)
+{
+    if (B < 1 || Ho < 1 || Wo < 1 || Cin < 1 || Cout < 32 || Cout % 32 != 0 || (ks != 1 && ks != 3 && ks != 5)) return -1;
+    const int64_t N = (int64_t)ks * ks * Cin, Npad = (N + 127) / 128 * 128;
+    const int64_t S = v2v::wgrad_slabs(B * Ho * Wo, (int)Cout, N);
+    return S * Cout * (Npad + 1) * 4;
+}
+
+int v2v_conv_wgrad_nhwc_hip(const void *dy, const void *x1, int64_t C1, const void *x2, int64_t C2, int64_t Cin_out, int64_t B, int64_t Hin, int64_t Win,
+                            int64_t Cout, int ks, int stride, void *workspace, float *dw, float *db, void *stream)
+{
+    if (!dy || !x1 || !workspace || !dw) return fail(V2V_ERR_NULL, "v2v_conv_wgrad_nhwc_hip: dy/x1/workspace/dw is NULL");
+    if ((ks != 1 && ks != 3 && ks != 5) || (stride != 1 && stride != 2)) return fail(V2V_ERR_PARAM, "ks must be 1, 3 or 5, stride 1 or 2");
+    const int64_t Ho = (Hin - 1) / stride + 1, Wo = (Win - 1) / stride + 1;
+    if (B < 1 || Hin < 1 || Win < 1 || C1 < 1 || C2 < 0 || Cin_out < 1 || Cin_out > C1 + C2 || Cout < 32 || Cout % 32 != 0
+        || B * Hin * Win * (C1 > C2 ? C1 : C2) > 0x7FFFFFFFLL || B * Ho * Wo * Cout > 0x7FFFFFFFLL || (int64_t)ks * ks * (C1 + C2) > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C1 >= 1, 1 <= Cin_out <= C1 + C2, Cout a multiple of 32, tensors below 2^31 elements");
+    if (!aligned(dy, 2) || !aligned(x1, 2) || !aligned(x2, 2) || !aligned(workspace, 4) || !aligned(dw, 4) || !aligned(db, 4))
+        return fail(V2V_ERR_ALIGN, "buffers misaligned");
+    const hipError_t e = v2v::launch_conv_wgrad(static_cast<const uint16_t *>(dy), static_cast<const uint16_t *>(x1), (int)C1,
+                                                static_cast<const uint16_t *>(x2), (int)C2, (int)Cin_out, dw, db, static_cast<float *>(workspace),
+                                                (int)B, (int)Hin, (int)Win, (int)Ho, (int)Wo, (int)Cout, ks, stride, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv_wgrad_kernel launch");
+}
+
+int v2v_upsample2x_bwd_nhwc_hip(const void *dout, int64_t B, int64_t H, int64_t W, int64_t C, void *dx, void *stream)
+{
+    if (!dout || !dx) return fail(V2V_ERR_NULL, "v2v_upsample2x_bwd_nhwc_hip: dout/dx is NULL");
+    if (B < 1 || H < 1 || W < 1 || C < 8 || C % 8 != 0 || B * 4 * H * W * C > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C %% 8 == 0, tensors below 2^31 elements");
+    if (!aligned(dout, 16) || !aligned(dx, 16)) return fail(V2V_ERR_ALIGN, "dout/dx need 16-byte alignment");
+    const hipError_t e = v2v::launch_upsample2x_cat_bwd(static_cast<const uint16_t *>(dout), static_cast<uint16_t *>(dx), (int)B, (int)H, (int)W, (int)C,
+                                                        0, (int)C, static_cast<hipStream_t>(stream));    // the whole tensor as one slice
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "upsample2x_cat_bwd_kernel launch");
+}
+
+int64_t v2v_conv1x1_bwd_workspace_bytes(int64_t M, int64_t C)
+{
+    if (M < 1 || C < 8 || C > 128 || (C & (C - 1)) != 0) return -1;
+    return v2v::conv1x1_bwd_slabs(M) * (C + 1) * 4;
+}
+
+int v2v_conv1x1_bwd_nhwc_hip(const float *dy, const void *x, const void *skip, const float *weight, int64_t M, int64_t C, void *dx, float *dw, float *db,
+                             void *workspace, void *stream)
+{
+    if (!dy || !x || !weight || !dx || !dw || !db || !workspace) return fail(V2V_ERR_NULL, "v2v_conv1x1_bwd_nhwc_hip: a required pointer is NULL");
+    if (M < 1 || C < 8 || C > 128 || (C & (C - 1)) != 0 || M * C > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need M >= 1 and C a power of two in 8..128 (one output channel)");
+    if (!aligned(dy, 4) || !aligned(x, 16) || !aligned(skip, 16) || !aligned(dx, 16) || !aligned(weight, 4) || !aligned(workspace, 4))
+        return fail(V2V_ERR_ALIGN, "x/skip/dx need 16-byte alignment, dy/weight/workspace 4-byte");
+    const hipError_t e = v2v::launch_conv1x1_bwd_cout(dy, static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(skip), weight,
+                                                      static_cast<uint16_t *>(dx), dw, db, static_cast<float *>(workspace), M, (int)C, 1,
+                                                      static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv1x1_bwd_cout_kernel launch");
+}
+
+// ---- the plain UNet (EVFlowNet): the concat-skip upsampling's adjoint, the prediction backward for 1..3 outputs ------------------------
+int v2v_upsample2x_cat_bwd_nhwc_hip(const void *dout, int64_t B, int64_t H, int64_t W, int64_t Ctot, int64_t c0, int64_t C, void *dx, void *stream)
+{
+    if (!dout || !dx) return fail(V2V_ERR_NULL, "v2v_upsample2x_cat_bwd_nhwc_hip: dout/dx is NULL");
+    if (B < 1 || H < 1 || W < 1 || C < 8 || C % 8 != 0 || Ctot % 8 != 0 || c0 < 0 || c0 % 8 != 0 || c0 + C > Ctot || B * 4 * H * W * Ctot > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need B,H,W >= 1, C, c0 and Ctot multiples of 8, c0 + C <= Ctot, tensors below 2^31 elements");
+    if (!aligned(dout, 16) || !aligned(dx, 16)) return fail(V2V_ERR_ALIGN, "dout/dx need 16-byte alignment");
+    if (dx == dout) return fail(V2V_ERR_PARAM, "dx must not alias dout");
+    const hipError_t e = v2v::launch_upsample2x_cat_bwd(static_cast<const uint16_t *>(dout), static_cast<uint16_t *>(dx), (int)B, (int)H, (int)W, (int)Ctot,
+                                                        (int)c0, (int)C, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "upsample2x_cat_bwd_kernel launch");
+}
+
+int64_t v2v_conv1x1_bwd_cout_workspace_bytes(int64_t M, int64_t C, int64_t Cout)
+{
+    if (M < 1 || C < 8 || C > 128 || (C & (C - 1)) != 0 || Cout < 1 || Cout > 3) return -1;
+    return v2v::conv1x1_bwd_slabs(M) * Cout * (C + 1) * 4;
+}
+
+int v2v_conv1x1_bwd_cout_nhwc_hip(const float *dy, const void *x, const void *skip, const float *weight, int64_t M, int64_t C, int64_t Cout, void *dx,
+                                  float *dw, float *db, void *workspace, void *stream)
+{
+    if (!dy || !x || !weight || !dx || !dw || !db || !workspace) return fail(V2V_ERR_NULL, "v2v_conv1x1_bwd_cout_nhwc_hip: a required pointer is NULL");
+    if (M < 1 || C < 8 || C > 128 || (C & (C - 1)) != 0 || Cout < 1 || Cout > 3 || M * C > 0x7FFFFFFFLL)
+        return fail(V2V_ERR_SHAPE, "need M >= 1, C a power of two in 8..128, Cout 1..3");
+    if (!aligned(dy, 4) || !aligned(x, 16) || !aligned(skip, 16) || !aligned(dx, 16) || !aligned(weight, 4) || !aligned(workspace, 4) || !aligned(dw, 4)
+        || !aligned(db, 4))
+        return fail(V2V_ERR_ALIGN, "x/skip/dx need 16-byte alignment, dy/weight/dw/db/workspace 4-byte");
+    const hipError_t e = v2v::launch_conv1x1_bwd_cout(dy, static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(skip), weight,
+                                                      static_cast<uint16_t *>(dx), dw, db, static_cast<float *>(workspace), M, (int)C, (int)Cout,
+                                                      static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? V2V_OK : hip_fail(e, "conv1x1_bwd_cout_kernel launch");
+}
+
+}  // extern "C"

@@ -645,12 +645,6 @@ def dynconv_nhwc(x, atoms, packed, bias, relu=True):
 
 
 # ---- the dynamic decoder's backward and BatchNorm on batch statistics (kernels: the training section of v2v_amd/csrc/v2v_hyper.hpp) ---------
-def _launch_train(name: str, device, *args) -> None:
-    """_launch for the entry points of v2v_hyper_train_tu.hip, which keep their error text in v2v_hyper_train_last_error."""
-    with torch.cuda.device(device):
-        _lib.check(getattr(_lib.lib(), name)(*args, _lib.stream_ptr()), "v2v_hyper_train_last_error")
-
-
 def pack_dynconv_weights_t(weight):
     """compositional_coefficients float32 [128, 1536, 1, 1] -> the transposed bfloat16 stream dynconv_df_nhwc reads ([1536 feature columns in
     dF's order][128])."""
@@ -658,7 +652,7 @@ def pack_dynconv_weights_t(weight):
     if not weight.is_cuda or weight.dtype != torch.float32 or tuple(weight.shape) != (128, 1536, 1, 1):
         raise ValueError("weight must be a float32 CUDA tensor [128, 1536, 1, 1]")
     packed = torch.empty((128 * 1536,), dtype=torch.bfloat16, device=weight.device)
-    _launch_train("v2v_hyper_dynconv_pack_t_hip", weight.device, _ptr(weight.detach().contiguous()), _ptr(packed))
+    _launch("v2v_hyper_dynconv_pack_t_hip", weight.device, _ptr(weight.detach().contiguous()), _ptr(packed))
     return packed
 
 
@@ -670,7 +664,7 @@ def dynconv_df_nhwc(dz, packed_t):
         raise ValueError("packed_t must be the output of pack_dynconv_weights_t on dz's device")
     b, h, w, _ = dz.shape
     df = torch.empty((b, h, w, 4, 6, 64), dtype=torch.bfloat16, device=dz.device)
-    _launch_train("v2v_hyper_dynconv_df_hip", dz.device, _ptr(dz), _ptr(packed_t), b * h * w, _ptr(df))
+    _launch("v2v_hyper_dynconv_df_hip", dz.device, _ptr(dz), _ptr(packed_t), b * h * w, _ptr(df))
     return df
 
 
@@ -681,7 +675,7 @@ def dynconv_datoms_nhwc(x, df):
     b, h, w, _ = x.shape
     _need("df", df, shape=(b, h, w, 4, 6, 64), device=x.device)
     out = torch.empty((b, h, w, 25, 6), dtype=torch.float32, device=x.device)
-    _launch_train("v2v_hyper_dynconv_datoms_hip", x.device, _ptr(x), _ptr(df), b, h, w, _ptr(out))
+    _launch("v2v_hyper_dynconv_datoms_hip", x.device, _ptr(x), _ptr(df), b, h, w, _ptr(out))
     return out
 
 
@@ -693,7 +687,7 @@ def dynconv_dx_nhwc(atoms, df):
     _need("atoms", atoms, torch.float32, shape=(b, h, w, 25, 6))
     _need("df", df, shape=(b, h, w, 4, 6, 64), device=atoms.device, owner="atoms")
     out = torch.empty((b, h, w, 256), dtype=torch.bfloat16, device=atoms.device)
-    _launch_train("v2v_hyper_dynconv_dx_hip", atoms.device, _ptr(atoms), _ptr(df), b, h, w, _ptr(out))
+    _launch("v2v_hyper_dynconv_dx_hip", atoms.device, _ptr(atoms), _ptr(df), b, h, w, _ptr(out))
     return out
 
 
@@ -707,7 +701,7 @@ def dynconv_wgrad_nhwc(dz, x, atoms):
     ws = _workspace(_lib.lib().v2v_hyper_dynconv_wgrad_workspace_bytes(b, h, w), dz.device)
     dw = torch.empty((128, 1536, 1, 1), dtype=torch.float32, device=dz.device)
     db = torch.empty((128,), dtype=torch.float32, device=dz.device)
-    _launch_train("v2v_hyper_dynconv_wgrad_hip", dz.device, _ptr(dz), _ptr(x), _ptr(atoms), b, h, w, _ptr(ws), _ptr(dw), _ptr(db))
+    _launch("v2v_hyper_dynconv_wgrad_hip", dz.device, _ptr(dz), _ptr(x), _ptr(atoms), b, h, w, _ptr(ws), _ptr(dw), _ptr(db))
     return dw, db
 
 
@@ -716,7 +710,7 @@ def hyper_bn_stats(z, eps: float = 1e-5):
     _need("z", z, dims="[B,h,w,Cs]")
     cs = z.shape[3]
     mean, var, rstd = (torch.empty((cs,), dtype=torch.float32, device=z.device) for _ in range(3))
-    _launch_train("v2v_hyper_bn_stats_hip", z.device, _ptr(z), z.numel() // cs, cs, C.c_float(eps), _ptr(mean), _ptr(var), _ptr(rstd))
+    _launch("v2v_hyper_bn_stats_hip", z.device, _ptr(z), z.numel() // cs, cs, C.c_float(eps), _ptr(mean), _ptr(var), _ptr(rstd))
     return mean, var, rstd
 
 
@@ -732,7 +726,7 @@ def hyper_bn_apply(z, mean, rstd, gamma, beta, tanh: bool):
     _need("z", z, dims="[B,h,w,Cs]")
     cs, cv, g, b = _bn_affine(z, gamma, beta)
     out = torch.empty_like(z)
-    _launch_train("v2v_hyper_bn_apply_hip", z.device, _ptr(z), _ptr(mean), _ptr(rstd), _ptr(g), _ptr(b), z.numel() // cs, cs, cv, int(bool(tanh)), _ptr(out))
+    _launch("v2v_hyper_bn_apply_hip", z.device, _ptr(z), _ptr(mean), _ptr(rstd), _ptr(g), _ptr(b), z.numel() // cs, cs, cv, int(bool(tanh)), _ptr(out))
     return out
 
 
@@ -746,8 +740,8 @@ def hyper_bn_bwd(dy, z, mean, rstd, gamma, beta, tanh: bool):
     _need("dy", dy, dy.dtype, shape=z.shape, device=z.device, owner="z")
     sums = torch.empty((4, cs), dtype=torch.float32, device=z.device)
     dz = torch.empty_like(z)
-    _launch_train("v2v_hyper_bn_bwd_hip", z.device, _ptr(dy), int(dy.dtype == torch.float32), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(g), _ptr(b), z.numel() // cs,
-                  cs, cv, int(bool(tanh)), _ptr(sums), _ptr(dz))
+    _launch("v2v_hyper_bn_bwd_hip", z.device, _ptr(dy), int(dy.dtype == torch.float32), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(g), _ptr(b), z.numel() // cs,
+            cs, cv, int(bool(tanh)), _ptr(sums), _ptr(dz))
     return dz, sums[1, :cv], sums[0, :cv], sums[2, :cv]
 
 
@@ -759,5 +753,5 @@ def hyper_atoms_bwd(datoms, pre, bases):
     _need("datoms", datoms, torch.float32, shape=(b, h, w, 25, 6), device=pre.device, owner="pre")
     _need("bases", bases, torch.float32, shape=(12, 25), device=pre.device, owner="pre")
     out = torch.empty((b, h, w, 128), dtype=torch.float32, device=pre.device)
-    _launch_train("v2v_hyper_atoms_bwd_hip", pre.device, _ptr(datoms), _ptr(pre), _ptr(bases), b * h * w, _ptr(out))
+    _launch("v2v_hyper_atoms_bwd_hip", pre.device, _ptr(datoms), _ptr(pre), _ptr(bases), b * h * w, _ptr(out))
     return out

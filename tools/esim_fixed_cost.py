@@ -1,7 +1,12 @@
 """Fixed (per-launch / per-workgroup) cost of the headline ESIM launch: kernel time for 256 clips x N frames x 256 x 256 float32,
-reference-default parameters, bilinear 5 bins, N = 2 .. 33 -> slope (ms per frame pair) and intercept (prologue + epilogue + stores)."""
+reference-default parameters, bilinear 5 bins, N = 2 .. 33 -> slope (ms per frame pair) and intercept (prologue + epilogue + stores).
+
+    python tools/esim_fixed_cost.py [--lib PATH]     PATH: another build of libv2v_hip.so to time instead of the tree's (same-box A/B)"""
 import os
 import sys
+
+if "--lib" in sys.argv:                                    # before v2v_amd is imported: the binding reads V2V_HIP_LIB once
+    os.environ["V2V_HIP_LIB"] = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
 
 import numpy as np
 import torch

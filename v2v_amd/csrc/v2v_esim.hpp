@@ -170,11 +170,49 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
     int *s_kb = reinterpret_cast<int *>(s_w + 2 * a.K);    // [Tb] first pair index of each bin segment
 
     // ---- workgroup prologue: tables into LDS
+    const int clip = blockIdx.x / a.blocks_per_clip;
+    const int blk = blockIdx.x - clip * a.blocks_per_clip;
+    const uint32_t p0 = (uint32_t)(blk * kBlock + threadIdx.x) * VEC;
+    // ONCE: what is uniform over the clip -- the parameter checks, SYMONLY's promise, the reciprocal threshold -- is worked out once per
+    // workgroup, by the few lanes that fill s_thr, and handed to the work-items as one LDS flag word and one 16-byte LDS read; the
+    // bilinear tables then need a single barrier.  Every work-item used to run a float64 division (~30 vector instructions) and ten
+    // float64 compares on these wave-uniform values: -2.1 % on the headline, -2.0 % on its uint8 twin (profiles/esim_setup/).
+    // (Not in the noise-free instances: memory-bound, they measured 0.8 % SLOWER with it on the same box and keep the per-lane form.)
+    constexpr bool ONCE = NOISE;
+    const double *pp = a.params + (int64_t)clip * a.params_stride;
+    double c_pos, c_neg, base_std = 0.0, hot_frac = 0.0, hot_std = 0.0;
+    uint64_t seed_;
+    uint32_t clip_id;
+    auto read_clip = [&]() {                                   // the clip's parameters and keys (wave-uniform)
+        c_pos = pp[0];
+        c_neg = pp[1];
+        if constexpr (NOISE) { base_std = pp[2]; hot_frac = pp[3]; hot_std = pp[4]; }
+        seed_ = a.clip_keys ? a.clip_keys[2 * clip] : a.seed;
+        clip_id = a.clip_keys ? (uint32_t)a.clip_keys[2 * clip + 1] : (uint32_t)(a.clip_id0 + (uint64_t)clip);
+    };
+    if constexpr (ONCE) read_clip();                           // before anything is written: scalar loads
     if constexpr (ICDF) icdf_to_lds(s_icdf);
-    if (threadIdx.x < 2) {
-        const double c = a.params[(int64_t)(blockIdx.x / a.blocks_per_clip) * a.params_stride + threadIdx.x];
+    __shared__ int s_bad;                                      // ONCE: the clip's flag word
+    if constexpr (ONCE) {
+        if (threadIdx.x < 5) {
+            // parameters the arithmetic below is not exact for (host lists are checked by the callers; a DEVICE-resident [B,5] table -- the
+            // loaders' per-sample draws -- only here): thresholds outside [1e-9, 1e30] (the floor-divide estimate needs |potential| / C < 2^40;
+            // zero, negative and NaN thresholds have no meaning in the reference either), negative or non-finite noise parameters; and
+            // SYMONLY's promise C+ == C-.  The clip comes out as NaN planes + the statistics' flag word (see poison_clip below).
+            const double c = threadIdx.x == 0 ? c_pos : threadIdx.x == 1 ? c_neg : threadIdx.x == 2 ? base_std : threadIdx.x == 3 ? hot_frac : hot_std;
+            bool ok = c >= (threadIdx.x < 2 ? 1e-9 : 0.0) && c <= 1e30;
+            if constexpr (SYMONLY) ok = ok && c_pos == c_neg;
+            const bool any_bad = __builtin_amdgcn_ballot_w64(!ok) != 0;
+            if (threadIdx.x < 2) {
+                s_thr[2 * threadIdx.x] = c;
+                s_thr[2 * threadIdx.x + 1] = (1.0 / c) * 0x1.ffffffffffffcp-1;   // 1/C biased down by 2^-50 so that floor(|p| * inv) never exceeds the true quotient (one-sided correction)
+            }
+            if (threadIdx.x == 0) s_bad = (int)any_bad;
+        }
+    } else if (threadIdx.x < 2) {
+        const double c = pp[threadIdx.x];
         s_thr[2 * threadIdx.x] = c;
-        s_thr[2 * threadIdx.x + 1] = (1.0 / c) * 0x1.ffffffffffffcp-1;       // same expression as inv_pos / inv_neg below
+        s_thr[2 * threadIdx.x + 1] = (1.0 / c) * 0x1.ffffffffffffcp-1;       // same expression as inv_pos below
     }
     if constexpr (IN == kInU8) s_lut[threadIdx.x] = g_lut_esim64[threadIdx.x];
     else s_lut[threadIdx.x] = make_float2(g_lut_esim32[threadIdx.x], (float)threadIdx.x);
@@ -210,8 +248,14 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
             if (b0 > a.Tb - 2) b0 = a.Tb - 2;
             return b0 < 0 ? 0 : b0;
         };
-        for (int b = threadIdx.x; b < a.Tb; b += kBlock) s_kb[b] = 0x7FFFFFFF;
-        __syncthreads();
+        if constexpr (ONCE) {
+            // s_kb[b] = first pair of segment b.  The loop below writes entries 1 .. Tb - 2, each exactly once (seg() runs from 0 at k = 0
+            // to Tb - 2 at k = K - 1 without decreasing); the two it never reaches are set here: no initialising pass, no barrier in between
+            if (threadIdx.x == 0) { s_kb[0] = 0x7FFFFFFF; s_kb[a.Tb - 1] = 0x7FFFFFFF; }
+        } else {
+            for (int b = threadIdx.x; b < a.Tb; b += kBlock) s_kb[b] = 0x7FFFFFFF;
+            __syncthreads();
+        }
         for (int k = threadIdx.x; k < a.K; k += kBlock) {
             const double t_norm = t_of(k);
             const int b0 = seg_of(t_norm);
@@ -227,16 +271,13 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
     if constexpr (FIDX) clip_bad = __syncthreads_or(fidx_bad) != 0;       // every workgroup of the clip stages the same row: all agree
     else __syncthreads();
 
-    const int clip = blockIdx.x / a.blocks_per_clip;
-    const int blk = blockIdx.x - clip * a.blocks_per_clip;
-    const uint32_t p0 = (uint32_t)(blk * kBlock + threadIdx.x) * VEC;
     if (p0 >= (uint32_t)a.HW) return;
     // output planes may be padded (row pitch >= W, plane size >= pitch * H: the consumer's x16 padding written in place); the
     // VEC pixels of a work-item share a row (VEC == 4 needs W % 4 == 0), and a plane is stored a handful of times per clip
     const int64_t pix_off = (a.out_pitch == a.W) ? (int64_t)p0 : (int64_t)(p0 / (uint32_t)a.W) * a.out_pitch + (p0 % (uint32_t)a.W);
 
-    // a clip whose inputs break a promise (V2V_FLAG_SYMMETRIC with C+ != C-; a frame index outside the clip): NaN planes + the
-    // statistics' kStatBad word -- loud, never a wrong count, never an out-of-bounds read
+    // a clip whose inputs break a promise (parameters outside their domain; V2V_FLAG_SYMMETRIC with C+ != C-; a frame index outside the
+    // clip): NaN planes + the statistics' kStatBad word -- loud, never a wrong count, never an out-of-bounds read
     auto poison_clip = [&]() {
         using pacc_t = typename std::conditional<OUT64, double, float>::type;
         pacc_t bad[VEC];
@@ -252,25 +293,21 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
         if (clip_bad) { poison_clip(); return; }                       // workgroup-uniform
     }
 
-    const double *pp = a.params + (int64_t)clip * a.params_stride;
     // symmetric clips keep the threshold and its (slightly low) reciprocal in VGPRs; asymmetric ones read s_thr by polarity.
     // 1/C biased down by 2^-50 so that floor(|p| * inv) never exceeds the true quotient (one-sided correction)
-    double pos = pp[0];
-    double inv_pos = (1.0 / pos) * 0x1.ffffffffffffcp-1;
-    asm volatile("" : "+v"(pos), "+v"(inv_pos));
-    double base_std = 0.0, hot_frac = 0.0, hot_std = 0.0;
-    if constexpr (NOISE) { base_std = pp[2]; hot_frac = pp[3]; hot_std = pp[4]; }
-    // parameters the arithmetic below is not exact for (host lists are checked by the callers; a DEVICE-resident [B,5] table -- the
-    // loaders' per-sample draws -- only here): thresholds outside [1e-9, 1e30] (the floor-divide estimate needs |potential| / C < 2^40;
-    // zero, negative and NaN thresholds have no meaning in the reference either), negative or non-finite noise parameters.  The clip
-    // comes out as NaN planes + the statistics' flag word, like every other broken per-clip promise (clip-uniform branch).
-    {
-        bool ok = pp[0] >= 1e-9 && pp[0] <= 1e30 && pp[1] >= 1e-9 && pp[1] <= 1e30;
-        if constexpr (NOISE) ok = ok && base_std >= 0.0 && base_std <= 1e30 && hot_frac >= 0.0 && hot_frac <= 1e30 && hot_std >= 0.0 && hot_std <= 1e30;
-        if (!ok) { poison_clip(); return; }
+    double pos, inv_pos;
+    if constexpr (ONCE) {
+        if (__builtin_amdgcn_readfirstlane(s_bad) != 0) { poison_clip(); return; }   // clip-uniform
+        pos = s_thr[0];                                                // the same bits by the same expression, computed once
+        inv_pos = s_thr[1];
+    } else {
+        read_clip();
+        pos = c_pos;
+        inv_pos = (1.0 / pos) * 0x1.ffffffffffffcp-1;
+        // (the per-lane form of the checks the ONCE instances make while they fill s_thr; clip-uniform branch)
+        if (!(c_pos >= 1e-9 && c_pos <= 1e30 && c_neg >= 1e-9 && c_neg <= 1e30)) { poison_clip(); return; }
     }
-    const uint64_t seed_ = a.clip_keys ? a.clip_keys[2 * clip] : a.seed;
-    const uint32_t clip_id = a.clip_keys ? (uint32_t)a.clip_keys[2 * clip + 1] : (uint32_t)(a.clip_id0 + (uint64_t)clip);
+    asm volatile("" : "+v"(pos), "+v"(inv_pos));
     // F32W4: addresses = a wave-uniform part (clip, frame / plane: scalar registers) + the lane's own 32-bit byte offset (the C entry
     // bounds H*W and the plane size), so that no 64-bit lane address lives across the time loop (docs/experiments, "scalar-base
     // addresses": timing-neutral by itself; here it is wanted for its registers -- 4 to 6 per instance, what the 4-frame ring was short of)
@@ -301,8 +338,8 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
         }
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            const double scaled = u0[j] * (pp[0] + pp[1]);
-            pot[j] = scaled - pp[1];                                   // v2v_core_esim.py:29
+            const double scaled = u0[j] * (c_pos + c_neg);
+            pot[j] = scaled - c_neg;                                   // v2v_core_esim.py:29
         }
         if constexpr (NOISE) {
 #pragma unroll
@@ -634,12 +671,12 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
         }
     };
     if constexpr (SYMONLY) {
-        if (pp[0] != pp[1]) { poison_clip(); return; }                 // guarantee broken: poison this clip's planes
+        static_assert(!SYMONLY || ONCE, "the flag word carries the C+ == C- promise");   // a broken one poisoned the clip above
         run(std::true_type{});
     } else if constexpr (ASYM4) {
         run(std::false_type{});
     } else {
-        if (pp[0] == pp[1]) run(std::true_type{});                     // wave-uniform (per clip)
+        if (c_pos == c_neg) run(std::true_type{});                     // wave-uniform (per clip)
         else run(std::false_type{});
     }
 

@@ -227,7 +227,11 @@ def v2e_replay_arrays(record, k, hw):
 
 def v2e_voxel(frames, params: V2EParams, luts, *, rng_mode=RNG_PHILOX, seed=0, clip_id0=0, bin_mode=BIN_SUM, num_bins=5,
               frames_per_bin=1, replay=None):
-    """frames [B,N,H,W] uint8 / float32 (integer-valued) -> (float64 voxels, totals[B,2])."""
+    """frames [B,N,H,W] uint8 / float32 -> (float64 voxels, totals[B,2]).
+
+    float32 frames may hold anything: an integer in 0..255 takes the lin_log table entry (golden G1), every other value
+    (non-integer, negative, beyond 255, NaN, infinite) the formula float32(log(float64(x) / 255 + 0.01)) itself.  Totals
+    skip non-finite counts and are otherwise unspecified for clips with non-finite content."""
     frames = np.ascontiguousarray(frames)
     b, n, h, w = frames.shape
     k = n - 1

@@ -24,6 +24,9 @@ int main(void)
     oracle_v2e_params P = {24.0, V2E_SPATIAL_TEMPORAL_INDEPENDENT, 0.5, 0.1, 0.0, 0.1, 30.0, 0.1, 1.0 / 240, 5.0, 0.1, 0.1, 1};
     rc |= oracle_v2e_voxel_clip(v8, ORACLE_IN_U8, N, HW, lutv, &P, ORACLE_RNG_PHILOX, 5, 1, NULL, ORACLE_BIN_SUM, 8, 1, out, totals);
     P.threshold_model = V2E_PN_RELATED;
+    /* arbitrary float32 content: non-integer pixels, NaN, +inf, a negative value and one beyond 255 (the formula branch of lin_log) */
+    v32[3] = 17.25f; v32[HW + 4] = 200.5f; v32[2 * HW + 5] = 0.125f; v32[3 * HW + 7] = NAN; v32[4 * HW + 9] = INFINITY;
+    v32[5 * HW + 11] = -3.0f; v32[6 * HW + 13] = 300.0f;
     rc |= oracle_v2e_voxel_clip(v32, ORACLE_IN_F32, N, HW, lutv, &P, ORACLE_RNG_PHILOX, 5, 1, NULL, ORACLE_BIN_BILINEAR, 5, 1, out, totals);
     int64_t ts[5] = {0, 10, 20, 30, 40}, xs[5] = {0, 1, 2, 3, 9}, ys[5] = {0, 1, 2, 3, 11};
     int8_t ps[5] = {0, 1, 1, 0, 1};

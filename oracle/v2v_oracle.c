@@ -472,10 +472,21 @@ static double shot_sum_value(__int128 s)
     return (double)hi * 4294967296.0 + (double)lo;
 }
 
+/* lin_log of a float32 pixel: the table entry (golden G1) for an integer in 0..255, else the effective formula itself --
+ * float64 log, one float32 rounding (v2e_linlog_direct in oracle/v2v_oracle.py).  No float -> int cast of anything else:
+ * it is undefined for NaN, infinities and values beyond int. */
+static float v2e_linlog_f32(float x, const float *lut)
+{
+    if (x >= 0.0f && x <= 255.0f) { const int xi = (int)x; if ((float)xi == x) return lut[xi]; }
+    return (float)log((double)x / 255 + 0.01);
+}
+
 /*
- * One clip.  frames [N,HW] u8 or f32 (integer-valued).  lut = golden G1 v2e32.  rng: PHILOX or REPLAY.
+ * One clip.  frames [N,HW] u8 or f32 (any float32 content: non-integer, out of 0..255, NaN, infinite).  lut = golden G1
+ * v2e32.  rng: PHILOX or REPLAY.
  * out: SUM -> [K/fpb, HW] ; BILINEAR -> [Tb, HW] (float64).  Follows generate_events (v2v_core_v2e.py:401-553)
  * pixel by pixel with NumPy's dtype promotions made explicit (lp32 / base32 flags, see oracle/v2v_oracle.py).
+ * totals (ON, OFF): a non-finite count adds nothing; totals of clips with non-finite content are otherwise unspecified.
  */
 int oracle_v2e_voxel_clip(const void *frames, int in_dtype, int64_t N, int64_t HW, const float *lut,
                           const oracle_v2e_params *P, int rng_mode, uint64_t seed, uint32_t clip_id,
@@ -525,9 +536,9 @@ int oracle_v2e_voxel_clip(const void *frames, int in_dtype, int64_t N, int64_t H
     for (int64_t p = 0; p < HW; ++p) {
         for (int64_t o = 0; o < n_out; ++o) out[o * HW + p] = 0.0;
         /* frame 0: lp = base = lin_log(frame0) (the low-pass update with delta_time = 0 is the identity) */
-        const int x0 = in_f32 ? (int)f32[p] : (int)f8[p];
-        double lp64 = (double)lut[x0], base64 = lp64;
-        float lp_f = lut[x0], base_f = lp_f;
+        const float log0 = in_f32 ? v2e_linlog_f32(f32[p], lut) : lut[f8[p]];
+        double lp64 = (double)log0, base64 = lp64;
+        float lp_f = log0, base_f = lp_f;
         double pt, nt;
         float nrate;
         if (rng_mode == ORACLE_RNG_PHILOX) {
@@ -544,7 +555,7 @@ int oracle_v2e_voxel_clip(const void *frames, int in_dtype, int64_t N, int64_t H
                 if (rng_mode == ORACLE_RNG_PHILOX) v2e_native_thres(P, seed, clip_id, (uint32_t)(V2E_F_FRAME0 + V2E_F_STRIDE * i), (uint32_t)p, &pt, &nt);
                 else { pt = rp->pos_thres[k * rp->thres_frame_stride + p]; nt = rp->neg_thres[k * rp->thres_frame_stride + p]; }
             }
-            const float log_new = in_f32 ? lut[(int)f32[i * HW + p]] : lut[f8[i * HW + p]];
+            const float log_new = in_f32 ? v2e_linlog_f32(f32[i * HW + p], lut) : lut[f8[i * HW + p]];
             double i01_64 = 0.0; float i01_32 = 0.0f;
             if (in_f32) i01_32 = (f32[i * HW + p] + 20.0f) / 275.0f;
             else i01_64 = v2e_inten01_u8(f8[i * HW + p], P->uint8_wrap);
@@ -592,8 +603,11 @@ int oracle_v2e_voxel_clip(const void *frames, int in_dtype, int64_t N, int64_t H
                     const double f = (P->shot_noise_rate_hz / 2) * dt;
                     /* per pixel: intensity factor x float32 reciprocal threshold (biased low by 2^-22: the same value
                      * that estimates the floor-divide quotient on the device); per frame: nominal threshold x rate scale */
-                    const float scale_p = (float)(f / mean_p) * (float)pos_nominal, scale_n = (float)(f / mean_n) * (float)neg_nominal;
-                    const float fac32 = (float)fac;
+                    /* outside the reference's domain (np.random.poisson raises on a negative or NaN rate: a pixel beyond 346.67, a frame
+                     * whose mean factor is not positive) the native definition is "no shot noise": the factor and the scale clamp at 0 */
+                    const float scale_p = mean_p > 0 ? (float)(f / mean_p) * (float)pos_nominal : 0.0f;
+                    const float scale_n = mean_n > 0 ? (float)(f / mean_n) * (float)neg_nominal : 0.0f;
+                    const float fac32 = fac > 0 ? (float)fac : 0.0f;
                     const float inv_p = (float)((1.0 / pt) * 0x1.fffff8p-1), inv_n = (float)((1.0 / nt) * 0x1.fffff8p-1);
                     const float lam_p = (fac32 * inv_p) * scale_p;
                     const float lam_n = (fac32 * inv_n) * scale_n;
@@ -617,7 +631,8 @@ int oracle_v2e_voxel_clip(const void *frames, int in_dtype, int64_t N, int64_t H
                 base64 = base64 - fneg * nt;
             }
             const double vox = fpos - fneg;
-            on_total += (int64_t)fpos; off_total += (int64_t)fneg;
+            if (isfinite(fpos)) on_total += (int64_t)fpos;
+            if (isfinite(fneg)) off_total += (int64_t)fneg;
             if (bin_mode == ORACLE_BIN_SUM) out[(k / fpb) * HW + p] += vox;
             else for (int b = 0; b < Tb; ++b) { const double c = vox * bil_w(k, K, b, Tb); out[(int64_t)b * HW + p] += c; }
         }

@@ -399,7 +399,9 @@ def v2e_video_to_voxel(video, FPS, threshold_model, thres_mean_mean, thres_mean_
       * refractory_period_s > 0: the reference raises TypeError (np.clip without a_min, :534-537); the intended
         semantics min(count, int(dt/refractory)) is implemented.
       * threshold_model 'spatial_independent_temporal_changing' crashes in the reference (:423-426): rejected.
-    `record` (dict) receives the random fields in draw order, for replay on the GPU."""
+    `record` (dict) receives the random fields in draw order, for replay on the GPU.
+    `rng` may carry an `exp` attribute: the exponential applied to the float32 leak-rate array (:349); default np.exp.
+    The device-native fields need the native expf there (tests/golden/make_goldens.py::g14_v2e_native says why)."""
     if threshold_model not in V2E_MODELS:
         raise ValueError(f"unsupported threshold_model {threshold_model!r}")
     if seed is not None and rng is V2ERng:
@@ -450,7 +452,7 @@ def v2e_video_to_voxel(video, FPS, threshold_model, thres_mean_mean, thres_mean_
                 nt = rng.normal(thres_mean_mean, thres_mean_std, frame.shape)
             pos_thres, neg_thres, pos_pre, neg_pre = clip_thres(pt, nt)
             noise_rate = rng.randn(h, w).astype(np.float32)
-            noise_rate = np.exp(math.log(10) * noise_rate_cov_decades * noise_rate)
+            noise_rate = getattr(rng, "exp", np.exp)(math.log(10) * noise_rate_cov_decades * noise_rate)
             rec["noise_rate"] = noise_rate
             rec["pos_thres"].append(pos_thres)
             rec["neg_thres"].append(neg_thres)

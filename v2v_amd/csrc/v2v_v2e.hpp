@@ -476,8 +476,10 @@ __device__ __forceinline__ void v2e_main_body(const V2eArgs &a, const int clip, 
             const double mean_p = (shot_sum_value(s4, 0) / 1099511627776.0) / (double)a.HW;      // / 2^40: two factors at 2^20
             const double mean_n = (shot_sum_value(s4, 1) / 1099511627776.0) / (double)a.HW;
             const double f = (P.shot_noise_rate_hz / 2) * dt;
-            fc.scale_p = (float)(f / mean_p) * (float)pos_nominal;      // x nominal threshold: the per-pixel factor is 1/threshold
-            fc.scale_n = (float)(f / mean_n) * (float)neg_nominal;
+            // x nominal threshold: the per-pixel factor is 1/threshold.  A frame mean that is not positive (pixels far beyond 255 or not
+            // finite, where the reference's np.random.poisson raises on a negative or NaN rate) gives no shot noise in that frame
+            fc.scale_p = mean_p > 0 ? (float)(f / mean_p) * (float)pos_nominal : 0.0f;
+            fc.scale_n = mean_n > 0 ? (float)(f / mean_n) * (float)neg_nominal : 0.0f;
         }
         fc.cap = refractory ? (double)(int)(dt / P.refractory_period_s) : 0.0;
         s_fc[k] = fc;
@@ -630,7 +632,7 @@ __device__ __forceinline__ void v2e_main_body(const V2eArgs &a, const int clip, 
                         double fac;
                         log_new[j] = v2e_linlog(x[j], a.lut);
                         v2e_inten_direct<IN>(x[j], P.uint8_wrap, i01_64[j], i01_32[j], fac);
-                        fac32[j] = (float)fac;
+                        fac32[j] = fac > 0 ? (float)fac : 0.0f;                                  // a rate is never negative: no shot noise beyond x = 346.67 (or NaN)
                         if constexpr (LP_TAB) {                                                  // (E1, E2) of a pixel outside the table
                             float eps = i01_32[j] * dt_tau32;
                             eps = __builtin_fminf(eps, 1.0f);
@@ -765,8 +767,10 @@ __device__ __forceinline__ void v2e_main_body(const V2eArgs &a, const int clip, 
                 const double neg_frame = nd > 0 ? nd : (nd == nd ? 0.0 : nd);
                 fpos[j] = floor(pos_frame * (double)inv_p[j]);
                 fneg[j] = floor(neg_frame * (double)inv_n[j]);
-                { const double r = __builtin_fma(-fpos[j], pt[j], pos_frame); if (r >= pt[j]) fpos[j] += 1.0; else if (!(r < pt[j])) fpos[j] = pos_frame / pt[j]; }
-                { const double r = __builtin_fma(-fneg[j], nt[j], neg_frame); if (r >= nt[j]) fneg[j] += 1.0; else if (!(r < nt[j])) fneg[j] = neg_frame / nt[j]; }
+                // a NaN residual: the potential or the threshold is not finite.  x - x is 0 for a finite potential (the plain quotient stands: 0 for
+                // an infinite threshold) and NaN for an infinite one -- np.floor_divide(inf, t) is NaN (its fmod is), not inf / t
+                { const double r = __builtin_fma(-fpos[j], pt[j], pos_frame); if (r >= pt[j]) fpos[j] += 1.0; else if (!(r < pt[j])) fpos[j] = pos_frame / pt[j] + (pos_frame - pos_frame); }
+                { const double r = __builtin_fma(-fneg[j], nt[j], neg_frame); if (r >= nt[j]) fneg[j] += 1.0; else if (!(r < nt[j])) fneg[j] = neg_frame / nt[j] + (neg_frame - neg_frame); }
                 fpos[j] = fpos[j] + (double)cnt_p[j];
                 fneg[j] = fneg[j] + (double)cnt_n[j];
             }

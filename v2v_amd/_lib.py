@@ -189,6 +189,16 @@ SIGNATURES = {
 }
 EXPORTS = tuple(SIGNATURES)
 
+# include/v2v_nernet.h: NER-Net's learned voxelisation (v2v_amd/nernet.py).  A table of its own, as the header is: SIGNATURES / EXPORTS
+# mirror include/v2v_hip.h entry by entry.
+NERNET_SIGNATURES = {
+    "v2v_learned_voxel_packed_elems": (I64, [P, I]),
+    "v2v_learned_voxel_workspace_bytes": (I64, [I64, I64]),
+    "v2v_learned_voxel_stats_hip": (I, [P, I, I64, P, I64, I64, P, P]),
+    "v2v_learned_voxel_hip": (I, [P, I, I64, P, I64, I64, I, I64, I64, P, P, I, F, I, I, P, P, P, P]),
+}
+NERNET_EXPORTS = tuple(NERNET_SIGNATURES)
+
 _lib = None
 
 
@@ -201,7 +211,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C v2v_amd/csrc`).  v2v_amd has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(NERNET_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     if L.v2v_version() != ABI_VERSION:

@@ -92,8 +92,10 @@ class TestH5Dataset(torch.utils.data.Dataset, voxel.MakeVoxelMixin):
 
 class TestH5EventDataset(TestH5Dataset):
     """data/testh5.py:305-381: the same samples, but `events` is the list of RAW event rows per image interval -- float64 [n,5] =
-    [x, y, t, p in {-1,+1}, 0] (one [1,5] row of zeros for an empty interval) -- instead of voxel grids.  No voxelisation, so no device
-    work: host IO only.  (`output_additional_evs` is not read by the reference's method either.)"""
+    [x, y, t, p in {-1,+1}, 0] (one [1,5] row of zeros for an empty interval) -- instead of voxel grids.  No voxelisation here, so no device
+    work in the dataset: host IO only.  The consumer of these rows is NER-Net's learned voxelisation, `v2v_amd.nernet.Voxelization`
+    (`forward_sequence(sample["events"])` takes the whole list in one upload and one launch pair).  (`output_additional_evs` is not read
+    by the reference's method either.)"""
     __test__ = False
 
     def __getitem__(self, idx):

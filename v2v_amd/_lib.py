@@ -199,6 +199,15 @@ NERNET_SIGNATURES = {
 }
 NERNET_EXPORTS = tuple(NERNET_SIGNATURES)
 
+# include/v2v_metrics.h: the evaluation metrics (v2v_amd/metrics.py), a table of its own for the same reason.
+METRICS_SIGNATURES = {
+    "v2v_image_metrics_workspace_bytes": (I64, [I64, I64, I64]),
+    "v2v_image_metrics_hip": (I, [P, I64, P, I64, I64, I64, I64, F, C.c_double, P, P, P, P]),
+    "v2v_flow_metrics_workspace_bytes": (I64, [I64, I64, I64]),
+    "v2v_flow_metrics_hip": (I, [P, I64, P, I64, P, I64, I64, I64, I64, I64, P, P, P, P]),
+}
+METRICS_EXPORTS = tuple(METRICS_SIGNATURES)
+
 _lib = None
 
 
@@ -211,7 +220,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C v2v_amd/csrc`).  v2v_amd has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(NERNET_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(NERNET_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     if L.v2v_version() != ABI_VERSION:

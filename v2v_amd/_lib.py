@@ -1,4 +1,15 @@
-"""ctypes binding of libv2v_hip.so (C ABI in include/v2v_hip.h).  Fails loudly when the library is missing."""
+"""ctypes binding of libv2v_hip.so (C ABI in include/v2v_hip.h, v2v_nernet.h, v2v_metrics.h) and the one calling convention every module
+of the package goes through.  Fails loudly when the library is missing.
+
+    lib()                          the loaded library, one binding table per header (SIGNATURES, NERNET_SIGNATURES, METRICS_SIGNATURES)
+    ptr(t, offset_elems=0)         the address of a tensor as a C pointer argument, None -> NULL
+    launch(name, device, *args)    the `_hip` entry point `name` on `device` and torch's current stream there, the stream last, status checked
+    need(name, t, dtype, ...)      ValueError unless t is a contiguous CUDA tensor of that dtype and shape
+    DTYPE_CODES                    torch dtype -> the dtype code of include/v2v_hip.h
+    check(rc) / require_gpu()      status -> exception; the RuntimeError every compute call raises first without a GPU
+
+Size queries (`*_bytes`, `*_elems`) take no stream and stay direct calls on lib().
+"""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,6 +22,7 @@ LIB_PATH = os.environ.get("V2V_HIP_LIB") or os.path.join(_HERE, "libv2v_hip.so")
 
 # enums of include/v2v_hip.h
 U8, F32, F64, BF16 = 0, 1, 2, 3
+DTYPE_CODES = {torch.uint8: U8, torch.float32: F32, torch.float64: F64, torch.bfloat16: BF16}   # a call site rejects what it does not take
 RNG_NONE, RNG_PHILOX, RNG_REPLAY, RNG_PHILOX_FAST = 0, 1, 2, 3
 BIN_SUM, BIN_BILINEAR = 0, 1
 FLAG_NOISE_EXTERNAL = 0x1
@@ -248,3 +260,28 @@ def require_gpu():
 
 def stream_ptr():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def ptr(t, offset_elems=0):
+    """The address of tensor t (`offset_elems` elements in) as a pointer argument; None gives NULL.  CUDA and page-locked host tensors alike;
+    the address is taken as it is (whether an empty tensor stands for NULL is the call site's to say)."""
+    if t is None:
+        return None
+    return C.c_void_p(t.data_ptr() + offset_elems * t.element_size()) if offset_elems else C.c_void_p(t.data_ptr())
+
+
+def launch(name: str, device, *args) -> None:
+    """The C entry point `name` on `device` and torch's current stream there: lib().<name>(*args, stream), status checked."""
+    with torch.cuda.device(device):
+        check(getattr(lib(), name)(*args, stream_ptr()))
+
+
+def need(name: str, t, dtype=torch.bfloat16, dims: str = "[B,H,W,C]", shape=None, last=None, device=None, owner: str = "x"):
+    """ValueError unless t is a contiguous CUDA tensor of `dtype`: 4-D, or of exactly `shape` when given; with `last` channels and on
+    `device` (the device of the operand called `owner`) when given.  -> t"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() \
+            or (t.dim() != 4 if shape is None else tuple(t.shape) != tuple(shape)) \
+            or (last is not None and t.shape[3] != last) or (device is not None and t.device != device):
+        where = f" on {owner}'s device" if device is not None else ""
+        raise ValueError(f"{name} must be a contiguous {str(dtype)[6:]} CUDA tensor {list(shape) if shape is not None else dims}{where}")
+    return t

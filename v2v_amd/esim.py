@@ -13,12 +13,22 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import DTYPE_CODES, launch, ptr
 
-_TORCH_IN = {torch.uint8: _lib.U8, torch.float32: _lib.F32}
-_OUT = {torch.float32: _lib.F32, torch.float64: _lib.F64}
+_TORCH_IN = (torch.uint8, torch.float32)        # frame dtypes the simulators read
+_OUT = (torch.float32, torch.float64)           # voxel-grid dtypes they write
 DEFAULT_MAPPING = "auto"        # work-item mapping of esim_voxel_batch when the caller does not pin it
 BIN_MODES = {"sum": _lib.BIN_SUM, "bilinear": _lib.BIN_BILINEAR}
 RNG_MODES = {"none": _lib.RNG_NONE, "philox": _lib.RNG_PHILOX, "replay": _lib.RNG_REPLAY, "philox_fast": _lib.RNG_PHILOX_FAST}
+MAPPING_FLAGS = {"auto": 0, "4px": _lib.FLAG_MAP_4PX, "2px": _lib.FLAG_MAP_2PX, "1px": _lib.FLAG_MAP_1PX}
+
+
+def _code(allowed, dtype):
+    """The dtype code of one of `allowed`.  Any other dtype raises KeyError, the exception the private dictionaries gave when a call site
+    indexed them with a caller's dtype (`out_dtype` of the simulators, `dtype` of synth_clips, both of algorithmic_bytes): kept as it was."""
+    if dtype not in allowed:
+        raise KeyError(dtype)
+    return DTYPE_CODES[dtype]
 
 
 def _params_tensor(params, batch: int, device):
@@ -133,20 +143,17 @@ def esim_voxel_batch(frames: torch.Tensor, params, *, bin_mode: str = "sum", num
     if stats is not None:
         if stats.dtype != torch.int32 or tuple(stats.shape) != (b, _lib.VOXEL_STATS_WORDS) or not stats.is_contiguous() or stats.device != frames.device:
             raise ValueError(f"stats must be a contiguous int32 [{b},{_lib.VOXEL_STATS_WORDS}] tensor on the frames' device")
-    fn = _lib.lib().v2v_esim_voxel_padded_hip if stats is None else _lib.lib().v2v_esim_voxel_stats_hip
-    extra = () if stats is None else (C.c_void_p(stats.data_ptr()),)
-    with torch.cuda.device(frames.device):
-        rc = fn(
-            C.c_void_p(frames.data_ptr()), _TORCH_IN[frames.dtype], b, n, h, w,
-            frames.stride(0) if b > 1 else n * frames.stride(1), frames.stride(1),
-            C.c_void_p(p.data_ptr()), pstride,
-            (_lib.FLAG_NOISE_EXTERNAL if put_noise_external else 0) | (_lib.FLAG_NO_NOISE if no_noise else 0) | (_lib.FLAG_SYMMETRIC if symmetric else 0) | {"auto": 0, "4px": _lib.FLAG_MAP_4PX, "2px": _lib.FLAG_MAP_2PX, "1px": _lib.FLAG_MAP_1PX}[mapping or DEFAULT_MAPPING],
-            RNG_MODES[rng_mode], C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint64(clip_id0),
-            C.c_void_p(clip_keys.data_ptr()) if clip_keys is not None else None,
-            C.byref(rp) if rp is not None else None, BIN_MODES[bin_mode], num_bins, frames_per_bin,
-            C.c_void_p(out.data_ptr()), _OUT[out.dtype], wp, hp * wp,
-            C.c_void_p(counts.data_ptr()) if counts is not None else None, *extra, _lib.stream_ptr())
-    _lib.check(rc)
+    extra = () if stats is None else (ptr(stats),)
+    launch("v2v_esim_voxel_padded_hip" if stats is None else "v2v_esim_voxel_stats_hip", frames.device,
+           ptr(frames), DTYPE_CODES[frames.dtype], b, n, h, w,
+           frames.stride(0) if b > 1 else n * frames.stride(1), frames.stride(1),
+           ptr(p), pstride,
+           (_lib.FLAG_NOISE_EXTERNAL if put_noise_external else 0) | (_lib.FLAG_NO_NOISE if no_noise else 0) | (_lib.FLAG_SYMMETRIC if symmetric else 0) | MAPPING_FLAGS[mapping or DEFAULT_MAPPING],
+           RNG_MODES[rng_mode], C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint64(clip_id0),
+           ptr(clip_keys),
+           C.byref(rp) if rp is not None else None, BIN_MODES[bin_mode], num_bins, frames_per_bin,
+           ptr(out), _code(_OUT, out.dtype), wp, hp * wp,
+           ptr(counts), *extra)
     # The launch is asynchronous: PyTorch's caching allocator keeps freed blocks stream-ordered, so dropping
     # p / keep here is safe for work queued on the same stream.
     return out
@@ -186,21 +193,19 @@ def esim_voxel_packed(frames: torch.Tensor, clip_offsets: torch.Tensor, frame_in
         raise ValueError(f"stored_frames must be a contiguous int32 [{b}] tensor on {dev}")
     ex = _lib.EsimExtras(stats.data_ptr() if stats is not None else None, frame_index.data_ptr(), clip_offsets.data_ptr(),
                          stored_frames.data_ptr() if stored_frames is not None else None, frames.numel() if stored_frames is not None else 0)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().v2v_esim_voxel_ex_hip(
-            C.c_void_p(frames.data_ptr()), _lib.U8, b, n, h, w, align, h * w, C.c_void_p(params.data_ptr()), 5,
-            {"auto": 0, "4px": _lib.FLAG_MAP_4PX, "2px": _lib.FLAG_MAP_2PX, "1px": _lib.FLAG_MAP_1PX}[mapping or DEFAULT_MAPPING],
-            _lib.RNG_PHILOX, C.c_uint64(0), C.c_uint64(0), C.c_void_p(clip_keys.data_ptr()), None, _lib.BIN_SUM, num_bins, frames_per_bin,
-            C.c_void_p(out.data_ptr()), _lib.F32, wp, hp * wp, None, C.byref(ex), _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_esim_voxel_ex_hip", dev,
+           ptr(frames), _lib.U8, b, n, h, w, align, h * w, ptr(params), 5,
+           MAPPING_FLAGS[mapping or DEFAULT_MAPPING],
+           _lib.RNG_PHILOX, C.c_uint64(0), C.c_uint64(0), ptr(clip_keys), None, _lib.BIN_SUM, num_bins, frames_per_bin,
+           ptr(out), _lib.F32, wp, hp * wp, None, C.byref(ex))
     return out
 
 
 def algorithmic_bytes(frames_dtype: torch.dtype, b: int, n: int, h: int, w: int, bin_mode: str, num_bins: int,
                       frames_per_bin: int = 1, out_dtype: torch.dtype = torch.float32) -> int:
     """HBM bytes one launch must move: every input byte read once + every voxel byte written once."""
-    v = _lib.lib().v2v_esim_voxel_bytes(_TORCH_IN[frames_dtype], b, n, h, w, BIN_MODES[bin_mode], num_bins,
-                                        frames_per_bin, _OUT[out_dtype])
+    v = _lib.lib().v2v_esim_voxel_bytes(_code(_TORCH_IN, frames_dtype), b, n, h, w, BIN_MODES[bin_mode], num_bins,
+                                        frames_per_bin, _code(_OUT, out_dtype))
     if v < 0:
         _lib.check(int(v))
     return int(v)
@@ -211,10 +216,7 @@ def synth_clips(b: int, n: int, h: int, w: int, *, dtype: torch.dtype = torch.fl
     """Device-generated synthetic clips: integer-valued 0..255, [B,N,H,W]."""
     _lib.require_gpu()
     out = torch.empty((b, n, h, w), dtype=dtype, device=device)
-    with torch.cuda.device(out.device):
-        rc = _lib.lib().v2v_synth_clips_hip(C.c_void_p(out.data_ptr()), _TORCH_IN[dtype], b, n, h, w,
-                                            C.c_uint64(seed), C.c_uint64(clip_id0), _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_synth_clips_hip", out.device, ptr(out), _code(_TORCH_IN, dtype), b, n, h, w, C.c_uint64(seed), C.c_uint64(clip_id0))
     return out
 
 

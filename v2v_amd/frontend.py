@@ -9,12 +9,11 @@ OpenCV >= 4.0 uses -- what the reference's unpinned `opencv-python` installs) or
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._lib import launch, ptr
 
 GRAY_VERSIONS = {"cv4": 1, "cv3": 2}       # C ABI gray_first: BGR2GRAY as OpenCV >= 4.0 (15-bit weights) / as 2.x-3.x (14-bit)
 
@@ -46,13 +45,8 @@ def prepare_clip(raw: torch.Tensor, crop_before: int, min_i: int, min_j: int, fl
     cout = 1 if (gray_first or cs == 1) else 3
     imgs = torch.empty((n, crop_size, crop_size, cout), dtype=torch.uint8, device=dev) if want_imgs else None
     gray = torch.empty((n, crop_size, crop_size), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().v2v_frontend_hip(
-            C.c_void_p(raw.data_ptr()), t, hs, ws, cs, min_i, min_j, crop_before, need_h, need_w, crop_size, int(bool(flip)),
-            int(gray_first), C.c_void_p(idx.data_ptr()), n, C.c_void_p(di.data_ptr()) if di is not None else None,
-            C.c_void_p(dj.data_ptr()) if dj is not None else None, C.c_void_p(imgs.data_ptr()) if imgs is not None else None,
-            C.c_void_p(gray.data_ptr()), _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_frontend_hip", dev, ptr(raw), t, hs, ws, cs, min_i, min_j, crop_before, need_h, need_w, crop_size, int(bool(flip)),
+           int(gray_first), ptr(idx), n, ptr(di), ptr(dj), ptr(imgs), ptr(gray))
     return imgs, gray
 
 
@@ -100,10 +94,6 @@ def prepare_clips_batch(raw: torch.Tensor, clip_table, img_idxes, crop_size: int
     cout = 1 if (gray_first or cs == 1) else 3
     imgs = torch.empty((b, n, crop_size, crop_size, cout), dtype=torch.uint8, device=dev) if want_imgs else None
     gray = torch.empty((b, n, crop_size, crop_size), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().v2v_frontend_batch_hip(C.c_void_p(raw.data_ptr()), b, t, hs, ws, cs, C.c_void_p(tab.data_ptr()), int(max_crop_before), crop_size,
-                                               int(gray_first), C.c_void_p(idx.data_ptr()), n,
-                                               C.c_void_p(imgs.data_ptr()) if imgs is not None else None,
-                                               C.c_void_p(gray.data_ptr()), _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_frontend_batch_hip", dev, ptr(raw), b, t, hs, ws, cs, ptr(tab), int(max_crop_before), crop_size,
+           int(gray_first), ptr(idx), n, ptr(imgs), ptr(gray))
     return imgs, gray

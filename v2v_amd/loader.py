@@ -24,7 +24,6 @@ Every sample gets exactly what WebvidDatasetV2.__getitem__ / SimulatingCollator 
 """
 from __future__ import annotations
 
-import ctypes as C
 import mmap
 import time
 
@@ -33,6 +32,7 @@ import torch
 from torch.utils.data import BatchSampler, ConcatDataset, DataLoader, RandomSampler, SequentialSampler
 
 from . import _lib, esim
+from ._lib import launch, ptr
 
 _PARAM_KEYS = ("pos_thres", "neg_thres", "base_noise_std", "hot_pixel_fraction", "hot_pixel_std")
 
@@ -57,11 +57,8 @@ def clip_frames_f32(src: torch.Tensor, pick=None, frames: int | None = None) -> 
     out = torch.empty((b, n_l, c, h, w), dtype=torch.float32, device=src.device)
     if b == 0 or n_l == 0:
         return out
-    with torch.cuda.device(src.device):
-        rc = _lib.lib().v2v_clip_frames_f32_hip(C.c_void_p(src.data_ptr()), src.stride(0) if b > 1 else t * src.stride(1), src.stride(1),
-                                                C.c_void_p(pick.data_ptr()) if pick is not None else None, b, n_l, h, w, c,
-                                                C.c_void_p(out.data_ptr()), _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_clip_frames_f32_hip", src.device, ptr(src), src.stride(0) if b > 1 else t * src.stride(1), src.stride(1), ptr(pick), b, n_l, h, w, c,
+           ptr(out))
     return out
 
 
@@ -75,13 +72,8 @@ def clip_frames_packed(clips: torch.Tensor, clip_offsets: torch.Tensor, pick: to
     out = torch.empty((b, n_l, 1, h, w), dtype=torch.float32, device=clips.device)
     if b == 0 or n_l == 0:
         return out
-    with torch.cuda.device(clips.device):
-        rc = _lib.lib().v2v_clip_frames_f32_bounded_hip(C.c_void_p(clips.data_ptr()), align, C.c_void_p(clip_offsets.data_ptr()), h * w,
-                                                        C.c_void_p(pick.data_ptr()), n_l,
-                                                        C.c_void_p(stored_frames.data_ptr()) if stored_frames is not None else None,
-                                                        clips.numel() if stored_frames is not None else 0,
-                                                        b, n_l, h, w, 1, C.c_void_p(out.data_ptr()), _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_clip_frames_f32_bounded_hip", clips.device, ptr(clips), align, ptr(clip_offsets), h * w, ptr(pick), n_l,
+           ptr(stored_frames), clips.numel() if stored_frames is not None else 0, b, n_l, h, w, 1, ptr(out))
     return out
 
 

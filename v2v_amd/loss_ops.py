@@ -15,18 +15,14 @@ Everything but LPIPS' bf16 activations is float32 (other dtypes are widened), on
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._lib import DTYPE_CODES, launch, need, ptr
+from .nhwc_ops import _DTYPES
 
 TC, L1, L2 = 0, 1, 2
 MAPS = ("image0_warped_to1", "processed0_warped_to1", "visibility_mask", "error_map")
-
-
-def _ptr(t, offset_elems=0):
-    return C.c_void_p(t.data_ptr() + 4 * offset_elems) if t is not None else None
 
 
 def _f32(name, t, shape=None):
@@ -60,8 +56,7 @@ def warp_bilinear(img: torch.Tensor, flow: torch.Tensor) -> torch.Tensor:
     n, c, h, w = img.shape
     img, flow = _f32("img", img), _f32("flow", flow, (n, 2, h, w))
     out = torch.empty_like(img)
-    with torch.cuda.device(img.device):
-        _lib.check(_lib.lib().v2v_warp_bilinear_hip(_ptr(img), _ptr(flow), n, c, h, w, _ptr(out), _lib.stream_ptr()))
+    launch("v2v_warp_bilinear_hip", img.device, ptr(img), ptr(flow), n, c, h, w, ptr(out))
     return out
 
 
@@ -76,8 +71,7 @@ def warp_bilinear_adjoint(dout: torch.Tensor, flow: torch.Tensor, hw=None) -> to
     dout, flow = _f32("dout", dout), _f32("flow", flow, (n, 2, h, w))
     din = torch.empty_like(dout)
     ws = _workspace(n, c, h, w, True, dout.device)
-    with torch.cuda.device(dout.device):
-        _lib.check(_lib.lib().v2v_warp_bilinear_adjoint_hip(_ptr(dout), _ptr(flow), n, c, h, w, _ptr(din), _ptr(ws), _lib.stream_ptr()))
+    launch("v2v_warp_bilinear_adjoint_hip", dout.device, ptr(dout), ptr(flow), n, c, h, w, ptr(din), ptr(ws))
     return din
 
 
@@ -106,9 +100,8 @@ def tc_loss_fwd(image0, image1, processed0, processed1, flow, alpha=50.0, weight
     losses = torch.empty((3, n), dtype=torch.float32, device=dev)
     maps = tuple(torch.empty((n, c, h, w), dtype=torch.float32, device=dev) for _ in MAPS) if output_images else (None,) * 4
     ws = _workspace(n, c, h, w, False, dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().v2v_tc_loss_fwd_hip(_ptr(image0), _ptr(image1), _ptr(processed0), _ptr(processed1), _ptr(flow), n, 1, c * h * w, 0, 2 * h * w, 0,
-                                                  0, c, h, w, alpha, flow_sign, *weights, _ptr(losses), *(_ptr(m) for m in maps), _ptr(ws), _lib.stream_ptr()))
+    launch("v2v_tc_loss_fwd_hip", dev, ptr(image0), ptr(image1), ptr(processed0), ptr(processed1), ptr(flow), n, 1, c * h * w, 0, 2 * h * w, 0,
+           0, c, h, w, alpha, flow_sign, *weights, ptr(losses), *(ptr(m) for m in maps), ptr(ws))
     return (losses, maps) if output_images else losses
 
 
@@ -121,9 +114,8 @@ def tc_loss_bwd(image0, image1, processed0, processed1, flow, gout, alpha=50.0, 
     d1 = torch.empty_like(processed1)
     d0 = torch.empty_like(processed1) if weights[TC] != 0.0 else None
     ws = _workspace(n, c, h, w, True, d1.device)
-    with torch.cuda.device(d1.device):
-        _lib.check(_lib.lib().v2v_tc_loss_bwd_hip(_ptr(image0), _ptr(image1), _ptr(processed0), _ptr(processed1), _ptr(flow), n, 1, c * h * w, 0, 2 * h * w, 0,
-                                                  0, c, h, w, alpha, flow_sign, *weights, _ptr(gout), 0, _ptr(d1), _ptr(d0), _ptr(ws), _lib.stream_ptr()))
+    launch("v2v_tc_loss_bwd_hip", d1.device, ptr(image0), ptr(image1), ptr(processed0), ptr(processed1), ptr(flow), n, 1, c * h * w, 0, 2 * h * w, 0,
+           0, c, h, w, alpha, flow_sign, *weights, ptr(gout), 0, ptr(d1), ptr(d0), ptr(ws))
     return d0, d1
 
 
@@ -140,8 +132,8 @@ def _seq_inputs(pred, frame, flow, L0, weights):
     flow = _f32("flow", flow, (b, t, 2, h, w)) if tc else None
     chw = c * h * w
     # image0 / processed0 / flow start at the first step that has a temporal term: frame and pred one step earlier, the flow of step L0
-    ptrs = (_ptr(frame, (L0 - 1) * chw) if tc else None, _ptr(frame), _ptr(pred, (L0 - 1) * chw) if tc else None, _ptr(pred),
-            _ptr(flow, L0 * 2 * h * w) if tc else None)
+    ptrs = (ptr(frame, (L0 - 1) * chw) if tc else None, ptr(frame), ptr(pred, (L0 - 1) * chw) if tc else None, ptr(pred),
+            ptr(flow, L0 * 2 * h * w) if tc else None)
     layout = (b, t, t * chw, chw, t * 2 * h * w, 2 * h * w, L0, c, h, w)
     return pred, frame, flow, ptrs, layout
 
@@ -155,8 +147,7 @@ def seq_loss_fwd(pred, frame, flow, L0, alpha=50.0, weights=(1.0, 1.0, 0.0)):
     b, t, c, h, w = pred.shape
     losses = torch.empty((3, b, t), dtype=torch.float32, device=pred.device)
     ws = _workspace(b * t, c, h, w, False, pred.device)
-    with torch.cuda.device(pred.device):
-        _lib.check(_lib.lib().v2v_tc_loss_fwd_hip(*ptrs, *layout, alpha, -1.0, *weights, _ptr(losses), None, None, None, None, _ptr(ws), _lib.stream_ptr()))
+    launch("v2v_tc_loss_fwd_hip", pred.device, *ptrs, *layout, alpha, -1.0, *weights, ptr(losses), None, None, None, None, ptr(ws))
     return losses
 
 
@@ -170,8 +161,7 @@ def seq_loss_bwd(pred, frame, flow, L0, gout, alpha=50.0, weights=(1.0, 1.0, 0.0
     gout = _f32("gout", gout, (3, b, t))
     dpred = torch.empty_like(pred)
     ws = _workspace(b * t, c, h, w, True, pred.device)
-    with torch.cuda.device(pred.device):
-        _lib.check(_lib.lib().v2v_tc_loss_bwd_hip(*ptrs, *layout, alpha, -1.0, *weights, _ptr(gout), 1, _ptr(dpred), None, _ptr(ws), _lib.stream_ptr()))
+    launch("v2v_tc_loss_bwd_hip", pred.device, *ptrs, *layout, alpha, -1.0, *weights, ptr(gout), 1, ptr(dpred), None, ptr(ws))
     return dpred
 
 
@@ -240,26 +230,6 @@ def sequence_losses(pred, frame, flow, l1_weight, l2_weight, temporal_consistenc
 
 
 # ---- LPIPS-VGG: the raw operators around the backbone's convolutions (v2v_amd/csrc/v2v_lpips.hpp; the network is v2v_amd/lpips.py) -----------
-_LP_DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _lp_launch(name, device, *args):
-    with torch.cuda.device(device):
-        _lib.check(getattr(_lib.lib(), name)(*args, _lib.stream_ptr()))
-
-
-def _lp_act(name, t, shape=None):
-    """t must be a contiguous bfloat16 CUDA tensor [B,H,W,C] (of exactly `shape` when given)."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 4 or not t.is_contiguous() \
-            or (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise ValueError(f"{name} must be a contiguous bfloat16 CUDA tensor {list(shape) if shape is not None else '[B,H,W,C]'}")
-    return t
-
-
 def _lp_vec(name, t, n, device):
     """t as a contiguous float32 vector of n elements on `device` (a [1,3,1,1] buffer or a [1,C,1,1] weight is fine)."""
     if not isinstance(t, torch.Tensor) or t.numel() != n or t.device != device:
@@ -271,28 +241,28 @@ def lpips_stem(x, weight, bias, shift, scale, normalize=False, out=None):
     """x float32 / bfloat16 [B,1|3,H,W] -> bfloat16 [B,H,W,64] = relu(conv3x3(((2x - 1 if normalize else x) - shift_c) / scale_c) + bias), zero
     padding AFTER the scaling; weight float32 [64,3,3,3] (a one-channel x stands for three equal channels).  out: write into this tensor."""
     _lib.require_gpu()
-    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in _LP_DTYPES or x.dim() != 4 or x.shape[1] not in (1, 3):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in _DTYPES or x.dim() != 4 or x.shape[1] not in (1, 3):
         raise ValueError("x must be a float32 or bfloat16 CUDA tensor [B,1|3,H,W]")
     x = x.detach().contiguous()
     b, cin, h, w = x.shape
     if weight.dtype != torch.float32 or tuple(weight.shape) != (64, 3, 3, 3) or weight.device != x.device:
         raise ValueError("weight must be float32 [64,3,3,3] on x's device")
-    out = torch.empty((b, h, w, 64), dtype=torch.bfloat16, device=x.device) if out is None else _lp_act("out", out, (b, h, w, 64))
-    _lp_launch("v2v_lpips_stem_hip", x.device, _p(x), _LP_DTYPES[x.dtype], b, cin, h, w, _p(weight.detach().contiguous()), _p(_lp_vec("bias", bias, 64, x.device)),
-               _p(_lp_vec("shift", shift, 3, x.device)), _p(_lp_vec("scale", scale, 3, x.device)), int(bool(normalize)), _p(out))
+    out = torch.empty((b, h, w, 64), dtype=torch.bfloat16, device=x.device) if out is None else need("out", out, shape=(b, h, w, 64))
+    launch("v2v_lpips_stem_hip", x.device, ptr(x), DTYPE_CODES[x.dtype], b, cin, h, w, ptr(weight.detach().contiguous()), ptr(_lp_vec("bias", bias, 64, x.device)),
+           ptr(_lp_vec("shift", shift, 3, x.device)), ptr(_lp_vec("scale", scale, 3, x.device)), int(bool(normalize)), ptr(out))
     return out
 
 
 def lpips_stem_bwd(dz, weight, scale, cin, normalize=False):
     """dz bfloat16 [B,H,W,64] (ReLU-masked) -> float32 [B,cin,H,W]: the gradient of lpips_stem's x (the three channels summed for cin = 1)."""
     _lib.require_gpu()
-    _lp_act("dz", dz)
+    need("dz", dz)
     b, h, w, c = dz.shape
     if c != 64 or cin not in (1, 3) or weight.dtype != torch.float32 or tuple(weight.shape) != (64, 3, 3, 3) or weight.device != dz.device:
         raise ValueError("dz must be [B,H,W,64], cin 1 or 3, weight float32 [64,3,3,3] on dz's device")
     dpred = torch.empty((b, cin, h, w), dtype=torch.float32, device=dz.device)
-    _lp_launch("v2v_lpips_stem_bwd_hip", dz.device, _p(dz), b, cin, h, w, _p(weight.detach().contiguous()), _p(_lp_vec("scale", scale, 3, dz.device)),
-               int(bool(normalize)), _p(dpred))
+    launch("v2v_lpips_stem_bwd_hip", dz.device, ptr(dz), b, cin, h, w, ptr(weight.detach().contiguous()), ptr(_lp_vec("scale", scale, 3, dz.device)),
+           int(bool(normalize)), ptr(dpred))
     return dpred
 
 
@@ -306,9 +276,9 @@ def _lp_pool_shape(x):
 def lpips_pool(x):
     """2x2 max-pool on NHWC bfloat16: [B,H,W,C] -> [B,H/2,W/2,C]."""
     _lib.require_gpu()
-    b, h, w, c = _lp_pool_shape(_lp_act("x", x))
+    b, h, w, c = _lp_pool_shape(need("x", x))
     out = torch.empty((b, h // 2, w // 2, c), dtype=torch.bfloat16, device=x.device)
-    _lp_launch("v2v_lpips_pool_hip", x.device, _p(x), b, h, w, c, _p(out))
+    launch("v2v_lpips_pool_hip", x.device, ptr(x), b, h, w, c, ptr(out))
     return out
 
 
@@ -316,18 +286,18 @@ def lpips_pool_bwd(dy, x, dtap=None, relu_mask=False):
     """Backward of lpips_pool: dy [B,H/2,W/2,C] goes to the first maximum (row-major) of each window of x [B,H,W,C]; + dtap [B,H,W,C] in
     float32 with ONE rounding to bfloat16; relu_mask: zero where x <= 0 (x is the post-ReLU tensor that was pooled)."""
     _lib.require_gpu()
-    b, h, w, c = _lp_pool_shape(_lp_act("x", x))
-    _lp_act("dy", dy, (b, h // 2, w // 2, c))
+    b, h, w, c = _lp_pool_shape(need("x", x))
+    need("dy", dy, shape=(b, h // 2, w // 2, c))
     if dtap is not None:
-        _lp_act("dtap", dtap, x.shape)
+        need("dtap", dtap, shape=x.shape)
     dx = torch.empty_like(x)
-    _lp_launch("v2v_lpips_pool_bwd_hip", x.device, _p(dy), _p(x), _p(dtap), int(bool(relu_mask)), b, h, w, c, _p(dx))
+    launch("v2v_lpips_pool_bwd_hip", x.device, ptr(dy), ptr(x), ptr(dtap), int(bool(relu_mask)), b, h, w, c, ptr(dx))
     return dx
 
 
 def _lp_compare_args(f0, f1, w):
-    _lp_act("f0", f0)
-    _lp_act("f1", f1, f0.shape)
+    need("f0", f0)
+    need("f1", f1, shape=f0.shape)
     n, cc = f0.shape[0], f0.shape[3]
     if cc not in (64, 128, 256, 512) or f1.device != f0.device:
         raise ValueError("f0 / f1 must have 64, 128, 256 or 512 channels and share a device")
@@ -342,7 +312,7 @@ def lpips_compare_fwd(f0, f1, w, dist):
     if not isinstance(dist, torch.Tensor) or dist.dtype != torch.float32 or tuple(dist.shape) != (n,) or not dist.is_contiguous() or dist.device != f0.device:
         raise ValueError(f"dist must be a contiguous float32 [{n}] tensor on f0's device")
     ws = torch.empty((_lib.lib().v2v_lpips_compare_workspace_bytes(n, hw),), dtype=torch.uint8, device=f0.device)
-    _lp_launch("v2v_lpips_compare_fwd_hip", f0.device, _p(f0), _p(f1), _p(w), n, hw, cc, _p(dist), _p(ws))
+    launch("v2v_lpips_compare_fwd_hip", f0.device, ptr(f0), ptr(f1), ptr(w), n, hw, cc, ptr(dist), ptr(ws))
     return dist
 
 
@@ -353,7 +323,7 @@ def lpips_compare_bwd(f0, f1, w, ddist):
     n, hw, cc, w = _lp_compare_args(f0, f1, w)
     ddist = _f32("ddist", ddist, (n,))
     df0 = torch.empty_like(f0)
-    _lp_launch("v2v_lpips_compare_bwd_hip", f0.device, _p(f0), _p(f1), _p(w), _p(ddist), n, hw, cc, _p(df0))
+    launch("v2v_lpips_compare_bwd_hip", f0.device, ptr(f0), ptr(f1), ptr(w), ptr(ddist), n, hw, cc, ptr(df0))
     return df0
 
 

@@ -13,22 +13,18 @@ Single channel only; the LPIPS-alex network is not part of this module (pass the
 """
 from __future__ import annotations
 
-import ctypes as C
 from collections import defaultdict
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._lib import launch, ptr
 from .datasets import data_sources
 
 COUNTS = ("n_dense", "n_sparse", "dense_gt1", "dense_gt3", "sparse_gt1", "sparse_gt3")
 FLOW_METRICS = ("dense_EPE", "dense_1PE", "dense_3PE", "sparse_EPE", "sparse_1PE", "sparse_3PE")
 WIN = 7
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
 
 
 def _frames(name, t, channels=None):
@@ -79,9 +75,7 @@ def image_metrics(pred: torch.Tensor, image: torch.Tensor, divisor: float = 255.
         n = L.v2v_image_metrics_workspace_bytes(T, H, W)
         _lib.check(min(n, 0))
         ws = torch.empty((n // 8,), dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.v2v_image_metrics_hip(_ptr(pred), ps, _ptr(image), is_, T, H, W, float(divisor), float(data_range), _ptr(ws), _ptr(out), _ptr(smap),
-                                               _lib.stream_ptr()))
+        launch("v2v_image_metrics_hip", dev, ptr(pred), ps, ptr(image), is_, T, H, W, float(divisor), float(data_range), ptr(ws), ptr(out), ptr(smap))
     return (out, smap) if ssim_map else out
 
 
@@ -108,8 +102,7 @@ def flow_metrics(pred: torch.Tensor, gt: torch.Tensor, events: torch.Tensor):
         n = L.v2v_flow_metrics_workspace_bytes(T, H, W)
         _lib.check(min(n, 0))
         ws = torch.empty((n // 8,), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.v2v_flow_metrics_hip(_ptr(pred), ps, _ptr(gt), gs, _ptr(events), es, T, Cn, H, W, _ptr(ws), _ptr(counts), _ptr(sums), _lib.stream_ptr()))
+        launch("v2v_flow_metrics_hip", dev, ptr(pred), ps, ptr(gt), gs, ptr(events), es, T, Cn, H, W, ptr(ws), ptr(counts), ptr(sums))
     return counts, sums
 
 

@@ -22,6 +22,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._lib import launch, ptr
 
 MAX_WIDTH = 128
 
@@ -122,23 +123,19 @@ def learned_voxel(events, weights, biases, dim, slope, normalize=False, combined
         T = int(seg.numel()) - 1
     if packed is None:
         packed = pack_mlp(weights, biases)
-    L = _lib.lib()
     with torch.cuda.device(dev):
-        ws_bytes = L.v2v_learned_voxel_workspace_bytes(T, B)
+        ws_bytes = _lib.lib().v2v_learned_voxel_workspace_bytes(T, B)
         if ws_bytes < 0:
             _lib.check(int(ws_bytes))
         ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
         out = torch.empty((T, B, Cb if combined else 2 * Cb, H, W), dtype=torch.float32, device=dev)
         t_n = torch.zeros(n, dtype=torch.float32, device=dev) if return_t else None
-        dt = _lib.F64 if ev.dtype == torch.float64 else _lib.F32
-        seg_p = C.c_void_p(seg.data_ptr()) if seg is not None else None
-        ev_p = C.c_void_p(ev.data_ptr()) if n else C.c_void_p(ws.data_ptr())          # an empty tensor has no address; n == 0 reads nothing
-        host_layers = (C.c_int * len(layers))(*layers)
-        s = _lib.stream_ptr()
-        _lib.check(L.v2v_learned_voxel_stats_hip(ev_p, dt, n, seg_p, T, B, C.c_void_p(ws.data_ptr()), s))
-        _lib.check(L.v2v_learned_voxel_hip(ev_p, dt, n, seg_p, T, B, Cb, H, W, C.c_void_p(packed.data_ptr()), host_layers, len(layers), float(slope),
-                                           int(bool(normalize)), int(bool(combined)), C.c_void_p(ws.data_ptr()), C.c_void_p(out.data_ptr()),
-                                           C.c_void_p(t_n.data_ptr()) if return_t and n else None, s))
+    dt = _lib.DTYPE_CODES[ev.dtype]
+    ev_p = ptr(ev) if n else ptr(ws)          # an empty tensor has no address; n == 0 reads nothing
+    host_layers = (C.c_int * len(layers))(*layers)
+    launch("v2v_learned_voxel_stats_hip", dev, ev_p, dt, n, ptr(seg), T, B, ptr(ws))
+    launch("v2v_learned_voxel_hip", dev, ev_p, dt, n, ptr(seg), T, B, Cb, H, W, ptr(packed), host_layers, len(layers), float(slope),
+           int(bool(normalize)), int(bool(combined)), ptr(ws), ptr(out), ptr(t_n) if n else None)
     if offsets is None:
         out = out[0]
     return (out, t_n) if return_t else out

@@ -1,7 +1,9 @@
 """The raw NHWC bfloat16 operators of the recurrent UNet, forward and backward: one Python function per C entry point of the layer kernels
 (v2v_amd/csrc/v2v_convlstm.hpp, v2v_train_tu.hip), plus the packed-weight cache every layer shares (packed_weights: one tensor or a
 tuple of tensors as the key, the only implementation).  No nn.Module and no autograd here: v2v_amd/train.py builds the
-torch.autograd.Functions on these, v2v_amd/convlstm.py the layers.
+torch.autograd.Functions on these, v2v_amd/convlstm.py the layers.  Every operator validates with _lib.need and calls its entry point
+through _lib.launch (the operand's device, torch's current stream there, status checked) with _lib.ptr arguments: the package's one
+calling convention, nothing of it is defined here.
 
     convlstm_step / conv_nhwc / conv3x3_nhwc / upsample2x_nhwc     the forward operators
     convgru_step / pack_gru_weights                        the ConvGRU step (gates launch + candidate launch) and its packing
@@ -26,28 +28,10 @@ import functools
 import torch
 
 from . import _lib
+from ._lib import DTYPE_CODES, launch, need, ptr
 
 
-_DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _launch(name: str, device, *args) -> None:
-    """The C entry point `name` on `device` and torch's current stream there: lib().<name>(*args, stream), status checked."""
-    with torch.cuda.device(device):
-        _lib.check(getattr(_lib.lib(), name)(*args, _lib.stream_ptr()))
-
-
-def _need(name: str, t, dtype=torch.bfloat16, dims: str = "[B,H,W,C]", shape=None, last=None, device=None, owner: str = "x") -> None:
-    """ValueError unless t is a contiguous CUDA tensor of `dtype`: 4-D, or of exactly `shape` when given; with `last` channels and on
-    `device` (the device of the operand called `owner`) when given."""
-    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (t.dim() != 4 if shape is None else tuple(t.shape) != tuple(shape)) \
-            or (last is not None and t.shape[3] != last) or (device is not None and t.device != device):
-        where = f" on {owner}'s device" if device is not None else ""
-        raise ValueError(f"{name} must be a contiguous {str(dtype)[6:]} CUDA tensor {list(shape) if shape is not None else dims}{where}")
+_DTYPES = (torch.float32, torch.bfloat16)            # what the layer kernels read and write (codes: _lib.DTYPE_CODES)
 
 
 def packed_weights(cache: dict, slot: str, tensors, make):
@@ -80,7 +64,7 @@ def nchw_to_nhwc_bf16(x: torch.Tensor, relu: bool = False) -> torch.Tensor:
     x = x.contiguous()
     b, c, h, w = x.shape
     out = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=x.device)
-    _launch("v2v_nchw_to_nhwc_bf16_hip", x.device, _ptr(x), _DTYPES[x.dtype], b, c, h, w, int(bool(relu)), _ptr(out))
+    launch("v2v_nchw_to_nhwc_bf16_hip", x.device, ptr(x), DTYPE_CODES[x.dtype], b, c, h, w, int(bool(relu)), ptr(out))
     return out
 
 
@@ -106,7 +90,7 @@ def to_nhwc8_bf16(x, scales=None):
     if scales is not None and (scales.dtype != torch.float32 or tuple(scales.shape) != (b, 2) or not scales.is_contiguous() or scales.device != x.device):
         raise ValueError(f"scales must be a contiguous float32 [{b},2] tensor on x's device")
     out = torch.empty((b, h, w, 8), dtype=torch.bfloat16, device=x.device)
-    _launch("v2v_to_nhwc8_bf16_scaled_hip", x.device, _ptr(x), *x.stride(), b, c, h, w, _ptr(scales), _ptr(out))
+    launch("v2v_to_nhwc8_bf16_scaled_hip", x.device, ptr(x), *x.stride(), b, c, h, w, ptr(scales), ptr(out))
     return out
 
 
@@ -121,7 +105,7 @@ def pack_gate_weights(weight: torch.Tensor) -> torch.Tensor:
     n = C.c_uint64(0)
     _lib.check(_lib.lib().v2v_convlstm_packed_bytes(c, C.byref(n)))
     packed = torch.empty((n.value // 2,), dtype=torch.bfloat16, device=weight.device)
-    _launch("v2v_convlstm_pack_weights_hip", weight.device, _ptr(weight.detach().contiguous()), c, _ptr(packed))
+    launch("v2v_convlstm_pack_weights_hip", weight.device, ptr(weight.detach().contiguous()), c, ptr(packed))
     return packed
 
 
@@ -130,11 +114,11 @@ def convlstm_step(x, h_prev, c_prev, packed, bias, nchw_dtype=torch.float32, til
     Returns (h_state bf16 NHWC, c_state fp32 NHWC, h as [B,C,H,W] in nchw_dtype -- float32 / bfloat16 -- or None when
     nchw_dtype is None).  c_out may be c_prev (updated in place)."""
     _lib.require_gpu()
-    _need("x", x)
+    need("x", x)
     b, h, w, c = x.shape
     for name, t, dt in (("h_prev", h_prev, torch.bfloat16), ("c_prev", c_prev, torch.float32)):
         if t is not None:
-            _need(name, t, dt, shape=x.shape, device=x.device)
+            need(name, t, dt, shape=x.shape, device=x.device)
     if bias.dtype != torch.float32 or bias.numel() != 4 * c or packed.dtype != torch.bfloat16 or packed.numel() != 4 * c * 2 * c * 9:
         raise ValueError("bias must be float32 [4C] and packed the output of pack_gate_weights for the same C")
     h_state = torch.empty_like(x)
@@ -142,8 +126,8 @@ def convlstm_step(x, h_prev, c_prev, packed, bias, nchw_dtype=torch.float32, til
     if nchw_dtype is not None and nchw_dtype not in _DTYPES:
         raise ValueError("nchw_dtype must be torch.float32, torch.bfloat16 or None")
     h_nchw = torch.empty((b, c, h, w), dtype=nchw_dtype, device=x.device) if nchw_dtype is not None else None
-    _launch("v2v_convlstm_step_hip", x.device, _ptr(x), _ptr(h_prev), _ptr(c_prev), _ptr(packed), _ptr(bias.detach().contiguous()), b, h, w, c, _ptr(h_state),
-            _ptr(c_state), _ptr(h_nchw), _DTYPES.get(nchw_dtype, _lib.F32), tile_rows)
+    launch("v2v_convlstm_step_hip", x.device, ptr(x), ptr(h_prev), ptr(c_prev), ptr(packed), ptr(bias.detach().contiguous()), b, h, w, c, ptr(h_state),
+           ptr(c_state), ptr(h_nchw), DTYPE_CODES.get(nchw_dtype, _lib.F32), tile_rows)
     return h_state, c_state, h_nchw
 
 
@@ -161,7 +145,7 @@ def pack_gru_weights(update_weight, reset_weight, out_weight):
     _lib.check(_lib.lib().v2v_convgru_packed_bytes(c, C.byref(ng), C.byref(nc)))
     pg = torch.empty((ng.value // 2,), dtype=torch.bfloat16, device=update_weight.device)
     pc = torch.empty((nc.value // 2,), dtype=torch.bfloat16, device=update_weight.device)
-    _launch("v2v_convgru_pack_weights_hip", update_weight.device, *(_ptr(w.detach().contiguous()) for w in ws), c, _ptr(pg), _ptr(pc))
+    launch("v2v_convgru_pack_weights_hip", update_weight.device, *(ptr(w.detach().contiguous()) for w in ws), c, ptr(pg), ptr(pc))
     return pg, pc
 
 
@@ -173,13 +157,13 @@ def convgru_step(x, h_prev, h_prev_f32, packed, gates_bias, out_bias, nchw_dtype
     rne_bf16(h_prev_f32 * reset) -- the two workspaces between the launches.  h_f32_out may be h_prev_f32 (updated in place).
     tile_gates / tile_cand: kernel instance codes 1..5 (include/v2v_hip.h), 0 = by shape."""
     _lib.require_gpu()
-    _need("x", x)
+    need("x", x)
     b, h, w, c = x.shape
     if (h_prev is None) != (h_prev_f32 is None):
         raise ValueError("h_prev and h_prev_f32 come together (both None: the zero state)")
     for name, t, dt in (("h_prev", h_prev, torch.bfloat16), ("h_prev_f32", h_prev_f32, torch.float32)):
         if t is not None:
-            _need(name, t, dt, shape=x.shape, device=x.device)
+            need(name, t, dt, shape=x.shape, device=x.device)
     pg, pc = packed
     if gates_bias.dtype != torch.float32 or gates_bias.numel() != 2 * c or out_bias.dtype != torch.float32 or out_bias.numel() != c \
             or pg.dtype != torch.bfloat16 or pg.numel() != 2 * c * 2 * c * 9 or pc.dtype != torch.bfloat16 or pc.numel() != c * 2 * c * 9:
@@ -190,9 +174,9 @@ def convgru_step(x, h_prev, h_prev_f32, packed, gates_bias, out_bias, nchw_dtype
     u = torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
     h_f32 = h_f32_out if h_f32_out is not None else torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
     h_nchw = torch.empty((b, c, h, w), dtype=nchw_dtype, device=x.device) if nchw_dtype is not None else None
-    _launch("v2v_convgru_step_hip", x.device, _ptr(x), _ptr(h_prev), _ptr(h_prev_f32), _ptr(pg), _ptr(pc), _ptr(gates_bias.detach().contiguous()),
-            _ptr(out_bias.detach().contiguous()), b, h, w, c, _ptr(u), _ptr(hr), _ptr(h_bf16), _ptr(h_f32), _ptr(h_nchw), _DTYPES.get(nchw_dtype, _lib.F32),
-            tile_gates, tile_cand)
+    launch("v2v_convgru_step_hip", x.device, ptr(x), ptr(h_prev), ptr(h_prev_f32), ptr(pg), ptr(pc), ptr(gates_bias.detach().contiguous()),
+           ptr(out_bias.detach().contiguous()), b, h, w, c, ptr(u), ptr(hr), ptr(h_bf16), ptr(h_f32), ptr(h_nchw), DTYPE_CODES.get(nchw_dtype, _lib.F32),
+           tile_gates, tile_cand)
     return (h_bf16, h_f32, u, hr) if nchw_dtype is None else (h_bf16, h_f32, u, hr, h_nchw)
 
 
@@ -208,7 +192,7 @@ def pack_gru16_weights(update_weight, reset_weight, out_weight):
     if any(not _is_f32_weight(w, (16, 32, 3, 3)) or w.device != update_weight.device for w in ws):
         raise ValueError("the three gate weights must be float32 CUDA tensors [16, 32, 3, 3] on one device")
     packed = torch.empty((_lib.lib().v2v_convgru16_packed_elems(),), dtype=torch.bfloat16, device=update_weight.device)
-    _launch("v2v_convgru16_pack_weights_hip", packed.device, *(_ptr(w.detach().contiguous()) for w in ws), _ptr(packed))
+    launch("v2v_convgru16_pack_weights_hip", packed.device, *(ptr(w.detach().contiguous()) for w in ws), ptr(packed))
     return packed
 
 
@@ -217,13 +201,13 @@ def convgru16_step(x, h_prev, h_prev_f32, packed, gates_bias, out_bias, nchw_dty
     h_prev_f32: the float32 master of h_prev; both None = zero state.  gates_bias float32 [32] = update | reset, out_bias float32 [16].
     Returns (h_bf16, h_f32[, h as [B,16,H,W] in nchw_dtype when that is not None]): convgru_step's precision contract."""
     _lib.require_gpu()
-    _need("x", x, dims="[B,H,W,16]", last=16)
+    need("x", x, dims="[B,H,W,16]", last=16)
     b, h, w, c = x.shape
     if (h_prev is None) != (h_prev_f32 is None):
         raise ValueError("h_prev and h_prev_f32 come together (both None: the zero state)")
     for name, t, dt in (("h_prev", h_prev, torch.bfloat16), ("h_prev_f32", h_prev_f32, torch.float32)):
         if t is not None:
-            _need(name, t, dt, shape=x.shape, device=x.device)
+            need(name, t, dt, shape=x.shape, device=x.device)
     if gates_bias.dtype != torch.float32 or gates_bias.numel() != 32 or out_bias.dtype != torch.float32 or out_bias.numel() != 16 \
             or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_convgru16_packed_elems():
         raise ValueError("gates_bias must be float32 [32], out_bias float32 [16] and packed the output of pack_gru16_weights")
@@ -232,8 +216,8 @@ def convgru16_step(x, h_prev, h_prev_f32, packed, gates_bias, out_bias, nchw_dty
     h_bf16 = torch.empty_like(x)
     h_f32 = torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
     h_nchw = torch.empty((b, c, h, w), dtype=nchw_dtype, device=x.device) if nchw_dtype is not None else None
-    _launch("v2v_convgru16_step_hip", x.device, _ptr(x), _ptr(h_prev), _ptr(h_prev_f32), _ptr(packed), _ptr(gates_bias.detach().contiguous()),
-            _ptr(out_bias.detach().contiguous()), b, h, w, _ptr(h_bf16), _ptr(h_f32), _ptr(h_nchw), _DTYPES.get(nchw_dtype, _lib.F32))
+    launch("v2v_convgru16_step_hip", x.device, ptr(x), ptr(h_prev), ptr(h_prev_f32), ptr(packed), ptr(gates_bias.detach().contiguous()),
+           ptr(out_bias.detach().contiguous()), b, h, w, ptr(h_bf16), ptr(h_f32), ptr(h_nchw), DTYPE_CODES.get(nchw_dtype, _lib.F32))
     return (h_bf16, h_f32) if nchw_dtype is None else (h_bf16, h_f32, h_nchw)
 
 
@@ -243,20 +227,20 @@ def pack_resblock16_weights(w1, w2):
     if not _is_f32_weight(w1, (16, 16, 3, 3)) or not _is_f32_weight(w2, (16, 16, 3, 3)) or w1.device != w2.device:
         raise ValueError("w1 and w2 must be float32 CUDA tensors [16, 16, 3, 3] on one device")
     packed = torch.empty((_lib.lib().v2v_resblock16_packed_elems(),), dtype=torch.bfloat16, device=w1.device)
-    _launch("v2v_resblock16_pack_weights_hip", w1.device, _ptr(w1.detach().contiguous()), _ptr(w2.detach().contiguous()), _ptr(packed))
+    launch("v2v_resblock16_pack_weights_hip", w1.device, ptr(w1.detach().contiguous()), ptr(w2.detach().contiguous()), ptr(packed))
     return packed
 
 
 def resblock16_nhwc(x, packed, b1, b2):
     """out = relu(conv2(relu(conv1(x) + b1)) + b2 + x) on NHWC bfloat16 [B,H,W,16] in ONE launch (ResidualBlock(16, 16), norm=None)."""
     _lib.require_gpu()
-    _need("x", x, dims="[B,H,W,16]", last=16)
+    need("x", x, dims="[B,H,W,16]", last=16)
     if b1.numel() != 16 or b2.numel() != 16 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_resblock16_packed_elems():
         raise ValueError("b1 and b2 must be [16] and packed the output of pack_resblock16_weights")
     b, h, w, _ = x.shape
     out = torch.empty_like(x)
-    _launch("v2v_resblock16_nhwc_hip", x.device, _ptr(x), _ptr(packed), _ptr(b1.detach().float().contiguous()), _ptr(b2.detach().float().contiguous()), b, h, w,
-            _ptr(out))
+    launch("v2v_resblock16_nhwc_hip", x.device, ptr(x), ptr(packed), ptr(b1.detach().float().contiguous()), ptr(b2.detach().float().contiguous()), b, h, w,
+           ptr(out))
     return out
 
 
@@ -266,7 +250,7 @@ def pack_head16_weights(weight):
     if not weight.is_cuda or weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[0] != 16 or weight.shape[1] > 8 or tuple(weight.shape[2:]) != (3, 3):
         raise ValueError("weight must be a float32 CUDA tensor [16, Cin <= 8, 3, 3]")
     packed = torch.empty((_lib.lib().v2v_conv_head16_packed_elems(),), dtype=torch.bfloat16, device=weight.device)
-    _launch("v2v_conv_head16_pack_weights_hip", weight.device, _ptr(weight.detach().contiguous()), weight.shape[1], _ptr(packed))
+    launch("v2v_conv_head16_pack_weights_hip", weight.device, ptr(weight.detach().contiguous()), weight.shape[1], ptr(packed))
     return packed
 
 
@@ -274,12 +258,12 @@ def conv_head16_nhwc(x8, packed, bias, relu=True):
     """out = [relu](conv3x3(x, pad 1) + bias): x8 [B,H,W,8] bfloat16 (to_nhwc8_bf16) -> [B,H,W,16] bfloat16, any H and W; FireNet's head
     ConvLayer(num_bins, 16, 3, padding=1) (model/model.py:278)."""
     _lib.require_gpu()
-    _need("x8", x8, dims="[B,H,W,8]", last=8)
+    need("x8", x8, dims="[B,H,W,8]", last=8)
     if bias.numel() != 16 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_conv_head16_packed_elems():
         raise ValueError("bias must be [16] and packed the output of pack_head16_weights")
     b, h, w, _ = x8.shape
     out = torch.empty((b, h, w, 16), dtype=torch.bfloat16, device=x8.device)
-    _launch("v2v_conv_head16_nhwc_hip", x8.device, _ptr(x8), _ptr(packed), _ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w, _ptr(out))
+    launch("v2v_conv_head16_nhwc_hip", x8.device, ptr(x8), ptr(packed), ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w, ptr(out))
     return out
 
 
@@ -294,7 +278,7 @@ def pack_conv_weights(weight: torch.Tensor) -> torch.Tensor:
     if n < 0:
         raise ValueError(f"the convolution kernel does not take {cin} -> {cout} channels, {ks}x{ks}")
     packed = torch.empty((n,), dtype=torch.bfloat16, device=weight.device)
-    _launch("v2v_conv_pack_weights_hip", weight.device, _ptr(weight.detach().contiguous()), cin, cout, ks, _ptr(packed))
+    launch("v2v_conv_pack_weights_hip", weight.device, ptr(weight.detach().contiguous()), cin, cout, ks, ptr(packed))
     return packed
 
 
@@ -317,18 +301,18 @@ def tile_like_batch(n: int):
 def conv_nhwc(x, packed, bias, ks: int, stride: int = 1, residual=None, relu=False, tile_rows: int = 0):
     """out = [relu](conv_ks(x, stride, pad ks//2) + bias [+ residual]) on NHWC bfloat16: x [B,Hin,Win,Cin] -> [B,Hout,Wout,Cout]."""
     _lib.require_gpu()
-    _need("x", x, dims="[B,H,W,Cin]")
+    need("x", x, dims="[B,H,W,Cin]")
     b, hin, win, cin = x.shape
     cout = bias.numel()
     if bias.dtype != torch.float32 or packed.dtype != torch.bfloat16 or packed.numel() != _conv_packed_elems(cin, cout, ks):
         raise ValueError("bias must be float32 [Cout] and packed the output of pack_conv_weights for the same Cin, Cout, ks")
     h, w = (hin - 1) // stride + 1, (win - 1) // stride + 1
     if residual is not None:
-        _need("residual", residual, shape=(b, h, w, cout), device=x.device)
+        need("residual", residual, shape=(b, h, w, cout), device=x.device)
     out = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device)
     like = tile_rows == 0 and _tile_like_batch > 0 and _tile_like_batch != b
-    _launch("v2v_conv_nhwc_like_hip" if like else "v2v_conv_nhwc_hip", x.device, _ptr(x), _ptr(packed), _ptr(bias.detach().contiguous()), _ptr(residual),
-            int(bool(relu)), b, hin, win, cin, cout, ks, stride, _ptr(out), _tile_like_batch if like else tile_rows)
+    launch("v2v_conv_nhwc_like_hip" if like else "v2v_conv_nhwc_hip", x.device, ptr(x), ptr(packed), ptr(bias.detach().contiguous()), ptr(residual),
+           int(bool(relu)), b, hin, win, cin, cout, ks, stride, ptr(out), _tile_like_batch if like else tile_rows)
     return out
 
 
@@ -348,12 +332,12 @@ def upsample2x_nhwc(x, skip=None):
     """out = bilinear_x2(x [+ skip]) on NHWC bfloat16 ([B,H,W,C] -> [B,2H,2W,C]): f.interpolate(scale_factor=2, mode='bilinear',
     align_corners=False) of UpsampleConvLayer.forward (model/submodules.py:86-87) behind the sum skip (model/unet.py:304)."""
     _lib.require_gpu()
-    _need("x", x)
+    need("x", x)
     if skip is not None:
-        _need("skip", skip, shape=x.shape, device=x.device)
+        need("skip", skip, shape=x.shape, device=x.device)
     b, h, w, c = x.shape
     out = torch.empty((b, 2 * h, 2 * w, c), dtype=torch.bfloat16, device=x.device)
-    _launch("v2v_upsample2x_nhwc_hip", x.device, _ptr(x), _ptr(skip), b, h, w, c, _ptr(out))
+    launch("v2v_upsample2x_nhwc_hip", x.device, ptr(x), ptr(skip), b, h, w, c, ptr(out))
     return out
 
 
@@ -361,16 +345,16 @@ def conv1x1_nhwc(x, weight, bias, skip=None, out_dtype=torch.bfloat16):
     """out[..., o] = bias[o] + sum_c weight[o, c] * (x[..., c] + skip[..., c]) on NHWC bfloat16 ([B,H,W,C] -> [B,H,W,Cout], Cout <= 3):
     the prediction layer ConvLayer(base, out, 1, activation=None) on skip_sum(x, head) (model/unet.py:58-64, :307)."""
     _lib.require_gpu()
-    _need("x", x)
+    need("x", x)
     if skip is not None:
-        _need("skip", skip, shape=x.shape, device=x.device)
+        need("skip", skip, shape=x.shape, device=x.device)
     b, h, w, c = x.shape
     weight = weight.detach().reshape(weight.shape[0], -1).float().contiguous()
     if weight.shape[1] != c or bias.numel() != weight.shape[0] or out_dtype not in _DTYPES:
         raise ValueError("weight must be [Cout, C(,1,1)], bias [Cout], out_dtype float32 or bfloat16")
     out = torch.empty((b, h, w, weight.shape[0]), dtype=out_dtype, device=x.device)
-    _launch("v2v_conv1x1_nhwc_hip", x.device, _ptr(x), _ptr(skip), _ptr(weight), _ptr(bias.detach().float().contiguous()), b * h * w, c, weight.shape[0],
-            _ptr(out), _DTYPES[out_dtype])
+    launch("v2v_conv1x1_nhwc_hip", x.device, ptr(x), ptr(skip), ptr(weight), ptr(bias.detach().float().contiguous()), b * h * w, c, weight.shape[0],
+           ptr(out), DTYPE_CODES[out_dtype])
     return out
 
 
@@ -382,7 +366,7 @@ def pack_head_weights(weight):
         raise ValueError("weight must be a float32 CUDA tensor [32, Cin <= 8, ks, ks], ks 3 or 5")
     ks = weight.shape[2]
     packed = torch.empty((_lib.lib().v2v_conv_head_packed_elems(ks),), dtype=torch.bfloat16, device=weight.device)
-    _launch("v2v_conv_head_pack_weights_hip", weight.device, _ptr(weight.detach().contiguous()), weight.shape[1], ks, _ptr(packed))
+    launch("v2v_conv_head_pack_weights_hip", weight.device, ptr(weight.detach().contiguous()), weight.shape[1], ks, ptr(packed))
     return packed
 
 
@@ -390,12 +374,12 @@ def conv_head_nhwc(x8, packed, bias, ks: int, relu=True):
     """out = [relu](conv_ks(x, stride 1, pad ks//2) + bias): x8 [B,H,W,8] bfloat16 (to_nhwc8_bf16) -> [B,H,W,32] bfloat16; the UNet's
     head ConvLayer(num_bins, 32, 5, stride 1, padding 2) (model/unet.py:77-78).  H and W multiples of 16."""
     _lib.require_gpu()
-    _need("x8", x8, dims="[B,H,W,8]", last=8)
+    need("x8", x8, dims="[B,H,W,8]", last=8)
     if bias.numel() != 32 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_conv_head_packed_elems(ks):
         raise ValueError("bias must be [32] and packed the output of pack_head_weights for the same ks")
     b, h, w, _ = x8.shape
     out = torch.empty((b, h, w, 32), dtype=torch.bfloat16, device=x8.device)
-    _launch("v2v_conv_head_nhwc_hip", x8.device, _ptr(x8), _ptr(packed), _ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w, ks, _ptr(out))
+    launch("v2v_conv_head_nhwc_hip", x8.device, ptr(x8), ptr(packed), ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w, ks, ptr(out))
     return out
 
 
@@ -406,7 +390,7 @@ def pack_stem_weights(weight):
             or weight.shape[1] > 8:
         raise ValueError("weight must be a float32 CUDA tensor [64, Cin <= 8, 3, 3]")
     packed = torch.empty((_lib.lib().v2v_conv_stem_packed_elems(),), dtype=torch.bfloat16, device=weight.device)
-    _launch("v2v_conv_stem_pack_weights_hip", weight.device, _ptr(weight.detach().contiguous()), weight.shape[1], _ptr(packed))
+    launch("v2v_conv_stem_pack_weights_hip", weight.device, ptr(weight.detach().contiguous()), weight.shape[1], ptr(packed))
     return packed
 
 
@@ -414,12 +398,12 @@ def conv_stem_nhwc(x8, packed, bias, relu=True):
     """out = [relu](conv3x3(x, stride 2, pad 1) + bias): x8 [B,H,W,8] bfloat16 (to_nhwc8_bf16) -> [B,H/2,W/2,64] bfloat16; the plain UNet's
     first encoder ConvLayer(num_bins, 64, 3, stride 2, padding 1) (model/unet.py:320-326).  H and W multiples of 16."""
     _lib.require_gpu()
-    _need("x8", x8, dims="[B,H,W,8]", last=8)
+    need("x8", x8, dims="[B,H,W,8]", last=8)
     if bias.numel() != 64 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_conv_stem_packed_elems():
         raise ValueError("bias must be [64] and packed the output of pack_stem_weights")
     b, h, w, _ = x8.shape
     out = torch.empty((b, h // 2, w // 2, 64), dtype=torch.bfloat16, device=x8.device)
-    _launch("v2v_conv_stem_nhwc_hip", x8.device, _ptr(x8), _ptr(packed), _ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w, _ptr(out))
+    launch("v2v_conv_stem_nhwc_hip", x8.device, ptr(x8), ptr(packed), ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w, ptr(out))
     return out
 
 
@@ -428,15 +412,15 @@ def upsample2x_cat_nhwc(x, skip=None):
     f.interpolate(skip_concat(x, skip), scale_factor=2, mode='bilinear', align_corners=False) (model/model_util.py:10, model/unet.py:350,
     model/submodules.py:86-87) without the low-resolution cat tensor."""
     _lib.require_gpu()
-    _need("x", x)
+    need("x", x)
     if skip is not None:
-        _need("skip", skip, device=x.device)
+        need("skip", skip, device=x.device)
         if skip.shape[:3] != x.shape[:3]:
             raise ValueError("skip must have x's batch and spatial size")
     b, h, w, c1 = x.shape
     c2 = 0 if skip is None else skip.shape[3]
     out = torch.empty((b, 2 * h, 2 * w, c1 + c2), dtype=torch.bfloat16, device=x.device)
-    _launch("v2v_upsample2x_cat_nhwc_hip", x.device, _ptr(x), c1, _ptr(skip), c2, b, h, w, _ptr(out))
+    launch("v2v_upsample2x_cat_nhwc_hip", x.device, ptr(x), c1, ptr(skip), c2, b, h, w, ptr(out))
     return out
 
 
@@ -459,7 +443,7 @@ def relu_bwd_nhwc(dy, y):
     """y > 0 ? dy : 0 on NHWC bfloat16 (y = the saved post-ReLU output)."""
     dy = _nhwc_bf16(dy)
     out = torch.empty_like(dy)
-    _launch("v2v_relu_bwd_nhwc_hip", dy.device, _ptr(dy), _ptr(y), dy.numel() // dy.shape[-1], dy.shape[-1], _ptr(out))
+    launch("v2v_relu_bwd_nhwc_hip", dy.device, ptr(dy), ptr(y), dy.numel() // dy.shape[-1], dy.shape[-1], ptr(out))
     return out
 
 
@@ -471,7 +455,7 @@ def pack_dgrad_weights(weight: torch.Tensor) -> torch.Tensor:
         raise ValueError(f"no data-gradient kernel for {cin} -> {cout} channels, {ks}x{ks}")
     packed = torch.empty((n,), dtype=torch.bfloat16, device=weight.device)
     scratch = torch.empty((weight.numel(),), dtype=torch.float32, device=weight.device)
-    _launch("v2v_conv_dgrad_pack_weights_hip", weight.device, _ptr(weight.detach().float().contiguous()), cin, cout, ks, _ptr(scratch), _ptr(packed))
+    launch("v2v_conv_dgrad_pack_weights_hip", weight.device, ptr(weight.detach().float().contiguous()), cin, cout, ks, ptr(scratch), ptr(packed))
     return packed
 
 
@@ -481,7 +465,7 @@ def conv_dgrad_nhwc(dy, packed, cin: int, ks: int, stride: int, hin: int, win: i
     b, cout = dy.shape[0], dy.shape[3]
     ws = _workspace(_lib.lib().v2v_conv_dgrad_workspace_bytes(b, hin, win, cin, cout, stride), dy.device)
     dx = torch.empty((b, hin, win, cin), dtype=torch.bfloat16, device=dy.device)
-    _launch("v2v_conv_dgrad_nhwc_hip", dy.device, _ptr(dy), _ptr(packed), _ptr(residual), b, hin, win, cin, cout, ks, stride, _ptr(ws), _ptr(dx))
+    launch("v2v_conv_dgrad_nhwc_hip", dy.device, ptr(dy), ptr(packed), ptr(residual), b, hin, win, cin, cout, ks, stride, ptr(ws), ptr(dx))
     return dx
 
 
@@ -494,7 +478,7 @@ def conv_wgrad_nhwc(dy, x1, x2=None, c2: int = 0, cin_out: int | None = None, ks
     ws = _workspace(_lib.lib().v2v_conv_wgrad_workspace_bytes(b, ho, wo, c1 + c2, cout, ks), dy.device)
     dw = torch.empty((cout, cin_out, ks, ks), dtype=torch.float32, device=dy.device)
     db = torch.empty((cout,), dtype=torch.float32, device=dy.device)
-    _launch("v2v_conv_wgrad_nhwc_hip", dy.device, _ptr(dy), _ptr(x1), c1, _ptr(x2), c2, cin_out, b, hin, win, cout, ks, stride, _ptr(ws), _ptr(dw), _ptr(db))
+    launch("v2v_conv_wgrad_nhwc_hip", dy.device, ptr(dy), ptr(x1), c1, ptr(x2), c2, cin_out, b, hin, win, cout, ks, stride, ptr(ws), ptr(dw), ptr(db))
     return dw, db
 
 
@@ -503,7 +487,7 @@ def upsample2x_bwd_nhwc(dout):
     dout = _nhwc_bf16(dout)
     b, h2, w2, c = dout.shape
     dx = torch.empty((b, h2 // 2, w2 // 2, c), dtype=torch.bfloat16, device=dout.device)
-    _launch("v2v_upsample2x_bwd_nhwc_hip", dout.device, _ptr(dout), b, h2 // 2, w2 // 2, c, _ptr(dx))
+    launch("v2v_upsample2x_bwd_nhwc_hip", dout.device, ptr(dout), b, h2 // 2, w2 // 2, c, ptr(dx))
     return dx
 
 
@@ -512,7 +496,7 @@ def upsample2x_cat_bwd_nhwc(dout, c0: int, c: int):
     dout = _nhwc_bf16(dout)
     b, h2, w2, ctot = dout.shape
     dx = torch.empty((b, h2 // 2, w2 // 2, c), dtype=torch.bfloat16, device=dout.device)
-    _launch("v2v_upsample2x_cat_bwd_nhwc_hip", dout.device, _ptr(dout), b, h2 // 2, w2 // 2, ctot, c0, c, _ptr(dx))
+    launch("v2v_upsample2x_cat_bwd_nhwc_hip", dout.device, ptr(dout), b, h2 // 2, w2 // 2, ctot, c0, c, ptr(dx))
     return dx
 
 
@@ -527,8 +511,8 @@ def conv1x1_bwd_cout_nhwc(dy, x, skip, weight):
     dx = torch.empty_like(x)
     dw = torch.empty((cout, c), dtype=torch.float32, device=x.device)
     db = torch.empty((cout,), dtype=torch.float32, device=x.device)
-    _launch("v2v_conv1x1_bwd_cout_nhwc_hip", x.device, _ptr(dy), _ptr(x), _ptr(skip), _ptr(weight.detach().float().reshape(cout, c).contiguous()), m, c, cout,
-            _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws))
+    launch("v2v_conv1x1_bwd_cout_nhwc_hip", x.device, ptr(dy), ptr(x), ptr(skip), ptr(weight.detach().float().reshape(cout, c).contiguous()), m, c, cout,
+           ptr(dx), ptr(dw), ptr(db), ptr(ws))
     return dx, dw.reshape(weight.shape), db
 
 
@@ -542,8 +526,8 @@ def conv1x1_bwd_nhwc(dy, x, skip, weight):
     dx = torch.empty_like(x)
     dw = torch.empty((c,), dtype=torch.float32, device=x.device)
     db = torch.empty((1,), dtype=torch.float32, device=x.device)
-    _launch("v2v_conv1x1_bwd_nhwc_hip", x.device, _ptr(dy), _ptr(x), _ptr(skip), _ptr(weight.detach().float().reshape(-1).contiguous()), m, c, _ptr(dx),
-            _ptr(dw), _ptr(db), _ptr(ws))
+    launch("v2v_conv1x1_bwd_nhwc_hip", x.device, ptr(dy), ptr(x), ptr(skip), ptr(weight.detach().float().reshape(-1).contiguous()), m, c, ptr(dx),
+           ptr(dw), ptr(db), ptr(ws))
     return dx, dw.reshape(weight.shape), db
 
 
@@ -554,8 +538,8 @@ def convlstm_step_bwd(x, h_prev, c_prev, packed, bias, dh, dc):
     dc = dc.float().contiguous() if dc is not None else None
     dgates = torch.empty((b, h, w, 4 * c), dtype=torch.bfloat16, device=x.device)
     dc_prev = torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
-    _launch("v2v_convlstm_step_bwd_hip", x.device, _ptr(x), _ptr(h_prev), _ptr(c_prev), _ptr(packed), _ptr(bias), _ptr(dh), _ptr(dc), b, h, w, c, _ptr(dgates),
-            _ptr(dc_prev))
+    launch("v2v_convlstm_step_bwd_hip", x.device, ptr(x), ptr(h_prev), ptr(c_prev), ptr(packed), ptr(bias), ptr(dh), ptr(dc), b, h, w, c, ptr(dgates),
+           ptr(dc_prev))
     return dgates, dc_prev
 
 
@@ -568,11 +552,11 @@ def hyper_context_nhwc8(events, prev):
     if not events.is_cuda or events.dtype != torch.float32 or events.dim() != 4 or events.shape[1] > 7:
         raise ValueError("events must be a float32 CUDA tensor [B, C <= 7, H, W]")
     b, c, h, w = events.shape
-    _need("prev", prev, torch.float32, shape=(b, 1, h, w), device=events.device, owner="events")
+    need("prev", prev, torch.float32, shape=(b, 1, h, w), device=events.device, owner="events")
     if h % 4 != 0 or w % 4 != 0:
         raise ValueError("H and W must be multiples of 4")
     out = torch.empty((b, h // 4, w // 4, 8), dtype=torch.bfloat16, device=events.device)
-    _launch("v2v_hyper_context_hip", events.device, _ptr(events), *events.stride(), _ptr(prev), b, c, h, w, _ptr(out))
+    launch("v2v_hyper_context_hip", events.device, ptr(events), *events.stride(), ptr(prev), b, c, h, w, ptr(out))
     return out
 
 
@@ -580,14 +564,14 @@ def context_conv_nhwc(x8, weight, bias):
     """out = conv3x3(x8, pad 1) + bias: x8 [B,h,w,8] bfloat16 (hyper_context_nhwc8) -> [B,h,w,32] bfloat16, any h and w;
     ConvolutionalContextFusion.conv (model/hyper/hyper_dynamic.py:22).  weight float32 [32, Cin <= 8, 3, 3], read as it is (no packing)."""
     _lib.require_gpu()
-    _need("x8", x8, dims="[B,h,w,8]", last=8)
+    need("x8", x8, dims="[B,h,w,8]", last=8)
     if weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[0] != 32 or weight.shape[1] > 8 or tuple(weight.shape[2:]) != (3, 3) \
             or bias.numel() != 32 or weight.device != x8.device:
         raise ValueError("weight must be float32 [32, Cin <= 8, 3, 3] on x8's device, bias [32]")
     b, h, w, _ = x8.shape
     out = torch.empty((b, h, w, 32), dtype=torch.bfloat16, device=x8.device)
-    _launch("v2v_hyper_context_conv_hip", x8.device, _ptr(x8), _ptr(weight.detach().contiguous()), _ptr(bias.detach().float().contiguous()), b, h, w,
-            weight.shape[1], _ptr(out))
+    launch("v2v_hyper_context_conv_hip", x8.device, ptr(x8), ptr(weight.detach().contiguous()), ptr(bias.detach().float().contiguous()), b, h, w,
+           weight.shape[1], ptr(out))
     return out
 
 
@@ -596,7 +580,7 @@ def tanh_bf16_(x):
     _lib.require_gpu()
     if not x.is_cuda or x.dtype != torch.bfloat16 or not x.is_contiguous() or x.numel() % 8 != 0:
         raise ValueError("x must be a contiguous bfloat16 CUDA tensor with a multiple of 8 elements")
-    _launch("v2v_tanh_bf16_hip", x.device, _ptr(x), x.numel(), _ptr(x))
+    launch("v2v_tanh_bf16_hip", x.device, ptr(x), x.numel(), ptr(x))
     return x
 
 
@@ -605,11 +589,11 @@ def hyper_atoms(coeff, bases):
     zero-padded to the convolution kernel's 128 columns), bases float32 [12,25] -> atoms float32 [B,h,w,25,6]:
     atoms[..., l, m] = sum_k tanh(coeff[..., m * 12 + k]) * bases[k, l] (DynamicAtomGeneration.forward, model/hyper/hyper_dynamic.py:54-56)."""
     _lib.require_gpu()
-    _need("coeff", coeff, dims="[B,h,w,128]", last=128)
-    _need("bases", bases, torch.float32, shape=(12, 25), device=coeff.device, owner="coeff")
+    need("coeff", coeff, dims="[B,h,w,128]", last=128)
+    need("bases", bases, torch.float32, shape=(12, 25), device=coeff.device, owner="coeff")
     b, h, w, _ = coeff.shape
     atoms = torch.empty((b, h, w, 25, 6), dtype=torch.float32, device=coeff.device)
-    _launch("v2v_hyper_atoms_hip", coeff.device, _ptr(coeff), _ptr(bases), b * h * w, _ptr(atoms))
+    launch("v2v_hyper_atoms_hip", coeff.device, ptr(coeff), ptr(bases), b * h * w, ptr(atoms))
     return atoms
 
 
@@ -624,7 +608,7 @@ def pack_dynconv_weights(weight):
     if n < 0:
         raise ValueError(f"the dynamic convolution takes 256 -> 128 channels with 6 atoms (got weight {tuple(weight.shape)})")
     packed = torch.empty((n,), dtype=torch.bfloat16, device=weight.device)
-    _launch("v2v_hyper_dynconv_pack_weights_hip", weight.device, _ptr(weight.detach().contiguous()), k // 6, cout, 6, _ptr(packed))
+    launch("v2v_hyper_dynconv_pack_weights_hip", weight.device, ptr(weight.detach().contiguous()), k // 6, cout, 6, ptr(packed))
     return packed
 
 
@@ -632,15 +616,15 @@ def dynconv_nhwc(x, atoms, packed, bias, relu=True):
     """out = [relu](DynamicConv(x, atoms) + bias) on NHWC bfloat16: x [B,H,W,256], atoms float32 [B,H,W,25,6] (hyper_atoms) -> [B,H,W,128];
     neither the unfolded input nor the intermediate features of model/hyper/hyper_dynamic.py:87-91 are written anywhere."""
     _lib.require_gpu()
-    _need("x", x, dims="[B,H,W,Cin]")
+    need("x", x, dims="[B,H,W,Cin]")
     b, h, w, cin = x.shape
     cout = bias.numel()
-    _need("atoms", atoms, torch.float32, shape=(b, h, w, 25, 6), device=x.device)
+    need("atoms", atoms, torch.float32, shape=(b, h, w, 25, 6), device=x.device)
     if bias.dtype != torch.float32 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_hyper_dynconv_packed_elems(cin, cout, 6, 5):
         raise ValueError("bias must be float32 [128] and packed the output of pack_dynconv_weights (256 -> 128 channels, 6 atoms)")
     out = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device)
-    _launch("v2v_hyper_dynconv_nhwc_hip", x.device, _ptr(x), _ptr(atoms), _ptr(packed), _ptr(bias.detach().contiguous()), int(bool(relu)), b, h, w, cin, cout,
-            6, 5, _ptr(out))
+    launch("v2v_hyper_dynconv_nhwc_hip", x.device, ptr(x), ptr(atoms), ptr(packed), ptr(bias.detach().contiguous()), int(bool(relu)), b, h, w, cin, cout,
+           6, 5, ptr(out))
     return out
 
 
@@ -652,30 +636,30 @@ def pack_dynconv_weights_t(weight):
     if not weight.is_cuda or weight.dtype != torch.float32 or tuple(weight.shape) != (128, 1536, 1, 1):
         raise ValueError("weight must be a float32 CUDA tensor [128, 1536, 1, 1]")
     packed = torch.empty((128 * 1536,), dtype=torch.bfloat16, device=weight.device)
-    _launch("v2v_hyper_dynconv_pack_t_hip", weight.device, _ptr(weight.detach().contiguous()), _ptr(packed))
+    launch("v2v_hyper_dynconv_pack_t_hip", weight.device, ptr(weight.detach().contiguous()), ptr(packed))
     return packed
 
 
 def dynconv_df_nhwc(dz, packed_t):
     """dz bf16 [B,H,W,128] (the ReLU backward applied) -> dF bf16 [B,H,W,4,6,64]: dF[p][cb][m][k] = sum_o dz[p][o] * W[o][(cb*64+k)*6+m],
     float32 accumulation on the matrix cores, one rounding."""
-    _need("dz", dz, dims="[B,H,W,128]", last=128)
+    need("dz", dz, dims="[B,H,W,128]", last=128)
     if packed_t.dtype != torch.bfloat16 or packed_t.numel() != 128 * 1536 or packed_t.device != dz.device:
         raise ValueError("packed_t must be the output of pack_dynconv_weights_t on dz's device")
     b, h, w, _ = dz.shape
     df = torch.empty((b, h, w, 4, 6, 64), dtype=torch.bfloat16, device=dz.device)
-    _launch("v2v_hyper_dynconv_df_hip", dz.device, _ptr(dz), _ptr(packed_t), b * h * w, _ptr(df))
+    launch("v2v_hyper_dynconv_df_hip", dz.device, ptr(dz), ptr(packed_t), b * h * w, ptr(df))
     return df
 
 
 def dynconv_datoms_nhwc(x, df):
     """x bf16 [B,H,W,256] (the dynamic convolution's input), dF (dynconv_df_nhwc) -> dAtoms float32 [B,H,W,25,6]:
     dAtoms[p][l][m] = sum_c x[p + offset_l][c] * dF[p][c][m] over the zero-padded 5 x 5 window."""
-    _need("x", x, dims="[B,H,W,256]", last=256)
+    need("x", x, dims="[B,H,W,256]", last=256)
     b, h, w, _ = x.shape
-    _need("df", df, shape=(b, h, w, 4, 6, 64), device=x.device)
+    need("df", df, shape=(b, h, w, 4, 6, 64), device=x.device)
     out = torch.empty((b, h, w, 25, 6), dtype=torch.float32, device=x.device)
-    _launch("v2v_hyper_dynconv_datoms_hip", x.device, _ptr(x), _ptr(df), b, h, w, _ptr(out))
+    launch("v2v_hyper_dynconv_datoms_hip", x.device, ptr(x), ptr(df), b, h, w, ptr(out))
     return out
 
 
@@ -684,33 +668,33 @@ def dynconv_dx_nhwc(atoms, df):
     if atoms.dim() != 5:
         raise ValueError("atoms must be float32 [B,H,W,25,6]")
     b, h, w = atoms.shape[:3]
-    _need("atoms", atoms, torch.float32, shape=(b, h, w, 25, 6))
-    _need("df", df, shape=(b, h, w, 4, 6, 64), device=atoms.device, owner="atoms")
+    need("atoms", atoms, torch.float32, shape=(b, h, w, 25, 6))
+    need("df", df, shape=(b, h, w, 4, 6, 64), device=atoms.device, owner="atoms")
     out = torch.empty((b, h, w, 256), dtype=torch.bfloat16, device=atoms.device)
-    _launch("v2v_hyper_dynconv_dx_hip", atoms.device, _ptr(atoms), _ptr(df), b, h, w, _ptr(out))
+    launch("v2v_hyper_dynconv_dx_hip", atoms.device, ptr(atoms), ptr(df), b, h, w, ptr(out))
     return out
 
 
 def dynconv_wgrad_nhwc(dz, x, atoms):
     """(dW float32 [128, 1536, 1, 1], db float32 [128]) of the dynamic convolution: dW[o][c*6+m] = sum_p dz[p][o] * bf16(F[p][c][m]) with the
     features F recomputed from x and atoms exactly as dynconv_nhwc computes and rounds them (they are never stored)."""
-    _need("dz", dz, dims="[B,H,W,128]", last=128)
+    need("dz", dz, dims="[B,H,W,128]", last=128)
     b, h, w, _ = dz.shape
-    _need("x", x, shape=(b, h, w, 256), device=dz.device, owner="dz")
-    _need("atoms", atoms, torch.float32, shape=(b, h, w, 25, 6), device=dz.device, owner="dz")
+    need("x", x, shape=(b, h, w, 256), device=dz.device, owner="dz")
+    need("atoms", atoms, torch.float32, shape=(b, h, w, 25, 6), device=dz.device, owner="dz")
     ws = _workspace(_lib.lib().v2v_hyper_dynconv_wgrad_workspace_bytes(b, h, w), dz.device)
     dw = torch.empty((128, 1536, 1, 1), dtype=torch.float32, device=dz.device)
     db = torch.empty((128,), dtype=torch.float32, device=dz.device)
-    _launch("v2v_hyper_dynconv_wgrad_hip", dz.device, _ptr(dz), _ptr(x), _ptr(atoms), b, h, w, _ptr(ws), _ptr(dw), _ptr(db))
+    launch("v2v_hyper_dynconv_wgrad_hip", dz.device, ptr(dz), ptr(x), ptr(atoms), b, h, w, ptr(ws), ptr(dw), ptr(db))
     return dw, db
 
 
 def hyper_bn_stats(z, eps: float = 1e-5):
     """z bf16 [B,h,w,Cs] -> (mean, biased variance, rstd = 1 / sqrt(var + eps)), float32 [Cs] each, over the B*h*w rows."""
-    _need("z", z, dims="[B,h,w,Cs]")
+    need("z", z, dims="[B,h,w,Cs]")
     cs = z.shape[3]
     mean, var, rstd = (torch.empty((cs,), dtype=torch.float32, device=z.device) for _ in range(3))
-    _launch("v2v_hyper_bn_stats_hip", z.device, _ptr(z), z.numel() // cs, cs, C.c_float(eps), _ptr(mean), _ptr(var), _ptr(rstd))
+    launch("v2v_hyper_bn_stats_hip", z.device, ptr(z), z.numel() // cs, cs, C.c_float(eps), ptr(mean), ptr(var), ptr(rstd))
     return mean, var, rstd
 
 
@@ -723,35 +707,35 @@ def _bn_affine(z, gamma, beta):
 
 def hyper_bn_apply(z, mean, rstd, gamma, beta, tanh: bool):
     """gamma * (z - mean) * rstd + beta [-> tanh] -> bf16 [B,h,w,Cs]; gamma / beta hold the Cv valid columns, the rest come out zero."""
-    _need("z", z, dims="[B,h,w,Cs]")
+    need("z", z, dims="[B,h,w,Cs]")
     cs, cv, g, b = _bn_affine(z, gamma, beta)
     out = torch.empty_like(z)
-    _launch("v2v_hyper_bn_apply_hip", z.device, _ptr(z), _ptr(mean), _ptr(rstd), _ptr(g), _ptr(b), z.numel() // cs, cs, cv, int(bool(tanh)), _ptr(out))
+    launch("v2v_hyper_bn_apply_hip", z.device, ptr(z), ptr(mean), ptr(rstd), ptr(g), ptr(b), z.numel() // cs, cs, cv, int(bool(tanh)), ptr(out))
     return out
 
 
 def hyper_bn_bwd(dy, z, mean, rstd, gamma, beta, tanh: bool):
     """Backward of hyper_bn_apply on batch statistics: dy bf16 or float32 [B,h,w,Cs] -> (dz bf16 [B,h,w,Cs], dgamma [Cv], dbeta [Cv],
     dz_sum [Cv] = the row sum of dz before its bf16 rounding: the bias gradient of the convolution in front, zero in exact arithmetic)."""
-    _need("z", z, dims="[B,h,w,Cs]")
+    need("z", z, dims="[B,h,w,Cs]")
     cs, cv, g, b = _bn_affine(z, gamma, beta)
     if dy.dtype not in _DTYPES:
         raise ValueError("dy must be float32 or bfloat16")
-    _need("dy", dy, dy.dtype, shape=z.shape, device=z.device, owner="z")
+    need("dy", dy, dy.dtype, shape=z.shape, device=z.device, owner="z")
     sums = torch.empty((4, cs), dtype=torch.float32, device=z.device)
     dz = torch.empty_like(z)
-    _launch("v2v_hyper_bn_bwd_hip", z.device, _ptr(dy), int(dy.dtype == torch.float32), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(g), _ptr(b), z.numel() // cs,
-            cs, cv, int(bool(tanh)), _ptr(sums), _ptr(dz))
+    launch("v2v_hyper_bn_bwd_hip", z.device, ptr(dy), int(dy.dtype == torch.float32), ptr(z), ptr(mean), ptr(rstd), ptr(g), ptr(b), z.numel() // cs,
+           cs, cv, int(bool(tanh)), ptr(sums), ptr(dz))
     return dz, sums[1, :cv], sums[0, :cv], sums[2, :cv]
 
 
 def hyper_atoms_bwd(datoms, pre, bases):
     """Adjoint of hyper_atoms: datoms float32 [B,h,w,25,6], pre bf16 [B,h,w,128] (what hyper_atoms read) -> dpre float32 [B,h,w,128],
     dpre[..., m*12+k] = (1 - tanh(pre)^2) * sum_l datoms[..., l, m] * bases[k, l]; columns 72..127 zero."""
-    _need("pre", pre, dims="[B,h,w,128]", last=128)
+    need("pre", pre, dims="[B,h,w,128]", last=128)
     b, h, w, _ = pre.shape
-    _need("datoms", datoms, torch.float32, shape=(b, h, w, 25, 6), device=pre.device, owner="pre")
-    _need("bases", bases, torch.float32, shape=(12, 25), device=pre.device, owner="pre")
+    need("datoms", datoms, torch.float32, shape=(b, h, w, 25, 6), device=pre.device, owner="pre")
+    need("bases", bases, torch.float32, shape=(12, 25), device=pre.device, owner="pre")
     out = torch.empty((b, h, w, 128), dtype=torch.float32, device=pre.device)
-    _launch("v2v_hyper_atoms_bwd_hip", pre.device, _ptr(datoms), _ptr(pre), _ptr(bases), b * h * w, _ptr(out))
+    launch("v2v_hyper_atoms_bwd_hip", pre.device, ptr(datoms), ptr(pre), ptr(bases), b * h * w, ptr(out))
     return out

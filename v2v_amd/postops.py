@@ -7,11 +7,10 @@ Everything runs in the HIP kernels (exact k-th values by radix select); CUDA flo
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._lib import launch, ptr
 
 
 def normalize_and_pad(voxel: torch.Tensor, normalize: bool = True, PAD: int = 16, method: str = "radix", valid_hw=None,
@@ -45,11 +44,7 @@ def normalize_and_pad(voxel: torch.Tensor, normalize: bool = True, PAD: int = 16
     if normalize:
         ws = torch.empty((_lib.lib().v2v_postops_workspace_bytes(b) // 8 + 1,), dtype=torch.int64, device=voxel.device)
     m = _lib.NORM_NONE if not normalize else (_lib.NORM_COUNT if method == "count" else _lib.NORM_RADIX)
-    with torch.cuda.device(voxel.device):
-        rc = _lib.lib().v2v_normalize_pad_ex_hip(C.c_void_p(voxel.data_ptr()), b, t * c, h, w, h_in, w_in, m, PAD,
-                                                 C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()) if ws is not None else None,
-                                                 _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_normalize_pad_ex_hip", voxel.device, ptr(voxel), b, t * c, h, w, h_in, w_in, m, PAD, ptr(out), ptr(ws))
     return out
 
 
@@ -70,10 +65,7 @@ def scales_from_stats(stats: torch.Tensor, elems_per_sample: int) -> torch.Tenso
     if stats.dtype != torch.int32 or stats.ndim != 2 or stats.shape[1] != _lib.VOXEL_STATS_WORDS or not stats.is_cuda or not stats.is_contiguous():
         raise ValueError(f"stats must be a contiguous int32 CUDA tensor [B,{_lib.VOXEL_STATS_WORDS}]")
     scales = torch.empty((stats.shape[0], 2), dtype=torch.float32, device=stats.device)
-    with torch.cuda.device(stats.device):
-        rc = _lib.lib().v2v_voxel_scales_hip(C.c_void_p(stats.data_ptr()), stats.shape[0], int(elems_per_sample), C.c_void_p(scales.data_ptr()),
-                                             _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_voxel_scales_hip", stats.device, ptr(stats), stats.shape[0], int(elems_per_sample), ptr(scales))
     return scales
 
 
@@ -95,11 +87,7 @@ def apply_scales(voxel: torch.Tensor, scales, PAD: int = 16, valid_hw=None, inpl
         out = voxel
     else:
         out = torch.empty((b, t, c, hp, wp), dtype=torch.float32, device=voxel.device)
-    with torch.cuda.device(voxel.device):
-        rc = _lib.lib().v2v_voxel_apply_scales_hip(C.c_void_p(voxel.data_ptr()), b, t * c, h, w, h_in, w_in, PAD,
-                                                   C.c_void_p(scales.data_ptr()) if scales is not None else None, C.c_void_p(out.data_ptr()),
-                                                   _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_voxel_apply_scales_hip", voxel.device, ptr(voxel), b, t * c, h, w, h_in, w_in, PAD, ptr(scales), ptr(out))
     return out
 
 
@@ -114,9 +102,6 @@ def voxel_scales_radix(voxel: torch.Tensor, method: str = "radix", valid_hw=None
     h, w = valid_hw if valid_hw is not None else (h_in, w_in)
     ws = torch.empty((_lib.lib().v2v_postops_workspace_bytes(b) // 8 + 1,), dtype=torch.int64, device=voxel.device)
     scales = torch.empty((b, 2), dtype=torch.float32, device=voxel.device)
-    with torch.cuda.device(voxel.device):
-        rc = _lib.lib().v2v_voxel_scales_select_hip(C.c_void_p(voxel.data_ptr()), b, t * c, h, w, h_in, w_in,
-                                                    _lib.NORM_COUNT if method == "count" else _lib.NORM_RADIX, C.c_void_p(scales.data_ptr()),
-                                                    C.c_void_p(ws.data_ptr()), _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_voxel_scales_select_hip", voxel.device, ptr(voxel), b, t * c, h, w, h_in, w_in,
+           _lib.NORM_COUNT if method == "count" else _lib.NORM_RADIX, ptr(scales), ptr(ws))
     return scales

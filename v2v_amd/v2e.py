@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .esim import BIN_MODES, _OUT, _TORCH_IN
+from ._lib import DTYPE_CODES, launch, ptr
+from .esim import BIN_MODES, _OUT, _TORCH_IN, _code
 
 
 def make_params(FPS, threshold_model, thres_mean_mean, thres_mean_std, thres_diff_mean, thres_diff_std, cutoff_hz,
@@ -91,15 +92,11 @@ def v2e_voxel_batch(frames: torch.Tensor, params: _lib.V2EParams, *, bin_mode: s
     if counts is not None and (counts.dtype != torch.int64 or tuple(counts.shape) != (b, 2) or not counts.is_contiguous()
                                or counts.device != dev):
         raise ValueError("counts must be a contiguous int64 [B,2] tensor on the frames' device")
-    with torch.cuda.device(dev):
-        rc = _lib.lib().v2v_v2e_voxel_hip(
-            C.c_void_p(frames.data_ptr()), _TORCH_IN[frames.dtype], b, n, h, w,
-            frames.stride(0) if b > 1 else n * frames.stride(1), frames.stride(1), C.byref(params), mode,
-            C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint64(clip_id0), C.byref(rp) if rp is not None else None,
-            BIN_MODES[bin_mode], num_bins, frames_per_bin, C.c_void_p(out.data_ptr()), _OUT[out.dtype],
-            C.c_void_p(counts.data_ptr()) if counts is not None else None,
-            C.c_void_p(ws.data_ptr()) if ws is not None else None, _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_v2e_voxel_hip", dev,
+           ptr(frames), DTYPE_CODES[frames.dtype], b, n, h, w,
+           frames.stride(0) if b > 1 else n * frames.stride(1), frames.stride(1), C.byref(params), mode,
+           C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint64(clip_id0), C.byref(rp) if rp is not None else None,
+           BIN_MODES[bin_mode], num_bins, frames_per_bin, ptr(out), _code(_OUT, out.dtype), ptr(counts), ptr(ws))
     return out
 
 

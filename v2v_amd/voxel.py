@@ -11,18 +11,22 @@ NumPy in -> NumPy float64 out; CUDA tensors in -> CUDA float64 tensor out.  The 
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._lib import launch, ptr
 
 
 def _dev(x, dtype, device):
     if isinstance(x, torch.Tensor):
         return x.to(device=device, dtype=dtype).contiguous().reshape(-1)
     return torch.as_tensor(np.ascontiguousarray(np.asarray(x).reshape(-1)), device=device).to(dtype)
+
+
+def _events(n, *tensors):
+    """The event pointers of a launch: NULL for an empty list (an empty tensor has no address)."""
+    return [ptr(t) if n else None for t in tensors]
 
 
 def _scatter(ts, xs, ys, ps, mode, num_bins, h, w, device, check_bounds=True):
@@ -36,12 +40,7 @@ def _scatter(ts, xs, ys, ps, mode, num_bins, h, w, device, check_bounds=True):
         raise AssertionError("len(xs)==len(ys)==len(ts)==len(ps) violated")      # event_utils.py:710
     out = torch.empty((num_bins, h, w), dtype=torch.float64, device=device)
     dropped = torch.empty((1,), dtype=torch.int64, device=device)
-    with torch.cuda.device(out.device):
-        rc = _lib.lib().v2v_events_to_voxel_hip(
-            C.c_void_p(ts_d.data_ptr()) if n else None, C.c_void_p(xs_d.data_ptr()) if n else None,
-            C.c_void_p(ys_d.data_ptr()) if n else None, C.c_void_p(ps_d.data_ptr()) if n else None, n, mode, num_bins,
-            h, w, C.c_void_p(out.data_ptr()), C.c_void_p(dropped.data_ptr()), _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_events_to_voxel_hip", out.device, *_events(n, ts_d, xs_d, ys_d, ps_d), n, mode, num_bins, h, w, ptr(out), ptr(dropped))
     if check_bounds and n and int(dropped.item()) != 0:
         raise IndexError(f"{int(dropped.item())} event(s) outside the {h}x{w} sensor / {num_bins} bins")   # np.add.at would raise
     return out
@@ -95,13 +94,7 @@ def events_to_voxel_torch(xs, ys, ts, ps, B, device=None, sensor_size=(180, 240)
     h, w = sensor_size
     out = torch.empty((B, h, w), dtype=torch.float32, device=dev)
     dropped = torch.empty((1,), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().v2v_events_to_voxel_f32_hip(
-            C.c_void_p(ts_d.data_ptr()) if n else None, C.c_void_p(xs_d.data_ptr()) if n else None,
-            C.c_void_p(ys_d.data_ptr()) if n else None, C.c_void_p(ps_d.data_ptr()) if n else None, n,
-            0 if temporal_bilinear else 1, B, h, w, C.c_void_p(out.data_ptr()), C.c_void_p(dropped.data_ptr()),
-            _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_events_to_voxel_f32_hip", dev, *_events(n, ts_d, xs_d, ys_d, ps_d), n, 0 if temporal_bilinear else 1, B, h, w, ptr(out), ptr(dropped))
     if n and int(dropped.item()) != 0:
         raise IndexError(f"{int(dropped.item())} event(s) outside the sensor / bin range")
     return out
@@ -156,11 +149,7 @@ def _scatter_f32(xs_d, ys_d, w_d, h, w, dev):
     out = torch.empty((1, h, w), dtype=torch.float32, device=dev)
     dropped = torch.empty((1,), dtype=torch.int64, device=dev)
     ts_d = torch.zeros((max(n, 1),), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().v2v_events_to_voxel_f32_hip(C.c_void_p(ts_d.data_ptr()) if n else None, C.c_void_p(xs_d.data_ptr()) if n else None,
-                                                    C.c_void_p(ys_d.data_ptr()) if n else None, C.c_void_p(w_d.data_ptr()) if n else None, n, 1, 1, h, w,
-                                                    C.c_void_p(out.data_ptr()), C.c_void_p(dropped.data_ptr()), _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_events_to_voxel_f32_hip", dev, *_events(n, ts_d, xs_d, ys_d, w_d), n, 1, 1, h, w, ptr(out), ptr(dropped))
     if n and int(dropped.item()) != 0:
         raise IndexError(f"{int(dropped.item())} event(s) outside the {h}x{w} image")   # index_put_ would raise
     return out[0]
@@ -217,12 +206,8 @@ def _grids_of_ranges(xs, ys, ts, ps, B, ranges, device, sensor_size, temporal_bi
         h, w = sensor_size
         out = torch.empty((len(ranges), B, h, w), dtype=torch.float32, device=dev)
         dropped = torch.empty((1,), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().v2v_events_to_voxel_f32_segmented_hip(
-                C.c_void_p(ts_d.data_ptr()), C.c_void_p(xs_d.data_ptr()), C.c_void_p(ys_d.data_ptr()), C.c_void_p(ps_d.data_ptr()), hi - lo,
-                C.c_void_p(seg.data_ptr()), len(ranges), 0, 0 if temporal_bilinear else 1, B, h, w, C.c_void_p(out.data_ptr()),
-                C.c_void_p(dropped.data_ptr()), _lib.stream_ptr())
-        _lib.check(rc)
+        launch("v2v_events_to_voxel_f32_segmented_hip", dev, ptr(ts_d), ptr(xs_d), ptr(ys_d), ptr(ps_d), hi - lo,
+               ptr(seg), len(ranges), 0, 0 if temporal_bilinear else 1, B, h, w, ptr(out), ptr(dropped))
         if int(dropped.item()) != 0:
             raise IndexError(f"{int(dropped.item())} event(s) outside the sensor / bin range")
         return list(out.unbind(0))
@@ -278,13 +263,7 @@ def make_voxels_segmented(evs, event_idx, H, W, num_bins=5, interpolate_bins=Fal
     out = torch.empty((f, num_bins, H, W), dtype=torch.float64, device=ts_d.device)
     dropped = torch.empty((1,), dtype=torch.int64, device=ts_d.device)
     mode = _lib.EV_MAKE_VOXEL_INTERP if interpolate_bins else _lib.EV_MAKE_VOXEL_DISCRETE
-    with torch.cuda.device(out.device):
-        rc = _lib.lib().v2v_events_to_voxel_segmented_hip(
-            C.c_void_p(ts_d.data_ptr()) if n else None, C.c_void_p(xs_d.data_ptr()) if n else None,
-            C.c_void_p(ys_d.data_ptr()) if n else None, C.c_void_p(ps_d.data_ptr()) if n else None, n,
-            C.c_void_p(seg.data_ptr()), f, mode, num_bins, H, W, C.c_void_p(out.data_ptr()), C.c_void_p(dropped.data_ptr()),
-            _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_events_to_voxel_segmented_hip", out.device, *_events(n, ts_d, xs_d, ys_d, ps_d), n, ptr(seg), f, mode, num_bins, H, W, ptr(out), ptr(dropped))
     if n and int(dropped.item()) != 0:
         raise IndexError(f"{int(dropped.item())} event(s) outside the {H}x{W} sensor / {num_bins} bins")
     return out.cpu().numpy() if is_np else out

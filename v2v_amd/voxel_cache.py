@@ -10,12 +10,11 @@ h5py when it is installed, else as an .npz with the same names.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib, monash
+from ._lib import launch, ptr
 
 
 def sequence_voxels(path, num_bins=5, temporal_bilinear=False, device="cuda"):
@@ -45,13 +44,8 @@ def sequence_voxels(path, num_bins=5, temporal_bilinear=False, device="cuda"):
     out = torch.empty((length, num_bins, h, w), dtype=torch.float32, device=dev)
     dropped = torch.empty((1,), dtype=torch.int64, device=dev)
     t_d, x_d, y_d, p_d, s_d = (torch.as_tensor(a, device=dev) for a in (ts, xs, ys, ps, seg))
-    with torch.cuda.device(dev):
-        rc = _lib.lib().v2v_events_to_voxel_f32_segmented_hip(
-            C.c_void_p(t_d.data_ptr()) if n_ev else None, C.c_void_p(x_d.data_ptr()) if n_ev else None,
-            C.c_void_p(y_d.data_ptr()) if n_ev else None, C.c_void_p(p_d.data_ptr()) if n_ev else None, n_ev,
-            C.c_void_p(s_d.data_ptr()), length, 3, 0 if temporal_bilinear else 1, num_bins, h, w,
-            C.c_void_p(out.data_ptr()), C.c_void_p(dropped.data_ptr()), _lib.stream_ptr())
-    _lib.check(rc)
+    launch("v2v_events_to_voxel_f32_segmented_hip", dev, *(ptr(t) if n_ev else None for t in (t_d, x_d, y_d, p_d)), n_ev,
+           ptr(s_d), length, 3, 0 if temporal_bilinear else 1, num_bins, h, w, ptr(out), ptr(dropped))
     if n_ev and int(dropped.item()) != 0:
         raise IndexError(f"{int(dropped.item())} event(s) outside the sensor / bin range")
     lo, hi = seg[:-1], seg[1:]

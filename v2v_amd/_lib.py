@@ -1,7 +1,8 @@
-"""ctypes binding of libv2v_hip.so (C ABI in include/v2v_hip.h, v2v_nernet.h, v2v_metrics.h) and the one calling convention every module
+"""ctypes binding of libv2v_hip.so (C ABI in include/v2v_hip.h, v2v_nernet.h, v2v_metrics.h, v2v_lpips_alex.h) and the one calling convention every module
 of the package goes through.  Fails loudly when the library is missing.
 
-    lib()                          the loaded library, one binding table per header (SIGNATURES, NERNET_SIGNATURES, METRICS_SIGNATURES)
+    lib()                          the loaded library, one binding table per header (SIGNATURES, NERNET_SIGNATURES, METRICS_SIGNATURES,
+                                   LPIPS_ALEX_SIGNATURES)
     ptr(t, offset_elems=0)         the address of a tensor as a C pointer argument, None -> NULL
     launch(name, device, *args)    the `_hip` entry point `name` on `device` and torch's current stream there, the stream last, status checked
     need(name, t, dtype, ...)      ValueError unless t is a contiguous CUDA tensor of that dtype and shape
@@ -220,6 +221,17 @@ METRICS_SIGNATURES = {
 }
 METRICS_EXPORTS = tuple(METRICS_SIGNATURES)
 
+# include/v2v_lpips_alex.h: the LPIPS-AlexNet test metric (v2v_amd/lpips_alex.py), likewise a table of its own.
+LPIPS_ALEX_SIGNATURES = {
+    "v2v_lpips_alex_stem_hip": (I, [P, I64, I64, I64, I64, I64, F, I, P, P, P, P, P, P]),
+    "v2v_lpips_alex_conv_hip": (I, [P, P, P, I64, I64, I64, I64, I64, I, I, P, P]),
+    "v2v_lpips_alex_pool_hip": (I, [P, I64, I64, I64, I64, P, P]),
+    "v2v_lpips_alex_compare_workspace_bytes": (I64, [I64, I64]),
+    "v2v_lpips_alex_compare_hip": (I, [P, P, P, I64, I64, I64, I, P, P, P]),
+    "v2v_lpips_alex_sum_hip": (I, [P, I64, P, P]),
+}
+LPIPS_ALEX_EXPORTS = tuple(LPIPS_ALEX_SIGNATURES)
+
 _lib = None
 
 
@@ -232,7 +244,8 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C v2v_amd/csrc`).  v2v_amd has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(NERNET_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(NERNET_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) \
+            + list(LPIPS_ALEX_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     if L.v2v_version() != ABI_VERSION:

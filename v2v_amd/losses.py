@@ -5,7 +5,7 @@ temporal_consistency_loss, including the negated flow.  A V2V user switches with
     from v2v_amd.losses import l1_loss, l2_loss, temporal_consistency_loss, perceptual_loss
 
 perceptual_loss is LPIPS with the vgg backbone (v2v_amd/lpips.py: backbone, normalise / compare and the gradient to pred on the device
-kernels); net='alex' / 'squeeze' stay the reference's.  loss_ops.sequence_losses evaluates all T steps of the three image losses at once,
+kernels); net='alex' as a loss and 'squeeze' stay the reference's (the alex TEST METRIC is v2v_amd.lpips_alex).  loss_ops.sequence_losses evaluates all T steps of the three image losses at once,
 bit-identically; LPIPS has no state in time, a sequence is a batch of N*T images (loss_ops.lpips_vgg)."""
 from __future__ import annotations
 

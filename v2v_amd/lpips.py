@@ -72,7 +72,7 @@ class LPIPSVGG(nn.Module):
     def __init__(self, net: str = "vgg", spatial: bool = False, pnet_tune: bool = False, chunk: int = DEFAULT_CHUNK):
         super().__init__()
         if net not in ("vgg", "vgg16"):
-            raise ValueError(f"LPIPSVGG runs the vgg backbone only (got net={net!r}); alex and squeeze stay the reference's")
+            raise ValueError(f"LPIPSVGG runs the vgg backbone only (got net={net!r}); alex is v2v_amd.lpips_alex.LPIPSAlex, squeeze stays the reference's")
         if spatial or pnet_tune:
             raise ValueError("LPIPSVGG has no spatial=True map and a frozen backbone (pnet_tune=False)")
         if int(chunk) < 1:

@@ -9,7 +9,8 @@
 
 The reference divides both frames by 255 in float32, takes F.mse_loss on the device, copies both frames to the host and runs
 skimage.metrics.structural_similarity(data_range=2) there, frame by frame; the kernels do the same arithmetic with every moment in float64.
-Single channel only; the LPIPS-alex network is not part of this module (pass the reference's own as `lpips_fn`).  No CPU path.
+Single channel only.  The LPIPS-alex network is v2v_amd.lpips_alex.LPIPSAlex: handed to compute_metrics as `lpips_fn` it takes all T frames
+in one batched pass; any other callable (the reference's own module) is called frame by frame.  No CPU path.
 """
 from __future__ import annotations
 
@@ -113,15 +114,18 @@ def _log_prefix(batch):
 
 def compute_metrics(pred, batch, lpips_fn=None):
     """ModelInterface.compute_metrics: pred and batch["frame"] [1,T,1,H,W] -> {"SOURCE/sequence/MSE": [T floats], ".../SSIM": [...]} and
-    ".../LPIPS" when lpips_fn is given (called as the reference calls its own: lpips_fn(pred / 255, frame / 255, normalize=True) per frame).
-    One device-to-host copy."""
+    ".../LPIPS" when lpips_fn is given: a v2v_amd.lpips_alex.LPIPSAlex runs all T frames in one batched pass (its `sequence`); any other
+    callable is called as the reference calls its own, lpips_fn(pred / 255, frame / 255, normalize=True) per frame.  One device-to-host copy."""
     _lib.require_gpu()
     frame = batch["frame"]
     if frame.dim() != 5 or frame.shape[0] != 1:
         raise ValueError("Batch size must be 1 for testing.")
     prefix = _log_prefix(batch)
     cols = [image_metrics(pred, frame)]
-    if lpips_fn is not None:
+    from .lpips_alex import LPIPSAlex   # here, not at the top: this module's names stay what they are
+    if isinstance(lpips_fn, LPIPSAlex):
+        cols.append(lpips_fn.sequence(pred, frame).double().reshape(-1, 1))
+    elif lpips_fn is not None:
         lp = [lpips_fn(pred[0, t] / 255, frame[0, t] / 255, normalize=True).reshape(()) for t in range(frame.shape[1])]
         cols.append(torch.stack(lp).double().reshape(-1, 1) if lp else torch.empty((0, 1), dtype=torch.float64, device=frame.device))
     host = torch.cat(cols, dim=1).cpu().numpy()

@@ -1,8 +1,8 @@
-"""ctypes binding of libv2v_hip.so (C ABI in include/v2v_hip.h, v2v_nernet.h, v2v_metrics.h, v2v_lpips_alex.h) and the one calling convention every module
+"""ctypes binding of libv2v_hip.so (C ABI in include/v2v_hip.h, v2v_nernet.h, v2v_metrics.h, v2v_lpips_alex.h, v2v_alex_train.h) and the one calling convention every module
 of the package goes through.  Fails loudly when the library is missing.
 
     lib()                          the loaded library, one binding table per header (SIGNATURES, NERNET_SIGNATURES, METRICS_SIGNATURES,
-                                   LPIPS_ALEX_SIGNATURES)
+                                   LPIPS_ALEX_SIGNATURES, ALEX_TRAIN_SIGNATURES)
     ptr(t, offset_elems=0)         the address of a tensor as a C pointer argument, None -> NULL
     launch(name, device, *args)    the `_hip` entry point `name` on `device` and torch's current stream there, the stream last, status checked
     need(name, t, dtype, ...)      ValueError unless t is a contiguous CUDA tensor of that dtype and shape
@@ -232,6 +232,16 @@ LPIPS_ALEX_SIGNATURES = {
 }
 LPIPS_ALEX_EXPORTS = tuple(LPIPS_ALEX_SIGNATURES)
 
+# include/v2v_alex_train.h: LPIPS-AlexNet's backward to the prediction (v2v_amd/lpips_alex.py).  A table of its own once more: the
+# v2v_lpips_alex_* family above is pinned name by name.
+ALEX_TRAIN_SIGNATURES = {
+    "v2v_alex_train_compare_bwd_hip": (I, [P, P, P, P, I64, I64, I64, I, P, P]),
+    "v2v_alex_train_conv_dgrad_hip": (I, [P, P, P, P, I64, I64, I64, I64, I64, I, P, P]),
+    "v2v_alex_train_pool_bwd_hip": (I, [P, P, P, I64, I64, I64, I64, I, P, P]),
+    "v2v_alex_train_stem_bwd_hip": (I, [P, P, P, I64, I64, I64, I64, F, I, P, P]),
+}
+ALEX_TRAIN_EXPORTS = tuple(ALEX_TRAIN_SIGNATURES)
+
 _lib = None
 
 
@@ -245,7 +255,7 @@ def lib():
             "(or `make -C v2v_amd/csrc`).  v2v_amd has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(NERNET_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) \
-            + list(LPIPS_ALEX_SIGNATURES.items()):
+            + list(LPIPS_ALEX_SIGNATURES.items()) + list(ALEX_TRAIN_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     if L.v2v_version() != ABI_VERSION:

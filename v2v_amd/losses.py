@@ -5,12 +5,14 @@ temporal_consistency_loss, including the negated flow.  A V2V user switches with
     from v2v_amd.losses import l1_loss, l2_loss, temporal_consistency_loss, perceptual_loss
 
 perceptual_loss is LPIPS with the vgg backbone (v2v_amd/lpips.py: backbone, normalise / compare and the gradient to pred on the device
-kernels); net='alex' as a loss and 'squeeze' stay the reference's (the alex TEST METRIC is v2v_amd.lpips_alex).  loss_ops.sequence_losses evaluates all T steps of the three image losses at once,
+kernels).  perceptual_loss_alex is the same class for `lpips_type: alex` (v2v_amd/lpips_alex.py, float32); a configuration that trains
+with it imports `perceptual_loss_alex as perceptual_loss`.  'squeeze' stays the reference's.  loss_ops.sequence_losses evaluates all T steps of the three image losses at once,
 bit-identically; LPIPS has no state in time, a sequence is a batch of N*T images (loss_ops.lpips_vgg)."""
 from __future__ import annotations
 
 from .loss_ops import L1, L2, TC, MAPS, PairLossFn, sequence_losses  # noqa: F401
 from .lpips import LPIPSVGG
+from .lpips_alex import LPIPSAlex
 
 
 def _pointwise(row, weight, pred, target, reduce_batch):
@@ -114,3 +116,59 @@ class perceptual_loss():
         if reduce_batch:
             return self.weight * dist.mean()
         return self.weight * dist
+
+
+def _reference_lpips_alex_state():
+    """The weights the reference trains with under lpips_type: alex: torchvision's pretrained alexnet features under PNetLin's `net.slice*`
+    keys + the five linear layers of PerceptualSimilarity/models/weights/v0.1/alex.pth.  RuntimeError naming what is missing."""
+    import os
+
+    import torch
+    from .lpips_alex import CONVS
+    hint = "pass state_dict= (a PNetLin state dict) instead"
+    try:
+        from torchvision import models as tv
+    except ImportError as e:
+        raise RuntimeError("perceptual_loss_alex(state_dict=None) takes the backbone from torchvision.models.alexnet(pretrained=True), and "
+                           f"torchvision is not importable here; {hint}") from e
+    try:
+        import PerceptualSimilarity
+    except ImportError as e:
+        raise RuntimeError("perceptual_loss_alex(state_dict=None) takes the linear layers from the PerceptualSimilarity package's "
+                           f"models/weights/v0.1/alex.pth, and that package is not importable here; {hint}") from e
+    path = os.path.join(os.path.dirname(os.path.abspath(PerceptualSimilarity.__file__)), "models", "weights", "v0.1", "alex.pth")
+    if not os.path.exists(path):
+        raise RuntimeError(f"perceptual_loss_alex(state_dict=None): {path} is missing; {hint}")
+    features = tv.alexnet(pretrained=True).features.state_dict()
+    state = {f"net.slice{s}.{idx}.{p}": features[f"{idx}.{p}"] for s, idx, *_ in CONVS for p in ("weight", "bias")}
+    state.update(torch.load(path, map_location="cpu"))
+    return state
+
+
+class perceptual_loss_alex():
+    def __init__(self, weight=1.0, net='alex', use_gpu=True, state_dict=None):
+        """
+        model/loss.py:95-119 with net='alex' (the reference's default, and what its `lpips_type: alex` configurations train with) on the
+        device kernels, float32, gradient to pred only.
+        state_dict: a PNetLin state dict (17 keys; without scaling_layer.* the reference's constants stay); None assembles the
+        reference's own weights from torchvision and the PerceptualSimilarity package.
+        """
+        self.model = LPIPSAlex(net=net)
+        state = dict(_reference_lpips_alex_state() if state_dict is None else state_dict)
+        for k, v in self.model.scaling_layer.state_dict().items():
+            state.setdefault(f"scaling_layer.{k}", v)
+        self.model.load_state_dict(state, strict=True)
+        if use_gpu:
+            self.model.cuda()
+        self.weight = weight
+
+    def __call__(self, pred, target, normalize=True, reduce_batch=True):
+        """
+        pred and target are float32 Tensors with shape N x C x H x W (C {1, 3}, H and W >= 31); one channel stands for three equal ones
+        normalize scales images from [0, 1] to [-1, 1] (default: True)
+        returns weight * mean over the batch, or weight * dist [N] with reduce_batch=False
+        """
+        dist = self.model(pred, target, normalize=normalize)
+        if reduce_batch:
+            return self.weight * dist.mean()
+        return self.weight * dist.reshape(-1)

@@ -1,19 +1,28 @@
 """LPIPS-AlexNet, the third metric of the reference's test loop (PerceptualSimilarity/models/networks_basic.py:PNetLin with pnet_type='alex',
-version '0.1', spatial=False; ModelInterface.compute_metrics, model/train_utils.py:198, 236), forward only, on the device kernels of
-v2v_amd/csrc/v2v_alex.hpp (include/v2v_lpips_alex.h).
+version '0.1', spatial=False; ModelInterface.compute_metrics, model/train_utils.py:198, 236; as a training loss model/loss.py:95-119 with
+net='alex'), on the device kernels of v2v_amd/csrc/v2v_alex.hpp (include/v2v_lpips_alex.h) and, for the backward to pred, of
+v2v_amd/csrc/v2v_alex_train.hpp (include/v2v_alex_train.h).
 
     LPIPSAlex()                                  the network under the reference's 17 state_dict keys (PerceptualLoss(net="alex").model.net's
                                                  state dict loads strict): scaling_layer.shift / scale, net.slice{1..5}.{idx}.{weight,bias},
                                                  lin{0..4}.model.1.weight
-    LPIPSAlex.forward(pred, target, normalize)   float32 [B,1,1,1] as the reference returns it: a drop-in `lpips_fn`
+    LPIPSAlex.forward(pred, target, normalize)   float32 [B,1,1,1] as the reference returns it: a drop-in `lpips_fn`; differentiable with
+                                                 respect to pred when pred requires grad (the loss: v2v_amd.losses.perceptual_loss_alex)
     LPIPSAlex.sequence(pred, frame, ...)         all T frames of a sequence: float32 [T] on the device (and the float64 tap means [T,5]), a
                                                  handful of launches per chunk, no host synchronisation
     stem / conv / pool / compare / tap_sum       the raw operators, one per kernel
+    compare_bwd / conv_dgrad / pool_bwd / stem_bwd   the raw operators of the backward; pack_dgrad_weights
     tap_sizes(h, w)                              the five (H, W) of the taps
 
 A metric, so float32 end to end: float32 NHWC activations, float32 weights, float32 accumulation on the float32-input matrix-core
 instruction (a k-ordered fmaf chain), norms and sums in float64.  No split-K and nothing that depends on how many images share a launch:
-per-frame results do not depend on T or on the chunk, bit for bit.  Frozen and always in eval mode.  No CPU path, no autograd."""
+per-frame results do not depend on T or on the chunk, bit for bit.  Frozen and always in eval mode.  No CPU path.  The gradient goes to
+pred only, float32, through kernels under the same rules (one fixed summation order per element, no atomics): two backward runs agree
+bit for bit, for any chunk.  sequence() is a metric and records no gradient.  The path that records the gradient cuts the batch into
+chunks of grad_chunk images (default 480, fewer for large frames: GRAD_CHUNK_ELEMS), the metric paths into chunks of `chunk` (40).
+
+Deviation from autograd, stated (as v2v_amd/lpips.py does for vgg): at a pixel whose pred features are ALL zero at a tap the reference's
+gradient is NaN (sqrt' at 0); here the norm's derivative is taken as 0 there."""
 from __future__ import annotations
 
 import torch
@@ -30,6 +39,8 @@ CONVS = ((1, 0, 3, 64, 11, 4, 2, False), (2, 3, 64, 192, 5, 1, 2, True), (3, 6, 
 CHANNELS = (64, 192, 384, 256, 256)
 MIN_SIDE = 31                       # 31 -> 7 -> 3 -> 1
 DEFAULT_CHUNK = 40                  # the frames of a test sequence: one launch per layer
+DEFAULT_GRAD_CHUNK = 480            # as a loss: the 12 x 40 images of a training sequence, one launch per layer (40 images leave the GPU half idle)
+GRAD_CHUNK_ELEMS = 1 << 28          # ... but no more images than keep the first tap of a chunk (pred and target) within 2^28 floats
 
 
 def tap_sizes(h: int, w: int):
@@ -131,6 +142,84 @@ def tap_sum(taps: torch.Tensor, out=None):
     return out
 
 
+# ---- raw operators of the backward to pred (include/v2v_alex_train.h) --------------------------------------------------------------------
+def pack_dgrad_weights(w: torch.Tensor) -> torch.Tensor:
+    """[Cout,Cin,KS,KS] -> float32 [KS*KS*Cout, Cin]: row (ky * KS + kx) * Cout + co holds w[co][:][KS-1-ky][KS-1-kx] -- the forward's
+    implicit GEMM run over dy gives the input gradient."""
+    cout, cin, ks, _ = w.shape
+    return w.detach().to(torch.float32).flip(2, 3).permute(2, 3, 0, 1).reshape(ks * ks * cout, cin).contiguous()
+
+
+def compare_bwd(f0: torch.Tensor, f1: torch.Tensor, w: torch.Tensor, ddist: torch.Tensor, relu_mask: bool = False):
+    """f0 (pred), f1 (target) float32 NHWC [n,H,W,C], w [C], ddist float32 [n] or [n,1,1,1] -> float32 [n,H,W,C]: the gradient of
+    sum_i ddist_i * (tap mean of image i) at f0, per pixel in float64, rounded once; relu_mask: 0 where f0 is not > 0.  Always a fresh
+    buffer: a tap's gradient joins the chain as the `dtap` of conv_dgrad / pool_bwd, nothing accumulates in place."""
+    _lib.require_gpu()
+    need("f0", f0, torch.float32)
+    need("f1", f1, torch.float32, shape=tuple(f0.shape), device=f0.device, owner="f0")
+    n, h, wd, c = f0.shape
+    if not isinstance(ddist, torch.Tensor) or tuple(ddist.shape) not in ((n,), (n, 1, 1, 1)):
+        raise ValueError(f"ddist must be float32 [{n}] or [{n},1,1,1]")
+    dz = torch.empty_like(f0)
+    launch("v2v_alex_train_compare_bwd_hip", f0.device, ptr(f0), ptr(f1), ptr(_vec("w", w, c, f0.device)), ptr(_vec("ddist", ddist, n, f0.device)), n, h * wd, c,
+           int(bool(relu_mask)), ptr(dz))
+    return dz
+
+
+def conv_dgrad(dy: torch.Tensor, packed: torch.Tensor, ks: int, dtap=None, mask=None):
+    """dy float32 NHWC [n,H,W,Cout], packed = pack_dgrad_weights(w) [ks*ks*Cout, Cin] -> dx float32 [n,H,W,Cin] = the input gradient of the
+    stride-1 convolution + dtap, 0 where mask (the post-ReLU activation that fed the convolution) is not > 0; both optional, [n,H,W,Cin]."""
+    _lib.require_gpu()
+    need("dy", dy, torch.float32)
+    n, h, w, cout = dy.shape
+    if packed.dim() != 2 or packed.shape[0] != ks * ks * cout:
+        raise ValueError(f"packed must be [{ks * ks * cout}, Cin] (got {tuple(packed.shape)})")
+    cin = packed.shape[1]
+    need("packed", packed, torch.float32, shape=(ks * ks * cout, cin), device=dy.device, owner="dy")
+    for name, t in (("dtap", dtap), ("mask", mask)):
+        if t is not None:
+            need(name, t, torch.float32, shape=(n, h, w, cin), device=dy.device, owner="dy")
+    dx = torch.empty((n, h, w, cin), dtype=torch.float32, device=dy.device)
+    launch("v2v_alex_train_conv_dgrad_hip", dy.device, ptr(dy), ptr(packed), ptr(dtap), ptr(mask), n, h, w, cin, cout, int(ks), ptr(dx))
+    return dx
+
+
+def pool_bwd(x: torch.Tensor, dy: torch.Tensor, dtap=None, relu_mask: bool = False):
+    """x float32 NHWC [n,H,W,C] (the pool's input), dy [n,(H-3)//2+1,(W-3)//2+1,C] -> dx [n,H,W,C]: dy gathered at each window's first
+    maximum, + dtap (optional, like x), 0 where x is not > 0 when relu_mask."""
+    _lib.require_gpu()
+    need("x", x, torch.float32)
+    n, h, w, c = x.shape
+    if h < 3 or w < 3:
+        raise ValueError(f"the 3x3 pool needs H, W >= 3 (got {h}x{w})")
+    need("dy", dy, torch.float32, shape=(n, (h - 3) // 2 + 1, (w - 3) // 2 + 1, c), device=x.device)
+    if dtap is not None:
+        need("dtap", dtap, torch.float32, shape=tuple(x.shape), device=x.device)
+    dx = torch.empty_like(x)
+    launch("v2v_alex_train_pool_bwd_hip", x.device, ptr(x), ptr(dy), ptr(dtap), n, h, w, c, int(bool(relu_mask)), ptr(dx))
+    return dx
+
+
+def stem_bwd(dz: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, cin: int, h: int, w: int, divisor: float = 1.0, normalize: bool = False, out=None):
+    """dz float32 NHWC [n,OH,OW,64] (the gradient at the stem's pre-activation), packed = pack_stem_weights(w) -> float32 [n,cin,h,w]: the
+    gradient at the frames stem() read with the same divisor / normalize."""
+    _lib.require_gpu()
+    need("dz", dz, torch.float32)
+    n = dz.shape[0]
+    (oh, ow) = tap_sizes(h, w)[0]
+    dev = dz.device
+    need("dz", dz, torch.float32, shape=(n, oh, ow, 64))
+    need("packed", packed, torch.float32, shape=(3, 122, 64), device=dev, owner="dz")
+    if cin not in (1, 3):
+        raise ValueError(f"cin must be 1 or 3 (got {cin})")
+    if out is None:
+        out = torch.empty((n, cin, h, w), dtype=torch.float32, device=dev)
+    need("out", out, torch.float32, shape=(n, cin, h, w), device=dev, owner="dz")
+    launch("v2v_alex_train_stem_bwd_hip", dev, ptr(dz), ptr(packed), ptr(_vec("scale", scale, 3, dev)), n, int(cin), int(h), int(w), float(divisor),
+           int(bool(normalize)), ptr(out))
+    return out
+
+
 # ---- the module --------------------------------------------------------------------------------------------------------------------------
 class _Lin(nn.Module):
     """NetLinLayer (networks_basic.py:113-120): Dropout (never active) + 1x1 convolution to one channel without bias, key `model.1.weight`."""
@@ -177,19 +266,20 @@ def _images(name, t):
 
 
 class LPIPSAlex(nn.Module):
-    def __init__(self, net: str = "alex", spatial: bool = False, chunk: int = DEFAULT_CHUNK):
+    def __init__(self, net: str = "alex", spatial: bool = False, chunk: int = DEFAULT_CHUNK, grad_chunk: int = DEFAULT_GRAD_CHUNK):
         super().__init__()
         if net != "alex":
             raise ValueError(f"LPIPSAlex runs the alex backbone only (got net={net!r}); vgg is v2v_amd.lpips.LPIPSVGG")
         if spatial:
             raise ValueError("LPIPSAlex has no spatial=True map")
-        if int(chunk) < 1:
-            raise ValueError("chunk must be at least 1")
+        if int(chunk) < 1 or int(grad_chunk) < 1:
+            raise ValueError("chunk and grad_chunk must be at least 1")
         self.scaling_layer = _Scaling()
         self.net = _Backbone()
         for k, c in enumerate(CHANNELS):
             setattr(self, f"lin{k}", _Lin(c))
-        self.chunk = int(chunk)
+        self.chunk = int(chunk)                                         # images per backbone launch of the metric paths
+        self.grad_chunk = int(grad_chunk)                               # ... of the path that records the gradient (results do not depend on either)
         self._packed = {}                                              # nhwc_ops.packed_weights' cache
         for p in self.parameters():
             p.requires_grad_(False)
@@ -217,22 +307,42 @@ class LPIPSAlex(nn.Module):
         scale = packed_weights(self._packed, "scale", sc.scale, lambda v: v.to(torch.float32).reshape(-1).contiguous())
         return convs, lins, shift, scale
 
-    def _chunk(self, pred, ps, target, ts, divisor, normalize, taps):
-        """taps float64 [c,5] <- the five tap means of c image pairs; both images of a pair go through the backbone in one batch of 2 c."""
+    def _chunk(self, pred, ps, target, ts, divisor, normalize, taps, save=False):
+        """taps float64 [c,5] <- the five tap means of c image pairs; both images of a pair go through the backbone in one batch of 2 c.
+        save: returns the five (pred, target) post-ReLU taps, what _chunk_backward reads."""
         c, _, h, w = pred.shape
         convs, lins, shift, scale = self._weights()
         (oh, ow) = tap_sizes(h, w)[0]
         x = torch.empty((2 * c, oh, ow, 64), dtype=torch.float32, device=pred.device)
         for half, img, stride in ((x[:c], pred, ps), (x[c:], target, ts)):
             stem(img, stride, *convs[0], shift, scale, divisor, normalize, out=half)
+        saved = []
         for k, (_, _, _, _, ks, _, _, pooled) in enumerate(CONVS):
             if k:
                 if pooled:
                     x = pool(x)
                 x = conv(x, *convs[k], ks, relu=True)
             compare(x[:c], x[c:], lins[k], k, taps)
+            if save:
+                saved.append((x[:c], x[c:]))
+        return saved
 
-    def _run(self, pred, ps, target, ts, divisor, normalize, chunk):
+    def _chunk_backward(self, saved, ddist, cin, h, w, divisor, normalize, out):
+        """out float32 [c,cin,h,w] <- the gradient of sum_i ddist_i * dist_i at the c predictions of a chunk.  A tap's compare gradient is
+        a buffer of its own (`dtap`) that the kernel of the layer above adds in its epilogue, where the tap's ReLU is applied too."""
+        convs, lins, _, scale = self._weights()
+        dgrad = [None] + [packed_weights(self._packed, f"dgrad{idx}", self._conv(s, idx).weight, pack_dgrad_weights) for s, idx, *_ in CONVS[1:]]
+        tap = lambda k, relu=False: compare_bwd(*saved[k], lins[k], ddist, relu_mask=relu)   # noqa: E731
+        d = tap(4, relu=True)                                           # at conv5's pre-activation
+        d = conv_dgrad(d, dgrad[4], 3, dtap=tap(3), mask=saved[3][0])   # at conv4's
+        d = conv_dgrad(d, dgrad[3], 3, dtap=tap(2), mask=saved[2][0])   # at conv3's
+        d = conv_dgrad(d, dgrad[2], 3)                                  # at the second pool's output
+        d = pool_bwd(saved[1][0], d, dtap=tap(1), relu_mask=True)       # at conv2's pre-activation
+        d = conv_dgrad(d, dgrad[1], 5)                                  # at the first pool's output
+        d = pool_bwd(saved[0][0], d, dtap=tap(0), relu_mask=True)       # at the stem's pre-activation
+        return stem_bwd(d, convs[0][0], scale, cin, h, w, divisor, normalize, out=out)
+
+    def _run(self, pred, ps, target, ts, divisor, normalize, chunk, save=False):
         if pred.shape != target.shape:
             raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
         if pred.device != target.device or self.scaling_layer.shift.device != pred.device:
@@ -245,16 +355,25 @@ class LPIPSAlex(nn.Module):
         n = pred.shape[0]
         taps = torch.empty((n, 5), dtype=torch.float64, device=pred.device)
         dist = torch.empty((n,), dtype=torch.float32, device=pred.device)
-        for i in range(0, n, chunk):
-            self._chunk(pred[i:i + chunk], ps, target[i:i + chunk], ts, divisor, normalize, taps[i:i + chunk])
+        saved = [self._chunk(pred[i:i + chunk], ps, target[i:i + chunk], ts, divisor, normalize, taps[i:i + chunk], save) for i in range(0, n, chunk)]
         if n:
             tap_sum(taps, out=dist)
-        return dist, taps
+        return (dist, taps, saved) if save else (dist, taps)
 
     def forward(self, pred, target, normalize: bool = False):
-        """pred, target float32 CUDA [1|3,H,W] or [B,1|3,H,W] -> float32 [B,1,1,1], as PerceptualLoss.forward(pred, target, normalize)."""
+        """pred, target float32 CUDA [1|3,H,W] or [B,1|3,H,W] -> float32 [B,1,1,1], as PerceptualLoss.forward(pred, target, normalize).
+        With gradient recording on and a pred that requires grad the result carries the gradient to pred (the same kernels and the same
+        bits forward); target must not require grad."""
         _lib.require_gpu()
         pred, target = (t.unsqueeze(0) if isinstance(t, torch.Tensor) and t.dim() == 3 else t for t in (pred, target))
+        if isinstance(pred, torch.Tensor) and pred.requires_grad and torch.is_grad_enabled():
+            if isinstance(target, torch.Tensor) and target.requires_grad:
+                raise ValueError("LPIPSAlex has no gradient to target: detach it")
+            _images("pred", pred)
+            _images("target", target)
+            (oh, ow) = tap_sizes(pred.shape[2], pred.shape[3])[0]
+            chunk = max(1, min(self.grad_chunk, GRAD_CHUNK_ELEMS // (2 * 64 * oh * ow)))
+            return _LPIPSAlexFn.apply(pred, target, self, bool(normalize), chunk).reshape(-1, 1, 1, 1)
         pred, ps = _images("pred", pred)
         target, ts = _images("target", target)
         dist, _ = self._run(pred, ps, target, ts, 1.0, bool(normalize), self.chunk)
@@ -271,3 +390,25 @@ class LPIPSAlex(nn.Module):
         frame, fs = _images("frame", frame)
         dist, tp = self._run(pred, ps, frame, fs, float(divisor), bool(normalize), self.chunk if chunk is None else int(chunk))
         return (dist, tp) if taps else dist
+
+
+class _LPIPSAlexFn(torch.autograd.Function):
+    """forward: LPIPSAlex._run as it is, keeping every chunk's taps; backward: LPIPSAlex._chunk_backward chunk by chunk, no host
+    synchronisation."""
+
+    @staticmethod
+    def forward(ctx, pred, target, model, normalize, chunk):
+        p, ps = _images("pred", pred)
+        t, ts = _images("target", target)
+        dist, _, ctx.saved = model._run(p, ps, t, ts, 1.0, normalize, chunk, save=True)
+        ctx.cfg = (model, normalize, chunk, tuple(p.shape))
+        return dist
+
+    @staticmethod
+    def backward(ctx, ddist):
+        model, normalize, chunk, (n, cin, h, w) = ctx.cfg
+        ddist = ddist.detach().to(torch.float32).reshape(-1).contiguous()
+        dpred = torch.empty((n, cin, h, w), dtype=torch.float32, device=ddist.device)
+        for k, i in enumerate(range(0, n, chunk)):
+            model._chunk_backward(ctx.saved[k], ddist[i:i + chunk], cin, h, w, 1.0, normalize, dpred[i:i + chunk])
+        return dpred, None, None, None, None

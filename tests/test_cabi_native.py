@@ -31,6 +31,10 @@ def test_c_client_compiles_and_links(tmp_path):
     import __graft_entry__ as ge
     ge.build()
     _build(tmp_path)                                           # header is valid C11 and every symbol used resolves
+    cmd = ["gcc", "-std=c11", "-Wall", "-Wextra", "-pedantic", "-c", os.path.join(ROOT, "tests", "cabi", "all_headers.c"),
+           "-I", os.path.join(ROOT, "include"), "-o", str(tmp_path / "all_headers.o")]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0 and not res.stderr, res.stderr[-3000:]                  # all five public headers, as C
 
 
 @pytest.mark.gpu

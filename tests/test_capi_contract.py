@@ -1,16 +1,19 @@
-"""CPU-side checks of the C ABI's contract (include/v2v_hip.h): what every entry point answers to a call it must refuse, through the
-library's ONE thread-local error slot, and the ctypes binding against the header's prototypes.  No GPU: every call here fails argument
-validation before any HIP call.
+"""CPU-side checks of the C ABI's contract, for every public header under include/: what every entry point answers to a call it must
+refuse, through the library's ONE thread-local error slot, and the ctypes binding (the one table v2v_amd/_lib.py:HEADERS) against the
+headers' prototypes.  No GPU: every call here fails argument validation before any HIP call.
 
 The expected statuses and messages were recorded from the build of the commit before the entry points moved next to their launchers
 (the dynamic decoder's training entry points then kept their text behind v2v_hyper_train_last_error(); read through v2v_last_error(),
-those nine `_hip` calls returned the stale text of the failing call before them)."""
+those nine `_hip` calls returned the stale text of the failing call before them); those of the four newer headers from the build of the
+commit before this module covered them."""
 import ctypes as C
 import os
 import re
 import threading
 
 import pytest
+
+from capi_calls import _D, _d, _zero
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -23,8 +26,9 @@ def L():
     return _lib
 
 
-# every export whose name ends in _hip, called with every pointer NULL and every number 0: V2V_ERR_NULL and this message
-NULL_CALLS = {
+# every export whose name ends in _hip, called with every pointer NULL and every number 0: (status, message).  v2v_hip.h's 80 answer
+# V2V_ERR_NULL; an entry point of the newer headers that checks its shape first answers V2V_ERR_SHAPE
+NULL_CALLS = {name: (-1, message) for name, message in {
     "v2v_esim_voxel_hip": "v2v_esim_voxel_hip: frames/params/out_voxel is NULL",
     "v2v_esim_voxel_keyed_hip": "v2v_esim_voxel_hip: frames/params/out_voxel is NULL",
     "v2v_esim_voxel_padded_hip": "v2v_esim_voxel_hip: frames/params/out_voxel is NULL",
@@ -106,31 +110,41 @@ NULL_CALLS = {
     "v2v_lpips_pool_bwd_hip": "v2v_lpips_pool_bwd_hip: dy/x/dx is NULL",
     "v2v_lpips_compare_fwd_hip": "v2v_lpips_compare_fwd_hip: f0/f1/w/dist/workspace is NULL",
     "v2v_lpips_compare_bwd_hip": "v2v_lpips_compare_bwd_hip: f0/f1/w/ddist/df0 is NULL",
-}
-
-
-def _zero(t):
-    if t in (C.c_float, C.c_double):
-        return t(0.0)
-    if t in (C.c_int, C.c_int64, C.c_uint32, C.c_uint64):
-        return t(0)
-    return None                                    # every pointer class
+}.items()}
+NULL_CALLS.update({
+    "v2v_learned_voxel_stats_hip": (-1, "v2v_learned_voxel_stats_hip: events/workspace is NULL"),
+    "v2v_learned_voxel_hip": (-1, "v2v_learned_voxel_hip: events/workspace is NULL"),
+    "v2v_image_metrics_hip": (-2, "v2v_image_metrics_hip: the 7x7 window needs H >= 7 and W >= 7 (got 0 x 0)"),
+    "v2v_flow_metrics_hip": (-2, "v2v_flow_metrics_hip: need H, W >= 1 and H * W < 2^24, the reference's float32 counts (got 0 x 0)"),
+    "v2v_lpips_alex_stem_hip": (-2, "v2v_lpips_alex_stem_hip: a frame has 1 or 3 channels (got 0)"),
+    "v2v_lpips_alex_conv_hip": (-2, "v2v_lpips_alex_conv_hip: ks must be 3 or 5 (got 0)"),
+    "v2v_lpips_alex_pool_hip": (-2, "v2v_lpips_alex_pool_hip: C must be a multiple of 4 (got 0)"),
+    "v2v_lpips_alex_compare_hip": (-2, "v2v_lpips_alex_compare_hip: need HW >= 1 and [n,HW,384] below 2^31 elements (got n 0, HW 0)"),
+    "v2v_lpips_alex_sum_hip": (0, None),           # a count of 0 is V2V_OK without a launch, and n is all this entry point has
+    "v2v_alex_train_compare_bwd_hip": (-2, "v2v_alex_train_compare_bwd_hip: need HW >= 1 and [n,HW,384] below 2^31 elements (got n 0, HW 0)"),
+    "v2v_alex_train_conv_dgrad_hip": (-2, "v2v_alex_train_conv_dgrad_hip: ks must be 3 or 5 (got 0)"),
+    "v2v_alex_train_pool_bwd_hip": (-2, "v2v_alex_train_pool_bwd_hip: C must be a multiple of 4 (got 0)"),
+    "v2v_alex_train_stem_bwd_hip": (-2, "v2v_alex_train_stem_bwd_hip: a frame has 1 or 3 channels (got 0)"),
+})
 
 
 def _null_call(L, name):
-    return getattr(L.lib(), name)(*[_zero(t) for t in L.SIGNATURES[name][1]])
+    return getattr(L.lib(), name)(*_zero(L.SIGNATURES[name][1]))
 
 
 def test_null_table_covers_every_hip_export(L):
-    assert sorted(NULL_CALLS) == sorted(n for n in L.EXPORTS if n.endswith("_hip")) and len(NULL_CALLS) == 80
+    assert sorted(NULL_CALLS) == sorted(n for n in L.SIGNATURES if n.endswith("_hip")) and len(NULL_CALLS) == 93
+    assert (L.ERR_NULL, L.ERR_SHAPE, L.OK) == (-1, -2, 0) and all(NULL_CALLS[n][0] == L.ERR_NULL for n in L.HEADERS["v2v_hip.h"] if n in NULL_CALLS)
 
 
 @pytest.mark.parametrize("name", sorted(NULL_CALLS))
 def test_null_call_status_and_message(L, name):
     lib = L.lib()
-    assert _null_call(L, name) == L.ERR_NULL
-    assert lib.v2v_last_error().decode() == NULL_CALLS[name]
-    assert lib.v2v_hyper_train_last_error() == lib.v2v_last_error()            # the deprecated alias reads the same slot
+    status, message = NULL_CALLS[name]
+    assert _null_call(L, name) == status
+    if status != L.OK:
+        assert lib.v2v_last_error().decode() == message
+        assert lib.v2v_hyper_train_last_error() == lib.v2v_last_error()        # the deprecated alias reads the same slot
 
 
 def test_error_slot_is_per_thread(L):
@@ -147,19 +161,12 @@ def test_error_slot_is_per_thread(L):
     t = threading.Thread(target=other)
     t.start()
     t.join()
-    assert seen["rc"] == L.ERR_NULL and seen["before"] == b"" and seen["after"] == NULL_CALLS["v2v_hyper_dynconv_df_hip"].encode()
-    assert lib.v2v_last_error() == mine == NULL_CALLS["v2v_conv_nhwc_hip"].encode()
+    assert seen["rc"] == L.ERR_NULL and seen["before"] == b"" and seen["after"] == NULL_CALLS["v2v_hyper_dynconv_df_hip"][1].encode()
+    assert lib.v2v_last_error() == mine == NULL_CALLS["v2v_conv_nhwc_hip"][1].encode()
 
 
 # per family whose entry points moved next to their launchers (and the dynamic decoder's training family, whose error slot moved): one
 # shape and one alignment failure.  Dummy non-null pointers, never dereferenced: every case fails validation before any HIP call.
-_D = 4096
-
-
-def _d(k=0):
-    return C.c_void_p(_D * (k + 1))
-
-
 _ODD = C.c_void_p(_D + 8)                        # 8-byte aligned only
 
 VALIDATION_CASES = {
@@ -240,8 +247,8 @@ def _ctypes_class(t):
     return {C.c_int64: "i64", C.c_uint64: "i64", C.c_int: "i32", C.c_uint32: "i32", C.c_int32: "i32", C.c_float: "float", C.c_double: "double"}[t]
 
 
-def _header_prototypes():
-    hdr = open(os.path.join(ROOT, "include", "v2v_hip.h")).read()
+def _header_prototypes(header):
+    hdr = open(os.path.join(ROOT, "include", header)).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     hdr = re.sub(r"//[^\n]*", "", hdr)
     protos = {}
@@ -251,12 +258,48 @@ def _header_prototypes():
     return protos
 
 
-def test_binding_matches_header_prototypes(L):
-    protos = _header_prototypes()
-    assert list(protos) == list(L.EXPORTS), "the signature table lists the header's entry points, in the header's order"
-    for name, (res, args) in L.SIGNATURES.items():
+# entry points per header, and the names the newer headers were introduced with (v2v_nernet.h: its two launching ones)
+HEADER_ENTRIES = {"v2v_hip.h": 106, "v2v_nernet.h": 4, "v2v_metrics.h": 4, "v2v_lpips_alex.h": 6, "v2v_alex_train.h": 4}
+PINNED_NAMES = {
+    "v2v_nernet.h": ["v2v_learned_voxel_stats_hip", "v2v_learned_voxel_hip"],
+    "v2v_metrics.h": ["v2v_image_metrics_workspace_bytes", "v2v_image_metrics_hip", "v2v_flow_metrics_workspace_bytes", "v2v_flow_metrics_hip"],
+    "v2v_lpips_alex.h": ["v2v_lpips_alex_stem_hip", "v2v_lpips_alex_conv_hip", "v2v_lpips_alex_pool_hip", "v2v_lpips_alex_compare_workspace_bytes",
+                         "v2v_lpips_alex_compare_hip", "v2v_lpips_alex_sum_hip"],
+    "v2v_alex_train.h": ["v2v_alex_train_compare_bwd_hip", "v2v_alex_train_conv_dgrad_hip", "v2v_alex_train_pool_bwd_hip", "v2v_alex_train_stem_bwd_hip"],
+}
+
+
+@pytest.mark.parametrize("header", HEADER_ENTRIES)
+def test_binding_matches_header_prototypes(L, header):
+    protos, table = _header_prototypes(header), L.HEADERS[header]
+    assert list(protos) == list(table), "the header's table lists the header's entry points, in the header's order"
+    for name, (res, args) in table.items():
         want_res, want_args = protos[name]
         assert _ctypes_class(res) == want_res, name
         assert len(args) == len(want_args), (name, len(args), len(want_args))
         got = [_ctypes_class(t) for t in args]
         assert got == want_args, (name, [i for i, (g, w) in enumerate(zip(got, want_args)) if g != w])
+    if header != "v2v_hip.h":
+        assert '#include "v2v_hip.h"' in re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+
+
+def test_one_table_over_the_headers(L):
+    assert list(L.HEADERS) == list(HEADER_ENTRIES) and {h: len(t) for h, t in L.HEADERS.items()} == HEADER_ENTRIES
+    assert sum(len(t) for t in L.HEADERS.values()) == len(L.SIGNATURES) == 124, "no name in two headers"
+    assert L.EXPORTS == tuple(L.SIGNATURES) == tuple(n for t in L.HEADERS.values() for n in t)
+    assert sum(n.endswith("_hip") for n in L.SIGNATURES) == 93
+    for header, names in PINNED_NAMES.items():
+        assert [n for n in L.HEADERS[header] if header != "v2v_nernet.h" or n.endswith("_hip")] == names
+    assert not any(n.startswith("v2v_lpips_alex_") for n in L.HEADERS["v2v_alex_train.h"])
+    lib = L.lib()
+    for name in L.SIGNATURES:
+        assert hasattr(lib, name), name
+    assert lib.v2v_version() == L.ABI_VERSION == 6
+
+
+def test_library_holds_no_other_name_of_the_alex_families(L):
+    """the names in the library's bytes (its dynamic symbol table, the entry points' own names in their messages) are the declared ones --
+    but for one translation unit's own name, which the Makefile hands to the compiler as the compilation-unit id"""
+    blob = open(L.LIB_PATH, "rb").read()
+    assert set(n.decode() for n in re.findall(rb"v2v_lpips_alex_[a-z0-9_]+", blob)) == set(L.HEADERS["v2v_lpips_alex.h"])
+    assert set(n.decode() for n in re.findall(rb"v2v_alex_train_[a-z0-9_]+", blob)) - {"v2v_alex_train_tu"} == set(L.HEADERS["v2v_alex_train.h"])

@@ -1,5 +1,5 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads and exports every symbol that
-include/v2v_hip.h declares; argument validation works without a GPU; host logic of the wrappers."""
+the public headers under include/ declare; argument validation works without a GPU; host logic of the wrappers."""
 import ctypes as C
 import os
 import re
@@ -18,15 +18,16 @@ def L():
     return _lib
 
 
-def test_header_symbols_all_exported(L):
-    hdr = open(os.path.join(ROOT, "include", "v2v_hip.h")).read()
+@pytest.mark.parametrize("header", ["v2v_hip.h", "v2v_nernet.h", "v2v_metrics.h", "v2v_lpips_alex.h", "v2v_alex_train.h"])
+def test_header_symbols_all_exported(L, header):
+    hdr = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)     # comments name entry points too
     declared = set(re.findall(r"\b(v2v_[a-z0-9_]+)\s*\(", hdr))
     declared -= {"v2v_status", "v2v_dtype"}
     assert declared, "no declarations parsed"
     lib = L.lib()
     for name in sorted(declared):
-        assert hasattr(lib, name), f"{name} declared in include/v2v_hip.h but not exported"
-    assert set(L.EXPORTS) == declared
+        assert hasattr(lib, name), f"{name} declared in include/{header} but not exported"
+    assert set(L.HEADERS[header]) == declared
 
 
 def test_version_and_no_gpu_behaviour(L):

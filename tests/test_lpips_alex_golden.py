@@ -1,11 +1,10 @@
 """CPU-side checks of the LPIPS-AlexNet metric (v2v_amd/lpips_alex.py, include/v2v_lpips_alex.h) against golden G34
 (tests/golden/g34_lpips_alex.npz, written by tests/golden/make_golden_lpips_alex.py from the reference's PNetLin): the stock restatement the
-timing tool and the GPU tests lean on (tests/lpips_alex_stock.py) reproduces it, the module carries the reference's 17 keys, the header
-declares what the binding binds and the library exports, the C entry points validate their arguments, the wrappers raise without a GPU.
-No GPU."""
+timing tool and the GPU tests lean on (tests/lpips_alex_stock.py) reproduces it, the module carries the reference's 17 keys, the C entry
+points validate their arguments (the header against the binding and the library: tests/test_capi_contract.py), the wrappers raise without
+a GPU.  No GPU."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import torch
 
 import lpips_alex_stock as STOCK
 import lpips_alex_weights as LW
+from capi_calls import _D, _d
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -117,51 +117,6 @@ def test_packing_layouts():
 
 
 # ---- the C entry points (include/v2v_lpips_alex.h) ---------------------------------------------------------------------------------------
-def test_entry_points_are_declared_bound_and_exported(L):
-    hdr = open(os.path.join(ROOT, "include", "v2v_lpips_alex.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = re.findall(r"\b(v2v_[a-z0-9_]+)\s*\(", hdr)
-    assert declared == list(L.LPIPS_ALEX_EXPORTS) == list(L.LPIPS_ALEX_SIGNATURES)
-    assert declared == ["v2v_lpips_alex_stem_hip", "v2v_lpips_alex_conv_hip", "v2v_lpips_alex_pool_hip", "v2v_lpips_alex_compare_workspace_bytes",
-                        "v2v_lpips_alex_compare_hip", "v2v_lpips_alex_sum_hip"]
-    lib = L.lib()
-    for name in declared:
-        assert hasattr(lib, name)
-    # every v2v_lpips_alex_* name the library's bytes hold (its dynamic symbol table, and the entry points' own names in their messages)
-    # is a declared one: nothing else of the family is exported
-    names = set(n.decode() for n in re.findall(rb"v2v_lpips_alex_[a-z0-9_]+", open(L.LIB_PATH, "rb").read()))
-    assert names == set(declared)
-    for other in (L.EXPORTS, L.NERNET_EXPORTS, L.METRICS_EXPORTS):
-        assert not set(L.LPIPS_ALEX_EXPORTS) & set(other)
-    assert '#include "v2v_hip.h"' in hdr
-
-
-def test_abi_version_stays_6(L):
-    assert L.lib().v2v_version() == 6 and L.ABI_VERSION == 6
-
-
-_D = 4096
-
-
-def _d(k=0):
-    return C.c_void_p(_D * (k + 1))
-
-
-def _zero(argtypes):
-    return [None if t is C.c_void_p else (0.0 if t in (C.c_float, C.c_double) else 0) for t in argtypes]
-
-
-def test_zeroed_arguments_are_refused_without_a_gpu(L):
-    lib = L.lib()
-    for name, (_, args) in L.LPIPS_ALEX_SIGNATURES.items():
-        rc = getattr(lib, name)(*_zero(args))
-        if name == "v2v_lpips_alex_sum_hip":
-            assert rc == L.OK, "a count of 0 is V2V_OK without a launch, and n is all this entry point has"
-        else:
-            assert rc in (L.ERR_NULL, L.ERR_SHAPE), name
-            assert name.encode() in lib.v2v_last_error()
-
-
 def _stem(**kw):
     return [kw.get("frames", _d()), kw.get("fs", 961), kw.get("n", 1), kw.get("cin", 1), kw.get("H", 31), kw.get("W", 31), kw.get("divisor", 255.0),
             1, kw.get("shift", _d(1)), _d(2), kw.get("weight", _d(3)), _d(4), kw.get("out", _d(5)), None]
@@ -202,6 +157,7 @@ def test_pool_compare_and_sum_argument_validation(L):
     w = lib.v2v_lpips_alex_compare_workspace_bytes
     assert w(1, 1) == 8 and w(3, 64) == 24 and w(3, 65) == 48 and w(80, 64 * 85) == 80 * 85 * 8 and w(0, 5) == 0
     assert w(1, 0) == L.ERR_SHAPE and w(-1, 4) == L.ERR_SHAPE and w(70000, 4) == L.ERR_SHAPE
+    assert w(0, 0) == L.ERR_SHAPE and b"v2v_lpips_alex_compare_workspace_bytes" in lib.v2v_last_error()
     f = lib.v2v_lpips_alex_compare_hip
     ok = lambda **kw: [kw.get("f0", _d()), kw.get("f1", _d(1)), kw.get("w", _d(2)), kw.get("n", 1), kw.get("HW", 6), kw.get("C", 192), kw.get("tap", 1),   # noqa: E731
                        kw.get("ws", _d(3)), kw.get("taps", _d(4)), None]

@@ -1,11 +1,10 @@
 """CPU-side checks of LPIPS-AlexNet as a training loss (v2v_amd/lpips_alex.py, include/v2v_alex_train.h) against golden G35
 (tests/golden/g35_lpips_alex_grad.npz, written by tests/golden/make_golden_lpips_alex_grad.py from the reference's PNetLin with autograd):
 the file's layout and the conditions its generator asserted, the stock restatement's float64 autograd (tests/lpips_alex_stock.py, the CPU
-cross-check the GPU tests lean on), the new header against the binding table and the library's symbols, every entry point's argument
-validation, the dgrad pack, the loss class's error without torchvision.  No GPU."""
+cross-check the GPU tests lean on), every entry point's argument validation (the header against the binding table and the library's
+symbols: tests/test_capi_contract.py), the dgrad pack, the loss class's error without torchvision.  No GPU."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import torch
 import lpips_alex_grad_cases as GC
 import lpips_alex_stock as STOCK
 import lpips_alex_weights as LW
+from capi_calls import _D, _d
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -143,48 +143,8 @@ def test_wrappers_raise_without_a_gpu(g34):
 
 
 # ---- the C entry points (include/v2v_alex_train.h) ------------------------------------------------------------------------------------------
-NAMES = ["v2v_alex_train_compare_bwd_hip", "v2v_alex_train_conv_dgrad_hip", "v2v_alex_train_pool_bwd_hip", "v2v_alex_train_stem_bwd_hip"]
-
-
-def test_entry_points_are_declared_bound_and_exported(L):
-    hdr = open(os.path.join(ROOT, "include", "v2v_alex_train.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = re.findall(r"\b(v2v_[a-z0-9_]+)\s*\(", hdr)
-    assert declared == list(L.ALEX_TRAIN_EXPORTS) == list(L.ALEX_TRAIN_SIGNATURES) == NAMES
-    assert not any(n.startswith("v2v_lpips_alex_") for n in declared)
-    lib = L.lib()
-    for name in declared:
-        assert hasattr(lib, name)
-    # every v2v_alex_train_* name in the library's bytes (symbol table, messages) is a declared one -- but for the translation unit's own
-    # name, which the Makefile hands to the compiler as the compilation-unit id
-    names = set(n.decode() for n in re.findall(rb"v2v_alex_train_[a-z0-9_]+", open(L.LIB_PATH, "rb").read()))
-    assert names - {"v2v_alex_train_tu"} == set(declared)
-    for other in (L.EXPORTS, L.NERNET_EXPORTS, L.METRICS_EXPORTS, L.LPIPS_ALEX_EXPORTS):
-        assert not set(L.ALEX_TRAIN_EXPORTS) & set(other)
-    assert '#include "v2v_hip.h"' in hdr
-    # the header's prototypes carry as many arguments as the binding table
-    for name, body in re.findall(r"\bint (v2v_[a-z0-9_]+)\s*\(([^)]*)\)", hdr):
-        assert len(body.split(",")) == len(L.ALEX_TRAIN_SIGNATURES[name][1]), name
-    assert L.lib().v2v_version() == 6 and L.ABI_VERSION == 6
-
-
-_D = 4096
-
-
-def _d(k=0):
-    return C.c_void_p(_D * (k + 1))
-
-
 _ODD = C.c_void_p(_D + 4)        # 4-byte but not 16-byte aligned
 _OFF = C.c_void_p(_D + 2)        # not even 4-byte aligned
-
-
-def test_zeroed_arguments_are_refused_without_a_gpu(L):
-    lib = L.lib()
-    for name, (_, args) in L.ALEX_TRAIN_SIGNATURES.items():
-        rc = getattr(lib, name)(*[None if t is C.c_void_p else (0.0 if t is C.c_float else 0) for t in args])
-        assert rc in (L.ERR_NULL, L.ERR_SHAPE), name
-        assert name.encode() in lib.v2v_last_error()
 
 
 def test_compare_bwd_argument_validation(L):

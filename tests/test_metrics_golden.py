@@ -1,16 +1,16 @@
 """CPU-side checks of the evaluation metrics (v2v_amd/metrics.py, include/v2v_metrics.h) against golden G33 (tests/golden/g33_metrics.npz,
 written by tests/golden/make_golden_metrics.py): the restatements the GPU tests lean on (tests/metrics_reference.py) reproduce it, the seeded
-inputs hash to what it records, the header declares what the binding binds, the C entry points validate their arguments, and the wrappers
-raise without a GPU.  No GPU."""
+inputs hash to what it records, the C entry points validate their arguments (the header against the binding: tests/test_capi_contract.py),
+and the wrappers raise without a GPU.  No GPU."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import metrics_reference as MR
+from capi_calls import _D, _d
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -124,29 +124,6 @@ def test_host_side_ratios_from_golden_counts(g33, name):
 
 
 # ---- the C entry points (include/v2v_metrics.h) ------------------------------------------------------------------------------------------
-def test_entry_points_are_declared_bound_and_exported(L):
-    hdr = open(os.path.join(ROOT, "include", "v2v_metrics.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = re.findall(r"\b(v2v_[a-z0-9_]+)\s*\(", hdr)
-    assert declared == list(L.METRICS_EXPORTS)
-    assert declared == ["v2v_image_metrics_workspace_bytes", "v2v_image_metrics_hip", "v2v_flow_metrics_workspace_bytes", "v2v_flow_metrics_hip"]
-    lib = L.lib()
-    for name in declared:
-        assert hasattr(lib, name)
-    assert not set(L.METRICS_EXPORTS) & set(L.EXPORTS) and not set(L.METRICS_EXPORTS) & set(L.NERNET_EXPORTS)
-
-
-def test_abi_version_stays_6(L):
-    assert L.lib().v2v_version() == 6 and L.ABI_VERSION == 6
-
-
-_D = 4096
-
-
-def _d(k=0):
-    return C.c_void_p(_D * (k + 1))
-
-
 def _img(**kw):
     return [kw.get("pred", _d()), kw.get("ps", 49), kw.get("image", _d(1)), kw.get("is_", 49), kw.get("T", 1), kw.get("H", 7), kw.get("W", 7),
             kw.get("divisor", 255.0), kw.get("data_range", 2.0), kw.get("ws", _d(2)), kw.get("out", _d(3)), kw.get("map", None), None]

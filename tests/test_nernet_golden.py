@@ -4,7 +4,6 @@ state dicts, the stock restatement the GPU tests lean on (tests/nernet_stock.py)
 entry points' argument validation.  No GPU."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ from torch import nn
 
 import nernet_stock as NS
 import seeded_weights as SW
+from capi_calls import _D, _d, _zero
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NET_KW = {"RepCNN_kernel_size": 3, "RepCNN_padding": 1, "RepCNN_channel": 16, "RepCNN_num_layers": 4}
@@ -168,24 +168,11 @@ def test_pack_mlp_layout():
 
 
 # ---- the C entry points (include/v2v_nernet.h) -------------------------------------------------------------------------------------------
-def test_entry_points_are_declared_bound_and_exported(L):
-    hdr = open(os.path.join(ROOT, "include", "v2v_nernet.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = re.findall(r"\b(v2v_[a-z0-9_]+)\s*\(", hdr)
-    assert declared == list(L.NERNET_EXPORTS) and "v2v_learned_voxel_stats_hip" in declared and "v2v_learned_voxel_hip" in declared
-    lib = L.lib()
-    for name in declared:
-        assert hasattr(lib, name)
+def test_every_entry_point_has_a_stub_in_the_integration_guide(L):
+    """the header against the binding table, the library and the refused zero call: tests/test_capi_contract.py"""
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    for name in declared:
+    for name in L.HEADERS["v2v_nernet.h"]:
         assert name in doc, f"{name} has no stub in INTEGRATION.md"
-
-
-_D = 4096
-
-
-def _d(k=0):
-    return C.c_void_p(_D * (k + 1))
 
 
 def _stats_args(**kw):
@@ -202,10 +189,9 @@ def _fused_args(layers=(1, 30, 30, 1), **kw):
 def test_argument_validation_answers_without_a_gpu(L):
     lib = L.lib()
     st, fu = lib.v2v_learned_voxel_stats_hip, lib.v2v_learned_voxel_hip
-    zero = lambda sig: [None if t is C.c_void_p else t(0) for t in sig]                                   # noqa: E731
-    assert st(*zero(L.NERNET_SIGNATURES["v2v_learned_voxel_stats_hip"][1])) == L.ERR_NULL
+    assert st(*_zero(L.SIGNATURES["v2v_learned_voxel_stats_hip"][1])) == L.ERR_NULL
     assert lib.v2v_last_error().decode() == "v2v_learned_voxel_stats_hip: events/workspace is NULL"
-    assert fu(*zero(L.NERNET_SIGNATURES["v2v_learned_voxel_hip"][1])) == L.ERR_NULL
+    assert fu(*_zero(L.SIGNATURES["v2v_learned_voxel_hip"][1])) == L.ERR_NULL
     assert lib.v2v_last_error().decode() == "v2v_learned_voxel_hip: events/workspace is NULL"
     assert st(*_stats_args(dt=0)) == L.ERR_DTYPE
     assert st(*_stats_args(n=-1)) == L.ERR_SHAPE

@@ -1,8 +1,8 @@
-"""ctypes binding of libv2v_hip.so (C ABI in include/v2v_hip.h, v2v_nernet.h, v2v_metrics.h, v2v_lpips_alex.h, v2v_alex_train.h) and the one calling convention every module
-of the package goes through.  Fails loudly when the library is missing.
+"""ctypes binding of libv2v_hip.so (C ABI in the public headers under include/) and the one calling convention every module of the package
+goes through.  Fails loudly when the library is missing.
 
-    lib()                          the loaded library, one binding table per header (SIGNATURES, NERNET_SIGNATURES, METRICS_SIGNATURES,
-                                   LPIPS_ALEX_SIGNATURES, ALEX_TRAIN_SIGNATURES)
+    HEADERS / SIGNATURES / EXPORTS the one binding table: per header, its flat union, the names
+    lib()                          the loaded library, every entry point of SIGNATURES bound
     ptr(t, offset_elems=0)         the address of a tensor as a C pointer argument, None -> NULL
     launch(name, device, *args)    the `_hip` entry point `name` on `device` and torch's current stream there, the stream last, status checked
     need(name, t, dtype, ...)      ValueError unless t is a contiguous CUDA tensor of that dtype and shape
@@ -72,8 +72,9 @@ P, I, I64, U32, U64, F = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64,
 _ESIM = [P, I] + [I64] * 6 + [P, I64, U32, I, U64, U64]                                  # frames..clip_id0
 _ESIM_PADDED = _ESIM + [P, C.POINTER(EsimReplay), I, I, I, P, I, I64, I64, P]              # clip_keys..out_counts (the stream follows)
 
-# {entry point: (restype, argtypes)}, in the order of include/v2v_hip.h (tests/test_capi_contract.py compares the two)
-SIGNATURES = {
+# The one binding table: public header under include/ -> {entry point: (restype, argtypes)}, each header's entries in the header's own order
+# (tests/test_capi_contract.py holds every row to its prototype).  A new family adds its header and its rows here, nowhere else.
+HEADERS = {"v2v_hip.h": {
     # library info / errors
     "v2v_version": (I, []),
     "v2v_last_error": (C.c_char_p, []),
@@ -199,48 +200,31 @@ SIGNATURES = {
     "v2v_lpips_compare_workspace_bytes": (I64, [I64, I64]),
     "v2v_lpips_compare_fwd_hip": (I, [P, P, P] + [I64] * 3 + [P, P, P]),
     "v2v_lpips_compare_bwd_hip": (I, [P, P, P, P] + [I64] * 3 + [P, P]),
-}
-EXPORTS = tuple(SIGNATURES)
-
-# include/v2v_nernet.h: NER-Net's learned voxelisation (v2v_amd/nernet.py).  A table of its own, as the header is: SIGNATURES / EXPORTS
-# mirror include/v2v_hip.h entry by entry.
-NERNET_SIGNATURES = {
+}, "v2v_nernet.h": {                                            # NER-Net's learned voxelisation (v2v_amd/nernet.py)
     "v2v_learned_voxel_packed_elems": (I64, [P, I]),
     "v2v_learned_voxel_workspace_bytes": (I64, [I64, I64]),
     "v2v_learned_voxel_stats_hip": (I, [P, I, I64, P, I64, I64, P, P]),
     "v2v_learned_voxel_hip": (I, [P, I, I64, P, I64, I64, I, I64, I64, P, P, I, F, I, I, P, P, P, P]),
-}
-NERNET_EXPORTS = tuple(NERNET_SIGNATURES)
-
-# include/v2v_metrics.h: the evaluation metrics (v2v_amd/metrics.py), a table of its own for the same reason.
-METRICS_SIGNATURES = {
+}, "v2v_metrics.h": {                                           # the evaluation metrics (v2v_amd/metrics.py)
     "v2v_image_metrics_workspace_bytes": (I64, [I64, I64, I64]),
     "v2v_image_metrics_hip": (I, [P, I64, P, I64, I64, I64, I64, F, C.c_double, P, P, P, P]),
     "v2v_flow_metrics_workspace_bytes": (I64, [I64, I64, I64]),
     "v2v_flow_metrics_hip": (I, [P, I64, P, I64, P, I64, I64, I64, I64, I64, P, P, P, P]),
-}
-METRICS_EXPORTS = tuple(METRICS_SIGNATURES)
-
-# include/v2v_lpips_alex.h: the LPIPS-AlexNet test metric (v2v_amd/lpips_alex.py), likewise a table of its own.
-LPIPS_ALEX_SIGNATURES = {
+}, "v2v_lpips_alex.h": {                                        # the LPIPS-AlexNet test metric (v2v_amd/lpips_alex.py)
     "v2v_lpips_alex_stem_hip": (I, [P, I64, I64, I64, I64, I64, F, I, P, P, P, P, P, P]),
     "v2v_lpips_alex_conv_hip": (I, [P, P, P, I64, I64, I64, I64, I64, I, I, P, P]),
     "v2v_lpips_alex_pool_hip": (I, [P, I64, I64, I64, I64, P, P]),
     "v2v_lpips_alex_compare_workspace_bytes": (I64, [I64, I64]),
     "v2v_lpips_alex_compare_hip": (I, [P, P, P, I64, I64, I64, I, P, P, P]),
     "v2v_lpips_alex_sum_hip": (I, [P, I64, P, P]),
-}
-LPIPS_ALEX_EXPORTS = tuple(LPIPS_ALEX_SIGNATURES)
-
-# include/v2v_alex_train.h: LPIPS-AlexNet's backward to the prediction (v2v_amd/lpips_alex.py).  A table of its own once more: the
-# v2v_lpips_alex_* family above is pinned name by name.
-ALEX_TRAIN_SIGNATURES = {
+}, "v2v_alex_train.h": {                                        # LPIPS-AlexNet's backward to the prediction (v2v_amd/lpips_alex.py)
     "v2v_alex_train_compare_bwd_hip": (I, [P, P, P, P, I64, I64, I64, I, P, P]),
     "v2v_alex_train_conv_dgrad_hip": (I, [P, P, P, P, I64, I64, I64, I64, I64, I, P, P]),
     "v2v_alex_train_pool_bwd_hip": (I, [P, P, P, I64, I64, I64, I64, I, P, P]),
     "v2v_alex_train_stem_bwd_hip": (I, [P, P, P, I64, I64, I64, I64, F, I, P, P]),
-}
-ALEX_TRAIN_EXPORTS = tuple(ALEX_TRAIN_SIGNATURES)
+}}
+SIGNATURES = {name: sig for table in HEADERS.values() for name, sig in table.items()}      # the flat union, in that order
+EXPORTS = tuple(SIGNATURES)
 
 _lib = None
 
@@ -254,8 +238,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C v2v_amd/csrc`).  v2v_amd has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(NERNET_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) \
-            + list(LPIPS_ALEX_SIGNATURES.items()) + list(ALEX_TRAIN_SIGNATURES.items()):
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     if L.v2v_version() != ABI_VERSION:

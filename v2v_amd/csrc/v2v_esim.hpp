@@ -17,8 +17,16 @@
 //   * the 256-entry log-intensity table (NumPy's bits, golden G1) lives in LDS; integer-valued input
 //     costs one ds_read per sample instead of a float64 pow+log.
 //   * np.floor_divide's exact result for a >= 0, b > 0 is the true floor of the real quotient; it is obtained
-//     without a division and without a per-pixel branch: q = floor(a * inv_low(b)), one sign-exact fma residual,
-//     and a rare (wave-level) +1 fix-up; q == 0 exactly when a < b, so the reference's where() masks fall out.
+//     without a division and without a per-pixel branch: q = floor(u), u = a * inv_low(b), and a rare (wave-level) +1
+//     fix-up found by one sign-exact fma residual; q == 0 exactly when a < b, so the reference's where() masks fall out.
+//     The residual and its compare run only behind a SCREEN on bits the step already has: with |u| < 2^20 the estimate
+//     can be short only if the top 24 bits of u's low word are all ones (lemma and proof: DESIGN.md section 4.2), so the
+//     hot path of a 4-pixel step is an unsigned max over four low words and one compare against a wave-uniform scalar
+//     (3 cheap vector instructions) where it ran 4 v_fma_f64 + 4 v_cmp_nlt_f64 + 3 s_or_b64.  A wave is PARANOID -- the
+//     scalar is 0, the full check runs in every step, same arithmetic -- when (1) the clip's parameters do not bound the
+//     quotient, (max(C+,C-) + 7.0 + 4.0625 (base_std + hot_std)) / min(C+,C-) >= 2^20 (bit 1 of the clip's flag word), or
+//     (2) a float32 frame value left the log table (sticky from that frame on, set by pix_logs' slow path).  Replayed
+//     noise fields (arbitrary host deviates) keep the full check at compile time.
 //   * symmetric thresholds (C+ == C-, wave-uniform per clip) take a loop specialised without the per-lane
 //     threshold selection; noise-free launches (V2V_FLAG_NO_NOISE) take kernels without the noise adds.
 //   * per-clip ON/OFF totals: lane-local counters -> wave reduction -> one 64-bit atomic per wave.
@@ -63,7 +71,7 @@ template <> struct LutEntry<kInF32> { using type = float2; };
 
 template <int IN, int VEC>
 __device__ __forceinline__ void pix_logs(const Raw<IN, VEC> &r, const typename LutEntry<IN>::type *lut,
-                                         typename LutT<IN>::type (&out)[VEC])
+                                         typename LutT<IN>::type (&out)[VEC], uint32_t &screen_min)
 {
     using ent_t = typename LutEntry<IN>::type;
     // table entry by BYTE offset: shift + mask (two full-rate VALU ops) instead of a bit-field extract and a
@@ -97,6 +105,7 @@ __device__ __forceinline__ void pix_logs(const Raw<IN, VEC> &r, const typename L
             bad |= __ballot(e.y != v);                         // e.y = (float)(b & 255): non-integer, negative, > 255, NaN
         }
         if (__builtin_expect(bad != 0, 0)) {                   // scalar test; lanes with clean pixels skip the bodies below
+            screen_min = 0u;                                   // sticky, wave-uniform: from here on a log difference is not bounded by the table's spread
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
                 const float v = raw_f32<VEC>(r, j);
@@ -120,6 +129,35 @@ __device__ __forceinline__ void pix_logs(const Raw<IN, VEC> &r, const typename L
 // C+ == C- too, and without the second (symmetric) loop the kernel fits 128 VGPRs = 4 waves per SIMD.
 template <int VEC, int RNG, bool NOISE, bool OUT64, bool EXT, bool SYMONLY>
 constexpr bool esim_asym4() { return V2V_ESIM_ASYM4 && NOISE && RNG == kRngPhilox && VEC == 4 && !OUT64 && !EXT && !SYMONLY; }
+
+// The quotient screen of the step: with u = p * inv_low(C) and |u| < 2^20, the reciprocal estimate trunc(u) is
+// short of floor(|p| / C) only if the top 24 bits of u's low word are all ones, so the step looks at that word and runs the residual
+// fma + compare of the fix-up only in the rare wave that passes (2^-24 per pixel and step for a random quotient).  The premise
+// |u| < 2^20 follows from the clip's parameters: |p| <= max(C+, C-) + kScreenLogSpread + kScreenGaussMax * (base_std + hot_std).
+// NOISE_FREE: the screen in the instances without the noise path too (their bound is evaluated per work-item).
+#ifndef V2V_ESIM_SCREEN
+#define V2V_ESIM_SCREEN 1
+#endif
+#ifndef V2V_ESIM_SCREEN_NOISE_FREE
+#define V2V_ESIM_SCREEN_NOISE_FREE 1
+#endif
+constexpr double kScreenLogSpread = 7.0;       // >= log(1.001) - log(0.001) = 6.909: the spread of both log tables
+constexpr double kScreenGaussMax = 4.0625;     // >= 4.009, the largest entry of the Gaussian table (v2v_rng.hpp)
+constexpr uint32_t kScreenLowWord = 0xFFFFFF00u;
+// copysign(1.0, x) for the rare fix-up, with the zero low word made on the spot: as a plain constant the compiler kept the pair in
+// registers across the whole time loop, which the float32 4-pixel instances at 128 VGPRs paid with scratch
+__device__ __forceinline__ double signed_one(double x)
+{
+    uint32_t lo;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(lo));
+    return __hiloint2double((int)(((uint32_t)__double2hiint(x) & 0x80000000u) | 0x3ff00000u), (int)lo);
+}
+__device__ __forceinline__ double quotient_bound_num(double c_pos, double c_neg, double base_std, double hot_std)
+{
+    const double noise = kScreenGaussMax * (base_std + hot_std);
+    const double reach = fmax(c_pos, c_neg) + kScreenLogSpread;
+    return reach + noise;
+}
 
 // FIDX   : the clip's frames are read through a per-clip index row (EsimArgs::frame_index, copied to LDS) and clips start at
 //          EsimArgs::clip_offsets -- the dataset's pause-index gather folded into the loads (instances: uint8 input, SUM bins, device noise).
@@ -207,7 +245,12 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
                 s_thr[2 * threadIdx.x] = c;
                 s_thr[2 * threadIdx.x + 1] = (1.0 / c) * 0x1.ffffffffffffcp-1;   // 1/C biased down by 2^-50 so that floor(|p| * inv) never exceeds the true quotient (one-sided correction)
             }
-            if (threadIdx.x == 0) s_bad = (int)any_bad;
+            // bit 1: the clip's parameters do not bound the floor-divide quotient below 2^20, the premise of the low-word screen in the
+            // step (kScreen*: after a reset |potential| < C, it starts in [-C-, C+), a table-valued log difference is at most kScreenLogSpread
+            // and a deviate of the Gaussian table at most kScreenGaussMax; the product by 2^20 is exact).  Such a clip runs the full check
+            // in every step: slower, the same arithmetic.  NaN parameters fail the compare too, and are poison by bit 0 anyway
+            const bool unbounded = !(quotient_bound_num(c_pos, c_neg, base_std, hot_std) < 0x1p20 * fmin(c_pos, c_neg));
+            if (threadIdx.x == 0) s_bad = (int)any_bad | (unbounded ? 2 : 0);
         }
     } else if (threadIdx.x < 2) {
         const double c = pp[threadIdx.x];
@@ -296,8 +339,17 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
     // symmetric clips keep the threshold and its (slightly low) reciprocal in VGPRs; asymmetric ones read s_thr by polarity.
     // 1/C biased down by 2^-50 so that floor(|p| * inv) never exceeds the true quotient (one-sided correction)
     double pos, inv_pos;
+    // SCREEN: the step finds the rare floor-divide fix-up on the low word of the quotient estimate (see kScreen* above).  Replayed noise
+    // fields are arbitrary host float64 deviates, which no table bounds: those instances keep the full check in every step.
+    // screen_min: the smallest low word that sends a wave into the fix-up's check -- one wave-uniform scalar register.  kScreenLowWord
+    // normally; 0 in a PARANOID wave, which then runs the full check in every step (slower, the same arithmetic): the clip's parameters
+    // do not bound the quotient, or (sticky, set by pix_logs' slow path) a frame value left the log table
+    constexpr bool SCREEN = V2V_ESIM_SCREEN && RNG != kRngReplay && (NOISE || V2V_ESIM_SCREEN_NOISE_FREE);
+    uint32_t screen_min = kScreenLowWord;
     if constexpr (ONCE) {
-        if (__builtin_amdgcn_readfirstlane(s_bad) != 0) { poison_clip(); return; }   // clip-uniform
+        const int flags = __builtin_amdgcn_readfirstlane(s_bad);       // clip-uniform: bit 0 poison, bit 1 quotient not bounded
+        if ((flags & 1) != 0) { poison_clip(); return; }
+        if constexpr (SCREEN) screen_min = (flags & 2) != 0 ? 0u : kScreenLowWord;
         pos = s_thr[0];                                                // the same bits by the same expression, computed once
         inv_pos = s_thr[1];
     } else {
@@ -306,6 +358,10 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
         inv_pos = (1.0 / pos) * 0x1.ffffffffffffcp-1;
         // (the per-lane form of the checks the ONCE instances make while they fill s_thr; clip-uniform branch)
         if (!(c_pos >= 1e-9 && c_pos <= 1e30 && c_neg >= 1e-9 && c_neg <= 1e30)) { poison_clip(); return; }
+        if constexpr (SCREEN) {
+            const bool unbounded = !(quotient_bound_num(c_pos, c_neg, 0.0, 0.0) < 0x1p20 * fmin(c_pos, c_neg));
+            screen_min = __builtin_amdgcn_readfirstlane((int)unbounded) != 0 ? 0u : kScreenLowWord;
+        }
     }
     asm volatile("" : "+v"(pos), "+v"(inv_pos));
     // F32W4: addresses = a wave-uniform part (clip, frame / plane: scalar registers) + the lane's own 32-bit byte offset (the C entry
@@ -373,7 +429,7 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
     lut_t lprev[VEC];
     {
         const Raw<IN, VEC> r0 = load_frame(0);
-        pix_logs<IN, VEC>(r0, s_lut, lprev);
+        pix_logs<IN, VEC>(r0, s_lut, lprev, screen_min);
     }
 
     // ---- binning state
@@ -431,7 +487,7 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
         lut_t ln[VEC];
         if constexpr (VEC == 1) {
             ln[0] = ln_pre[0];
-            pix_logs<IN, VEC>(raw_next, s_lut, ln_pre);
+            pix_logs<IN, VEC>(raw_next, s_lut, ln_pre, screen_min);
         }
         double base[NOISE ? VEC : 1];
         if constexpr (NOISE) {
@@ -491,7 +547,7 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
             wh = w2.y;
         }
 
-        if constexpr (VEC != 1) pix_logs<IN, VEC>(raw, s_lut, ln);
+        if constexpr (VEC != 1) pix_logs<IN, VEC>(raw, s_lut, ln, screen_min);
 
         // Branch-free per pixel: q = np.floor_divide(|p|, C) is 0 exactly when |p| < C, so the reference's
         // `where(p >= C+ ...)` / `where(p <= -C- ...)` masks (v2v_core_esim.py:51-55) need no separate test,
@@ -499,6 +555,7 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
         // Phase A: new potential, polarity, reciprocal quotient estimate and its sign-exact fma residual.
         double mag[VEC], thr[VEC], q[VEC], r[VEC];
         unsigned long long fix = 0;                                    // wave-level mask in an SGPR pair (no per-lane bool)
+        uint32_t ulo = 0;                                              // SCREEN: largest low word of the VEC quotient estimates
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
             const lut_t d = ln[j] - lprev[j];                          // difference in the input's precision (:42)
@@ -524,14 +581,24 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
             mag[j] = p;
             // inv is biased low, so the estimate never exceeds the true quotient in magnitude; it is short by one only when
             // |p|/C sits within ~1e-15 above an integer -- and then (or for a NaN potential) |r| < C fails
-            q[j] = trunc(p * inv);
-            r[j] = __builtin_fma(-q[j], thr[j], p);
-            fix |= __ballot(!(fabs(r[j]) < thr[j]));
+            const double u = p * inv;
+            q[j] = trunc(u);
+            if constexpr (SCREEN) {
+                // ... and then, with |u| < 2^20, the top 24 bits of u's low word are all ones: the residual and its compare wait for
+                // the rare branch, the hot path keeps an unsigned maximum over the work-item's pixels
+                const uint32_t lo = (uint32_t)__double2loint(u);
+                ulo = j == 0 ? lo : (lo > ulo ? lo : ulo);
+            } else {
+                r[j] = __builtin_fma(-q[j], thr[j], p);
+                fix |= __ballot(!(fabs(r[j]) < thr[j]));
+            }
         }
-        if (__builtin_expect(fix != 0, 0)) {                                // rare: exact multiples, NaN
+        if constexpr (SCREEN) fix = __ballot(ulo >= screen_min);
+        if (__builtin_expect(fix != 0, 0)) {                                // rare: exact multiples, NaN; a paranoid wave in every step
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
-                if (fabs(r[j]) >= thr[j]) q[j] += __builtin_copysign(1.0, r[j]);
+                if constexpr (SCREEN) r[j] = __builtin_fma(-q[j], thr[j], mag[j]);   // here, pixel by pixel: one residual live at a time
+                if (fabs(r[j]) >= thr[j]) q[j] += signed_one(r[j]);
                 // NaN potential: NumPy's compares are false -> no events.  INFINITE potential (a +-inf or overflowing frame value): the compare
                 // passes and np.floor_divide(inf, C) is NaN (fmod(inf, C)), so the reference counts NaN in this step and the potential is NaN
                 // from then on (v2v_core_esim.py:51-58) -- q = NaN reproduces both through q * C and the accumulate
@@ -546,6 +613,9 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
             const double qt = q[j] * thr[j];
             const double m2 = mag[j] - qt;                             // product rounded, then subtracted (no fma)
             pot[j] = m2;
+            // (F32W4, at their 128-VGPR budget: the reset stays in its own step.  Without the residual's compare in front of it the compiler
+            // sank it into the next step, which keeps q and the old potential of all four pixels live across the branch and spilled)
+            if constexpr (SCREEN && F32W4) asm volatile("" : "+v"(pot[j]));
             if constexpr (OUT64) {
                 double vox = q[j];
                 qabs[j] = __builtin_fabsf((float)q[j]);
@@ -635,7 +705,7 @@ __global__ void __launch_bounds__(kBlock, (SYMONLY || esim_asym4<VEC, RNG, NOISE
             const int f = (1 + u <= a.K) ? 1 + u : a.K;
             ring[u] = load_frame(f);
         }
-        if constexpr (VEC == 1) pix_logs<IN, VEC>(ring[0], s_lut, ln_pre);
+        if constexpr (VEC == 1) pix_logs<IN, VEC>(ring[0], s_lut, ln_pre, screen_min);
         int k0 = 0;
         for (; k0 + kRing <= a.K; k0 += kRing) {
             static_for(std::make_integer_sequence<int, kRing>{}, [&](auto u_tag) {

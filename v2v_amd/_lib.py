@@ -2,7 +2,8 @@
 goes through.  Fails loudly when the library is missing.
 
     HEADERS / SIGNATURES / EXPORTS the one binding table: per header, its flat union, the names
-    lib()                          the loaded library, every entry point of SIGNATURES bound
+    HEADERS_MORE / SIGNATURES_MORE the second table: headers added after ABI 6 was pinned (additive, same version)
+    lib()                          the loaded library, every entry point of both tables bound
     ptr(t, offset_elems=0)         the address of a tensor as a C pointer argument, None -> NULL
     launch(name, device, *args)    the `_hip` entry point `name` on `device` and torch's current stream there, the stream last, status checked
     need(name, t, dtype, ...)      ValueError unless t is a contiguous CUDA tensor of that dtype and shape
@@ -73,7 +74,9 @@ _ESIM = [P, I] + [I64] * 6 + [P, I64, U32, I, U64, U64]                         
 _ESIM_PADDED = _ESIM + [P, C.POINTER(EsimReplay), I, I, I, P, I, I64, I64, P]              # clip_keys..out_counts (the stream follows)
 
 # The one binding table: public header under include/ -> {entry point: (restype, argtypes)}, each header's entries in the header's own order
-# (tests/test_capi_contract.py holds every row to its prototype).  A new family adds its header and its rows here, nowhere else.
+# (tests/test_capi_contract.py holds every row to its prototype).  This table is ABI 6 as that test pins it -- five headers, 124 rows -- and
+# stays as it is: a family added after it puts its header and its rows into HEADERS_MORE below, which lib() binds the same way and the
+# same kind of contract test (tests/test_nam_capi_contract.py) holds to its header.  Additive, so v2v_version() stays 6.
 HEADERS = {"v2v_hip.h": {
     # library info / errors
     "v2v_version": (I, []),
@@ -226,6 +229,21 @@ HEADERS = {"v2v_hip.h": {
 SIGNATURES = {name: sig for table in HEADERS.values() for name, sig in table.items()}      # the flat union, in that order
 EXPORTS = tuple(SIGNATURES)
 
+# The second table, same shape: the headers added after ABI 6 was pinned.  Not part of HEADERS / SIGNATURES / EXPORTS; no name in both.
+HEADERS_MORE = {"v2v_nam.h": {                                  # NER-Net's recurrent network: NAM cell, context block, 16-channel head, valid extent (v2v_amd/nhwc_ops.py)
+    "v2v_nam_packed_elems": (I64, [I64]),
+    "v2v_nam_pack_weights_hip": (I, [P] * 6 + [I64, P, P]),
+    "v2v_nam_step_hip": (I, [P] * 5 + [I64] * 4 + [P] * 9 + [I, I, I64, I64, P]),
+    "v2v_gcb_workspace_bytes": (I64, [I64] * 4),
+    "v2v_gcb_nhwc_hip": (I, [P] * 12 + [F] + [I64] * 6 + [P, I64, P, P, P]),
+    "v2v_conv_head16in_packed_elems": (I64, []),
+    "v2v_conv_head16in_pack_weights_hip": (I, [P, I64, P, P]),
+    "v2v_to_nhwc16_bf16_hip": (I, [P] + [I64] * 8 + [P, P]),
+    "v2v_conv_head16in_nhwc_hip": (I, [P] * 3 + [I] + [I64] * 3 + [P, P]),
+    "v2v_valid_extent_nhwc_hip": (I, [P, I] + [I64] * 6 + [I, P]),
+}}
+SIGNATURES_MORE = {name: sig for table in HEADERS_MORE.values() for name, sig in table.items()}
+
 _lib = None
 
 
@@ -238,7 +256,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C v2v_amd/csrc`).  v2v_amd has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_MORE.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     if L.v2v_version() != ABI_VERSION:

@@ -112,6 +112,13 @@ template <int MF, int NF>
 __device__ __forceinline__ void gru_epilogue_gates(const ConvLstmArgs &a, cl_f32x16 (&acc)[MF][NF], int64_t mw0, int ch0, int fh, int64_t M);
 template <int MF, int NF>
 __device__ __forceinline__ void gru_epilogue_candidate(const ConvLstmArgs &a, cl_f32x16 (&acc)[MF][NF], int64_t mw0, int col0, int fh, int64_t M);
+// the NAM cell's epilogues (EPI = 5 / 6 / 7): defined in v2v_nam.hpp, which only the NAM translation unit includes
+template <int MF, int NF>
+__device__ __forceinline__ void nam_epilogue_m(const ConvLstmArgs &a, cl_f32x16 (&acc)[MF][NF], int64_t mw0, int ch, int fh, int64_t M);
+template <int MF, int NF>
+__device__ __forceinline__ void nam_epilogue_c(const ConvLstmArgs &a, cl_f32x16 (&acc)[MF][NF], int64_t mw0, int ch, int fh, int64_t M);
+template <int MF, int NF>
+__device__ __forceinline__ void nam_epilogue_h(const ConvLstmArgs &a, cl_f32x16 (&acc)[MF][NF], int64_t mw0, int ch0, int fh, int64_t M);
 
 // EPI = 0: ConvLSTM step (two inputs x|h, 4C gate columns, gate/cell epilogue).  EPI = 2: the step's BACKWARD on the same main loop
 // (the gate GEMM recomputed from the saved x, h_prev; the cell backward on the accumulators, epilogue below).  EPI = 1: plain 3x3 convolution of x with
@@ -130,11 +137,13 @@ __device__ __forceinline__ void gru_epilogue_candidate(const ConvLstmArgs &a, cl
 // K over two inputs like the step (x | h_prev, h_prev null = zero state) on weights packed in tiles of a.pack_cols columns.
 // EPI = 3, gates: 2C columns, fragment pairs (update, reset) of 32 hidden channels (NF = 2 or 4 -> 32 or 64 channels per wave).
 // EPI = 4, candidate: C columns laid out like EPI = 1's (fragment g of a wave = channels col0 + 32 g ..).
+// EPI = 5 / 6 / 7: the three launches of NER-Net's NAM cell (v2v_nam_tu.hip; epilogues and argument aliases in v2v_nam.hpp): 5 and 6 on the
+// step's geometry (4C columns, the four columns of a hidden channel in one wave), 7 on EPI = 3's (2C columns, fragment pairs).
 template <int MF, int WM, int STAGES = 2, int EPI = 0, int WN = 2, int NF = 4, int TPC = 1, int KS = 1>
 __global__ void __launch_bounds__(64 * WM * WN * KS, KS == 2 || WM * WN == 16 ? 1 : (STAGES == 2 && MF == 1) || WM * WN == 8 || NF < 4 ? 2 : 1) convlstm_step_kernel(const ConvLstmArgs a)
 {
     static_assert(KS == 1 || KS == 2, "one or two K groups");
-    static_assert(EPI == 1 || EPI == 4 || NF == 4 || (EPI == 3 && NF == 2), "the gate epilogue needs the four (GRU: two) gates of a channel in one wave");
+    static_assert(EPI == 1 || EPI == 4 || NF == 4 || ((EPI == 3 || EPI == 7) && NF == 2), "the gate epilogue needs the four (GRU: two) gates of a channel in one wave");
     static_assert(TPC == 1 || (TPC == 2 && EPI == 1), "two taps per chunk: plain convolution of 32 input channels");
     constexpr int kBN = WN * NF * 32, kBBytes = kBN * kClBK * 2;
     constexpr int kClBM = 32 * MF * WM, kClABytes = kClBM * kClBK * 2, kClStage = kClABytes + kBBytes;
@@ -148,7 +157,7 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, KS == 2 || WM * WN == 16 ? 
     const int C = a.C, HW = a.H * a.W;
     const int ks = EPI != 1 ? 3 : a.ks, pad = ks >> 1, n_taps = ks * ks, stride = EPI != 1 ? 1 : a.stride;
     const int Hin = EPI != 1 ? a.H : a.Hin, Win = EPI != 1 ? a.W : a.Win;
-    constexpr int kStepCh = EPI == 3 ? kBN / 2 : EPI == 4 ? kBN : WN * 32;   // hidden channels per column tile of the step (64, or 32 with one wave column)
+    constexpr int kStepCh = (EPI == 3 || EPI == 7) ? kBN / 2 : EPI == 4 ? kBN : WN * 32;   // hidden channels per column tile of the step (64, or 32 with one wave column)
     const int n_ct = EPI != 1 ? C / kStepCh : a.n_cols / kBN;     // column tiles
     const int ct = blockIdx.x % n_ct;
     const int64_t m0 = (int64_t)(blockIdx.x / n_ct) * kClBM;      // first pixel of the tile (flattened b,y,x)
@@ -396,6 +405,9 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, KS == 2 || WM * WN == 16 ? 
     }
     if constexpr (EPI == 3) { gru_epilogue_gates<MF, NF>(a, acc, m0 + wm * 32 * MF, ct * kStepCh + wn * 16 * NF + fr, fh, M); return; }
     if constexpr (EPI == 4) { gru_epilogue_candidate<MF, NF>(a, acc, m0 + wm * 32 * MF, ct * kBN + wn * 32 * NF + fr, fh, M); return; }
+    if constexpr (EPI == 5) { nam_epilogue_m<MF, NF>(a, acc, m0 + wm * 32 * MF, ct * kStepCh + wn * 32 + fr, fh, M); return; }
+    if constexpr (EPI == 6) { nam_epilogue_c<MF, NF>(a, acc, m0 + wm * 32 * MF, ct * kStepCh + wn * 32 + fr, fh, M); return; }
+    if constexpr (EPI == 7) { nam_epilogue_h<MF, NF>(a, acc, m0 + wm * 32 * MF, ct * kStepCh + wn * 16 * NF + fr, fh, M); return; }
     if constexpr (EPI == 2) {
     // ---- backward epilogue: the forward's gate / cell values recomputed on the accumulators (same expressions), then
     //   tc = tanh(c);  dc_tot = dc + dh * o * (1 - tc^2);  d_o = dh * tc;  d_i = dc_tot * g;  d_g = dc_tot * i;  d_r = dc_tot * c_prev
@@ -435,7 +447,7 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, KS == 2 || WM * WN == 16 ? 
 }
 
 // Host side: one instance of the kernel above on its grid.  Columns of the job: 4 C gate columns for the step and its backward (EPI 0 / 2),
-// n_cols for the plain convolution (EPI 1), 2 C for the ConvGRU's gates (EPI 3), C for its candidate (EPI 4); one workgroup per tile of
+// n_cols for the plain convolution (EPI 1), 2 C for the ConvGRU's gates (EPI 3) and the NAM cell's last launch (EPI 7), C for the candidate (EPI 4); one workgroup per tile of
 // 32 MF WM pixels x 32 WN NF columns.
 template <int MF, int WM, int STAGES = 2, int EPI = 0, int WN = 2, int NF = 4, int TPC = 1, int KS = 1>
 hipError_t launch_step_t(const ConvLstmArgs &a, hipStream_t s)
@@ -445,7 +457,7 @@ hipError_t launch_step_t(const ConvLstmArgs &a, hipStream_t s)
     static std::atomic<bool> raised[64];
     const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(&convlstm_step_kernel<MF, WM, STAGES, EPI, WN, NF, TPC, KS>), lds, raised);
     if (e != hipSuccess) return e;
-    const int64_t cols = EPI == 1 ? a.n_cols : EPI == 3 ? 2 * a.C : EPI == 4 ? a.C : 4 * a.C;
+    const int64_t cols = EPI == 1 ? a.n_cols : (EPI == 3 || EPI == 7) ? 2 * a.C : EPI == 4 ? a.C : 4 * a.C;
     // ceil: the last pixel tile may be partial (rows past B*H*W read the zero line and are not stored)
     const int64_t tiles = (((int64_t)a.B * a.H * a.W + 32 * MF * WM - 1) / (32 * MF * WM)) * (cols / (WN * NF * 32));
     hipLaunchKernelGGL((convlstm_step_kernel<MF, WM, STAGES, EPI, WN, NF, TPC, KS>), dim3((unsigned)tiles), dim3(64 * WM * WN * KS), lds, s, a);

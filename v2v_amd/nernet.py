@@ -8,7 +8,8 @@ statistics pre-pass and one fused kernel: normalisation, MLP in registers, float
 `v2v_amd.testh5.TestH5EventDataset` hands out exactly the rows this layer takes.
 
 Inference only: there is no backward kernel for the MLP, so a call under grad with parameters (or rows) that require it raises.
-`RepresentationCNN` stays stock torch.nn (its 2C-channel input is not a shape the package's convolutions take).  No CPU fallback.
+`RepresentationCNN` stays stock torch.nn.  `RepresentationRecurrent` puts the recurrent network of v2v_amd/nernet_unet.py behind the
+voxelisation, the reference's whole model.  No CPU fallback.
 
 Deliberate differences from the reference:
   * the reference normalises t IN PLACE through views of its argument (:204, :213), so it changes the caller's tensor and a second call on
@@ -249,3 +250,80 @@ class Voxelization(nn.Module):
             return vox
         T, B = vox.shape[:2]
         return self.ConvLayer(vox.flatten(0, 1)).unflatten(0, (T, B))
+
+
+def crop_sizes(height, width, num_encoders=3):
+    """CropParameters(width, height, num_encoders) of the reference (model/model_util.py:195-225) in four integers: the frame padded to
+    multiples of 2^num_encoders, the ceil half of the padding on top / left -> (padded height, padded width, top, left)."""
+    f = 1 << int(num_encoders)
+    ph, pw = -(-int(height) // f) * f, -(-int(width) // f) * f
+    return ph, pw, (ph - height + 1) // 2, (pw - width + 1) // 2
+
+
+class RepresentationRecurrent(nn.Module):
+    """Drop-in for model/nernet_model.py:RepresentationRecurrent (:23-99) with `recurrent_network: NIAM_STcell_GCB`: the learned voxelisation
+    (`representation`, rebuilt by set_resolution, its learned weights kept), the zero padding to multiples of 8 and the recurrent network
+    (`unetrecurrent`, v2v_amd.nernet_unet) -- the reference's module tree and state_dict keys.  YAML: target: v2v_amd.nernet.RepresentationRecurrent.
+    Inference only.  forward(events) -> (output_dict, event_tensor) as the reference; forward_sequence is what its test loop does with it."""
+
+    def __init__(self, unet_kwargs):
+        super().__init__()
+        from .nernet_unet import UNetNIAM_STcell_GCB
+        self.unet_kwargs = dict(unet_kwargs)
+        self.num_bins, self.num_encoders = unet_kwargs["num_bins"], unet_kwargs["num_encoders"]
+        self.mlp_layers, self.normalize = unet_kwargs["mlp_layers"], unet_kwargs["normalize"]
+        self.network = unet_kwargs["recurrent_network"]
+        self.unetrecurrent = UNetNIAM_STcell_GCB(unet_kwargs)
+        self.height = self.width = self.representation = None
+        self.set_resolution(256, 256)             # a placeholder, as in the reference, so that weights can be loaded
+
+    def set_resolution(self, H, W):
+        if (H, W) == (self.height, self.width):
+            return
+        old = None if self.representation is None else self.representation.state_dict()
+        k = self.unet_kwargs
+        self.height, self.width = int(H), int(W)
+        rep = Voxelization(k, k["use_cnn_representation"], voxel_dimension=(self.num_bins, self.height, self.width), mlp_layers=self.mlp_layers,
+                           activation=nn.LeakyReLU(negative_slope=0.1), pretrained=True, normalize=self.normalize, combine_voxel=k["combine_voxel"])
+        self.representation = rep.to(next(self.unetrecurrent.parameters()).device)
+        if old is not None:
+            self.representation.load_state_dict(old, strict=True)
+        self.crop = crop_sizes(self.height, self.width, self.num_encoders)
+
+    @property
+    def states(self):
+        return self.unetrecurrent.states
+
+    @states.setter
+    def states(self, states):
+        self.unetrecurrent.states = states
+
+    def reset_states(self):
+        self.unetrecurrent.reset_states()
+
+    def _pad(self, vox):
+        ph, pw, top, left = self.crop
+        return torch.nn.functional.pad(vox, (left, pw - self.width - left, top, ph - self.height - top))
+
+    def forward(self, x):
+        """x: [n, 5] event rows -> ({'image': [B,1,H8,W8]} on the frame padded to multiples of 8, the padded event tensor)"""
+        event_tensor = self._pad(self.representation(x))
+        return self.unetrecurrent(event_tensor), event_tensor
+
+    def forward_sequence(self, events, H, W):
+        """What ModelInterface.forward_sequence_nernet (model/train_utils.py:350-378) does: T event tensors of one sequence (batch 1) ->
+        [1, T, 1, H, W]; every output is cut at the top left, [:H, :W], as that caller cuts it.  The states are the caller's to reset.
+        The whole sequence is voxelised with one upload and one launch pair, as Voxelization.forward_sequence does it; RepresentationCNN
+        (stock torch.nn) then runs per step on a batch of one, the call forward() makes, so that a library's choice of another algorithm
+        for another batch size cannot tell the two paths apart."""
+        self.set_resolution(H, W)
+        events, rep = list(events), self.representation
+        if len(events) == 0:
+            raise ValueError("forward_sequence needs at least one interval")
+        offsets = torch.tensor([0] + [int(e.shape[0]) for e in events], dtype=torch.int64).cumsum(0)
+        vox = rep.quantization_layer(torch.cat(events, 0), batch_size=1, offsets=offsets)         # [T, 1, 2C, H, W]
+        imgs = []
+        for t in range(vox.shape[0]):
+            v = rep.ConvLayer(vox[t]) if rep.use_cnn_representation else vox[t]
+            imgs.append(self.unetrecurrent(self._pad(v))["image"][0, :, :H, :W])
+        return torch.stack(imgs)[None]

@@ -12,6 +12,10 @@ calling convention, nothing of it is defined here.
     conv1x1_nhwc                                           the 1x1 prediction layer on skip_sum(x, head)
     conv_head_nhwc / to_nhwc8_bf16 / pack_head_weights     the head (voxel bins -> 32 channels)
     conv_stem_nhwc / pack_stem_weights / upsample2x_cat_nhwc       the plain UNet (EVFlowNet): stride-2 stem (voxel bins -> 64), concat-skip upsampling
+    nam_step / pack_nam_weights                            NER-Net's NAM cell (three launches on the ConvLSTM / ConvGRU tile geometries) and its packing
+    conv_head16in_nhwc / to_nhwc16_bf16 / pack_head16in_weights    the head for 9 to 16 input channels (NER-Net: 2 * num_bins = 10 -> 32, 5x5)
+    gcb_nhwc / pack_gcb_weights / valid_extent_nhwc        NER-Net's global context block (1x1 convolution + attention pooling + residual, float32
+                                                           arithmetic) and the clear / edge-replicate helper of a canvas larger than its valid extent
     pack_gate_weights / pack_conv_weights / pack_dgrad_weights     one-off weight packing; packed_weights = the cache in front of them
     nchw_to_nhwc_bf16(x, relu=False)                      layout change in front of them (not needed for channels-last bf16 input)
     relu_bwd_nhwc / conv_dgrad_nhwc / conv_wgrad_nhwc / upsample2x_bwd_nhwc / upsample2x_cat_bwd_nhwc / conv1x1_bwd_nhwc / convlstm_step_bwd     the backward operators
@@ -422,6 +426,154 @@ def upsample2x_cat_nhwc(x, skip=None):
     out = torch.empty((b, 2 * h, 2 * w, c1 + c2), dtype=torch.bfloat16, device=x.device)
     launch("v2v_upsample2x_cat_nhwc_hip", x.device, ptr(x), c1, ptr(skip), c2, b, h, w, ptr(out))
     return out
+
+
+# ---- NER-Net's NAM cell (include/v2v_nam.h, v2v_amd/csrc/v2v_nam.hpp): three launches behind one call --------------------------------------
+NAM_KEYS = ("conv_x.0.weight", "conv_h.0.weight", "conv_m.0.weight", "conv_o.0.weight", "conv_last.weight", "LAG_conv.weight")   # under one NAM_withoutGCB
+
+
+def pack_nam_weights(conv_x, conv_h, conv_m, conv_o, conv_last, lag_conv):
+    """The six float32 tensors of NAM_KEYS ([7C,C,3,3], [4C,C,3,3], [3C,C,3,3], [C,2C,3,3], [C,2C,1,1], [C,C,1,1]) -> the packed bfloat16
+    streams of the three launches, one flat tensor (layout: v2v_amd/csrc/v2v_nam.hpp)."""
+    _lib.require_gpu()
+    ws = (conv_x, conv_h, conv_m, conv_o, conv_last, lag_conv)
+    c = lag_conv.shape[0] if lag_conv.dim() >= 2 else 0
+    shapes = ((7 * c, c, 3, 3), (4 * c, c, 3, 3), (3 * c, c, 3, 3), (c, 2 * c, 3, 3), (c, 2 * c), (c, c))
+    for key, w, shape in zip(NAM_KEYS, ws, shapes):
+        if not w.is_cuda or w.dtype != torch.float32 or w.device != conv_x.device or tuple(w.shape) not in (shape, shape + (1, 1)):
+            raise ValueError(f"{key} must be a float32 CUDA tensor {list(shape)} on one device, C = {c}")
+    n = _lib.lib().v2v_nam_packed_elems(c)
+    if n < 0:
+        _lib.check(int(n))
+    packed = torch.empty((n,), dtype=torch.bfloat16, device=conv_x.device)
+    launch("v2v_nam_pack_weights_hip", conv_x.device, *(ptr(w.detach().contiguous()) for w in ws), c, ptr(packed))
+    return packed
+
+
+def nam_step(x, m_t, h_prev, c_prev, packed, nchw_dtype=None, tile: int = 0, c_out=None, return_workspaces: bool = False, valid=None):
+    """One NAM_withoutGCB step on NHWC state.  x, m_t, h_prev: bfloat16 [B,H,W,C]; c_prev: float32; h_prev and c_prev both None = the zero
+    state.  packed = pack_nam_weights(...).  Returns a dict: h, c_bf16, m (bfloat16: what the next convolutions read), h_f32, c (float32;
+    c is the carried state, c_out may be c_prev: updated in place), m_f32 (float32), h_nchw ([B,C,H,W] in nchw_dtype, when that is not
+    None) and, with return_workspaces, alpha and o_pre (float32).  tile: 0 by shape, 1 / 2 = the 64- / 128-pixel instances.  valid = (Hv, Wv):
+    the operands are zero outside that extent of the canvas and the bfloat16 outputs come back zero there (None: the whole canvas)."""
+    _lib.require_gpu()
+    need("x", x)
+    b, h, w, c = x.shape
+    need("m_t", m_t, shape=x.shape, device=x.device)
+    if (h_prev is None) != (c_prev is None):
+        raise ValueError("h_prev and c_prev come together (both None: the zero state)")
+    for name, t, dt in (("h_prev", h_prev, torch.bfloat16), ("c_prev", c_prev, torch.float32)):
+        if t is not None:
+            need(name, t, dt, shape=x.shape, device=x.device)
+    if packed.dtype != torch.bfloat16 or packed.numel() != 180 * c * c or packed.device != x.device:
+        raise ValueError("packed must be the output of pack_nam_weights for the same C, on x's device")
+    if nchw_dtype is not None and nchw_dtype not in _DTYPES:
+        raise ValueError("nchw_dtype must be torch.float32, torch.bfloat16 or None")
+    f32 = lambda: torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)   # noqa: E731
+    out = {"h": torch.empty_like(x), "c_bf16": torch.empty_like(x), "m": torch.empty_like(x), "h_f32": f32(), "m_f32": f32(),
+           "c": c_out if c_out is not None else f32(), "alpha": f32(), "o_pre": f32()}
+    if nchw_dtype is not None:
+        out["h_nchw"] = torch.empty((b, c, h, w), dtype=nchw_dtype, device=x.device)
+    launch("v2v_nam_step_hip", x.device, ptr(x), ptr(m_t), ptr(h_prev), ptr(c_prev), ptr(packed), b, h, w, c, ptr(out["alpha"]), ptr(out["o_pre"]), ptr(out["m"]),
+           ptr(out["m_f32"]), ptr(out["c"]), ptr(out["c_bf16"]), ptr(out["h"]), ptr(out["h_f32"]), ptr(out.get("h_nchw")),
+           DTYPE_CODES.get(nchw_dtype, _lib.F32), tile, *((h, w) if valid is None else (int(valid[0]), int(valid[1]))))
+    if not return_workspaces:
+        del out["alpha"], out["o_pre"]
+    return out
+
+
+# ---- NER-Net's recurrent network (include/v2v_nam.h, v2v_amd/csrc/v2v_gcb.hpp): the global context block, the valid-extent helper ---------
+GCB_KEYS = ("conv_1x1.weight", "conv_1x1.bias", "GCB.conv_mask.weight", "GCB.conv_mask.bias", "GCB.channel_add_conv.0.weight", "GCB.channel_add_conv.0.bias",
+            "GCB.channel_add_conv.1.weight", "GCB.channel_add_conv.1.bias", "GCB.channel_add_conv.2.weight", "GCB.channel_add_conv.3.weight",
+            "GCB.channel_add_conv.3.bias")        # the reference's state_dict keys under one RecurrentConvLayer_NAM_GCB, in the order pack_gcb_weights takes them
+
+
+def pack_gcb_weights(*tensors):
+    """The eleven float32 tensors of GCB_KEYS (any trailing 1x1 dimensions) -> the tuple gcb_nhwc takes: each flat and contiguous, conv_1x1's
+    weight transposed to [Cin][Cout].  No arithmetic; goes through packed_weights like every other packing."""
+    if len(tensors) != len(GCB_KEYS):
+        raise ValueError(f"pack_gcb_weights takes the {len(GCB_KEYS)} tensors of GCB_KEYS")
+    c = tensors[0].shape[0]
+    shapes = ((c, c), (c,), (1, c), (1,), (c // 4, c), (c // 4,), (c // 4,), (c // 4,), (1,), (c, c // 4), (c,))
+    flat = []
+    for key, t, shape in zip(GCB_KEYS, tensors, shapes):
+        if not t.is_cuda or t.dtype != torch.float32 or t.device != tensors[0].device or t.numel() != shape[0] * (shape[1] if len(shape) > 1 else 1) \
+                or tuple(t.shape[:len(shape)]) != shape:
+            raise ValueError(f"{key} must be a float32 CUDA tensor {list(shape)} (+ 1x1 dimensions) on one device, C = {c}")
+        flat.append(t.detach().reshape(shape))
+    flat[0] = flat[0].t()
+    return tuple(t.contiguous().reshape(-1) for t in flat)
+
+
+def gcb_nhwc(x, packed, valid=None, eps: float = 1e-5, return_context: bool = False):
+    """out = x + g + add(ctx(g)), g = conv_1x1(x): RecurrentConvLayer_NAM_GCB's 1x1 convolution, ContextBlock2d (attention pooling,
+    channel_add) and the residual (model/nernet/submodules.py:365-442, :768-770) on NHWC bfloat16 [B,H,W,C], C in {32, 64, 128}, float32
+    arithmetic, three launches.  packed = pack_gcb_weights(...).  valid = (Hv, Wv): the pooling runs over rows < Hv and columns < Wv only
+    and out is zero elsewhere (None: the whole canvas).  return_context: also the float32 [B,2,C] tensor of ctx | add."""
+    _lib.require_gpu()
+    need("x", x)
+    b, h, w, c = x.shape
+    hv, wv = (h, w) if valid is None else (int(valid[0]), int(valid[1]))
+    if len(packed) != len(GCB_KEYS) or any(t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous() for t in packed) \
+            or [t.numel() for t in packed] != [c * c, c, c, 1, c * c // 4, c // 4, c // 4, c // 4, 1, c * c // 4, c]:
+        raise ValueError("packed must be the output of pack_gcb_weights for x's channel count, on x's device")
+    nbytes = _lib.lib().v2v_gcb_workspace_bytes(b, h, w, c)
+    if nbytes < 0:
+        _lib.check(int(nbytes))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    ctx_add = torch.empty((b, 2, c), dtype=torch.float32, device=x.device)
+    out = torch.empty_like(x)
+    launch("v2v_gcb_nhwc_hip", x.device, ptr(x), *(ptr(t) for t in packed), float(eps), b, h, w, c, hv, wv, ptr(ws), nbytes, ptr(ctx_add), ptr(out))
+    return (out, ctx_add) if return_context else out
+
+
+def to_nhwc16_bf16(x):
+    """float32 [B, 9 <= C <= 16, H, W] of any strides -> bfloat16 [B, H, W, 16] with the channels zero-padded to 16: conv_head16in_nhwc's
+    input layout (to_nhwc8_bf16 is the one for up to 8 channels)."""
+    _lib.require_gpu()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or not 9 <= x.shape[1] <= 16 or min(x.stride()) < 0:
+        raise ValueError("x must be a float32 CUDA tensor [B, 9 <= C <= 16, H, W]")
+    b, c, h, w = x.shape
+    out = torch.empty((b, h, w, 16), dtype=torch.bfloat16, device=x.device)
+    launch("v2v_to_nhwc16_bf16_hip", x.device, ptr(x), *x.stride(), b, c, h, w, ptr(out))
+    return out
+
+
+def pack_head16in_weights(weight):
+    """nn.Conv2d(9 <= Cin <= 16, 32, 5, padding=2).weight float32 -> the packed bfloat16 stream of conv_head16in_nhwc."""
+    _lib.require_gpu()
+    if not weight.is_cuda or weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[0] != 32 or not 9 <= weight.shape[1] <= 16 \
+            or tuple(weight.shape[2:]) != (5, 5):
+        raise ValueError("weight must be a float32 CUDA tensor [32, 9 <= Cin <= 16, 5, 5]")
+    packed = torch.empty((_lib.lib().v2v_conv_head16in_packed_elems(),), dtype=torch.bfloat16, device=weight.device)
+    launch("v2v_conv_head16in_pack_weights_hip", weight.device, ptr(weight.detach().contiguous()), weight.shape[1], ptr(packed))
+    return packed
+
+
+def conv_head16in_nhwc(x16, packed, bias, relu=True):
+    """out = [relu](conv5x5(x, pad 2) + bias): x16 [B,H,W,16] bfloat16 (to_nhwc16_bf16) -> [B,H,W,32] bfloat16, any H and W; the head
+    ConvLayer(2 * num_bins, 32, 5, padding=2) of NER-Net's UNetNIAM_STcell_GCB (model/nernet/unet.py)."""
+    _lib.require_gpu()
+    need("x16", x16, dims="[B,H,W,16]", last=16)
+    if bias.numel() != 32 or packed.dtype != torch.bfloat16 or packed.numel() != _lib.lib().v2v_conv_head16in_packed_elems() or packed.device != x16.device:
+        raise ValueError("bias must be [32] and packed the output of pack_head16in_weights, on x16's device")
+    b, h, w, _ = x16.shape
+    out = torch.empty((b, h, w, 32), dtype=torch.bfloat16, device=x16.device)
+    launch("v2v_conv_head16in_nhwc_hip", x16.device, ptr(x16), ptr(packed), ptr(bias.detach().float().contiguous()), int(bool(relu)), b, h, w, ptr(out))
+    return out
+
+
+def valid_extent_nhwc(x, valid, replicate: bool = False):
+    """In place on an NHWC canvas [B,H,W,C], bfloat16 or float32: pixels outside the valid extent valid = (Hv, Wv) are cleared; with
+    replicate, row Hv and column Wv take the nearest valid pixel instead (what upsample2x_nhwc must find there to compute, inside twice
+    the extent, the upsampling of the cropped tensor).  -> x"""
+    _lib.require_gpu()
+    if not isinstance(x, torch.Tensor) or x.dtype not in _DTYPES:
+        raise ValueError("x must be a contiguous float32 or bfloat16 CUDA tensor [B,H,W,C]")
+    need("x", x, x.dtype)
+    b, h, w, c = x.shape
+    launch("v2v_valid_extent_nhwc_hip", x.device, ptr(x), DTYPE_CODES[x.dtype], b, h, w, c, int(valid[0]), int(valid[1]), int(bool(replicate)))
+    return x
 
 
 # ---- backward: the data gradient of a convolution is the stride-1 convolution of the output gradient (spread onto the input grid for
